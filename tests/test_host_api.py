@@ -390,6 +390,33 @@ def test_committed_r06_bench_line_names_its_pipelining():
     assert "n_steps = 2" in alt["config"]["workload"] and 0.9 < alt["config"]["converged_fraction"] < d["extra_workloads"]["C5"]["config"]["converged_fraction"]
 
 
+def test_bench_dump_outputs_is_bounded_and_reproducible(tmp_path):
+    """bench.py --dump-outputs: every array as float64 .npy; a batch whose arrays fit is written whole, a larger one as the same seeded sample of
+    trajectories in every run (indices in trajectory_index.npy), the files below 64 MB in all."""
+    import sys
+    sys.path.insert(0, str(ROOT))
+    import bench
+    B, N, n, m = 8192, 201, 13, 4
+    big = {"states": np.arange(B * N * n, dtype=np.float64).reshape(B, N, n), "controls": np.ones((B, N - 1, m)),
+           "iterations": np.arange(B, dtype=np.int32), "cost": np.linspace(0.0, 1.0, B)}
+    for d in ("a", "b"):
+        bench.dump_outputs(big, str(tmp_path / d))
+    files = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert files == ["controls.npy", "cost.npy", "iterations.npy", "states.npy", "trajectory_index.npy"]
+    assert sum(p.stat().st_size for p in (tmp_path / "a").iterdir()) < 64e6
+    idx = np.load(tmp_path / "a" / "trajectory_index.npy").astype(np.int64)
+    assert 1000 < len(idx) < B and np.all(np.diff(idx) > 0)
+    for f in files:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype == np.float64 and np.array_equal(a, b), f
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "states.npy"), big["states"][idx])
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "iterations.npy"), idx)
+    small = {k: v[:1024] for k, v in big.items()}
+    bench.dump_outputs(small, str(tmp_path / "c"))
+    assert not (tmp_path / "c" / "trajectory_index.npy").exists()
+    np.testing.assert_array_equal(np.load(tmp_path / "c" / "states.npy"), small["states"])
+
+
 def test_rccl_stub_builds_and_exports_what_the_library_binds(tmp_path):
     """tests/rccl_stub (the shared-memory stand-in that lets several ranks share one GPU in the -m gpu suite) must export every nccl*
     entry point csrc/trajopt_hip.hip dlsym()s — checked here so that the GPU test cannot silently skip a symbol."""

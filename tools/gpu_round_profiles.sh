@@ -8,6 +8,7 @@ FINAL_FLAGS=--no-cpu-baseline PROFILE_COPY=${r}_quadrotor_altro_b8192 bash tools
 for b in 32768 131072 1048576; do
   FINAL_FLAGS=--no-cpu-baseline PROFILE_COPY=${r}_cartpole_b$b bash tools/run_profiles.sh ${r}_cartpole_b$b --workload cartpole --batch $b --steps 1 --warmup 1 > /dev/null 2>&1
 done
-python bench.py > gpurun_out/${r}_bench_default.json 2> gpurun_out/${r}_bench_default.err
+res=${OUT_DIR:-results}; mkdir -p "$res"
+python bench.py --full > "$res/${r}_bench_default.json" 2> "$res/${r}_bench_default.err"
 ls gpurun_out/${r}_*/kernel_stats.csv gpurun_out/${r}_*/hbm_traffic_pmc.json 2>&1 | head -20
-tail -c 300 gpurun_out/${r}_bench_default.err
+tail -c 300 "$res/${r}_bench_default.err"

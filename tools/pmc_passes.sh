@@ -10,5 +10,5 @@ export TMPDIR=/tmp; cd /tmp
 i=0
 for g in "${groups[@]}"; do
   i=$((i+1))
-  timeout 120 rocprofv3 --pmc $g -d "$out/p$i" -o p --output-format csv -- python "$repo/bench.py" "$@" --steps 1 --warmup 0 --no-cpu-baseline --no-profile > /dev/null 2> "$out/p$i.log"
+  timeout 120 rocprofv3 --pmc $g -d "$out/p$i" -o p --output-format csv -- python "$repo/bench.py" --full "$@" --steps 1 --warmup 0 --no-cpu-baseline --no-profile > /dev/null 2> "$out/p$i.log"
 done
