@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "common.h"
+#include "rp_plan.h"
 
 namespace to {
 
@@ -75,7 +76,7 @@ struct to_handle_s {
   int* d_crow = nullptr;    // [64] compact_row table of the model (tangent-matrix getters)
   std::vector<char> gl_set; // [n_costs] cost i carries per-trajectory linear terms (all clear: DevProblem::gl goes back to null)
   double* d_gl = nullptr;   // per-trajectory linear cost terms (DevProblem::gl), tiled, L = n_costs * (n + m); allocated on first use
-  double* d_cp = nullptr;   // per-trajectory constraint parameters (DevProblem::cp), tiled, L = n * n_cons; allocated on first use
+  double* d_cp = nullptr;   // per-trajectory constraint parameters (DevProblem::cp), tiled, L = (n + m) * number of constraints; allocated on first use
   double* d_tmp = nullptr;  // [Bp] scratch for reductions / outputs
   double* d_tmp2 = nullptr;
   // multi-GPU: RCCL communicator of the batch shards (to_comm_*; librccl is dlopen'ed on first use)
@@ -109,7 +110,7 @@ struct to_handle_s {
   std::vector<RpArr> rp_arr;
   std::vector<void*> rp_home, rp_work[2];
   int* rp_map[2] = {nullptr, nullptr};
-  int rp_cap[2] = {0, 0};
+  to::RpSized rp_sized[2];  // what each working set's buffers were sized for (rp_plan.h: re-used only for the same arrays within the capacity)
   int rp_level = 0;      // 0: the kernels work on the home arrays; else on rp_work[(rp_level - 1) & 1]
   int rp_B = 0, rp_Bp = 0;  // the batch of the handle while a solve works on a smaller set
   double rp_at = 0.7;    // ... the fraction of the working set that has to be left for a move (TRAJOPT_REPACK_AT)

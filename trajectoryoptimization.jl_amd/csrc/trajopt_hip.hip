@@ -348,7 +348,7 @@ int rp_setup(to_handle* h) {
   if ((int)h->rp_arr.size() > RP_MAX) return fail(TO_ERR_UNSUPPORTED, "repack table too long");
   return TO_OK;
 }
-size_t rp_bytes(const to_handle::RpArr& r, int Bp) { return (r.kind == 0 || r.kind == 3) ? sizeof(double) * (size_t)r.L * Bp : (r.kind == 1 ? sizeof(double) : sizeof(int)) * (size_t)Bp; }
+size_t rp_bytes(const to_handle::RpArr& r, int Bp) { return rp_slot_bytes({r.kind, r.L}, Bp); }
 // move the `count` active trajectories (list of the NEXT step, built by k_compact) into the other working set and go on there
 int rp_move(to_handle* h, int count) {
   KArgs& a = h->a;
@@ -360,22 +360,24 @@ int rp_move(to_handle* h, int count) {
     for (const auto& r : h->rp_arr) h->rp_home.push_back(rp_field(h, r.off));
     h->rp_B = a.P.B; h->rp_Bp = a.P.Bp;
   }
-  if (h->rp_cap[w] < Bp_new || h->rp_work[w].size() != h->rp_arr.size()) {  // (sized once per handle: the first move of a solve is the largest for this working set)
+  std::vector<RpSlot> need;
+  for (const auto& r : h->rp_arr) need.push_back({r.kind, r.L});
+  if (!rp_reusable(h->rp_sized[w], need, Bp_new)) {  // (rp_plan.h; as a rule sized once per configuration: the first move of a solve is the largest for this working set)
     for (void* q : h->rp_work[w]) if (q) g_free(h, q);
     h->rp_work[w].assign(h->rp_arr.size(), nullptr);
     if (h->rp_map[w]) g_free(h, h->rp_map[w]);
-    h->rp_map[w] = nullptr; h->rp_cap[w] = 0;
+    h->rp_map[w] = nullptr; h->rp_sized[w] = RpSized();
     // (+ one spare tile, like the home arrays: k_accept_roll's lanes without an accepted step store into the tile behind the batch)
     bool ok = true;
     for (size_t i = 0; ok && i < h->rp_arr.size(); ++i) ok = g_malloc(h, &h->rp_work[w][i], rp_bytes(h->rp_arr[i], Bp_new + 64), "repacked working set") == TO_OK;
-    ok = ok && g_malloc(h, (void**)&h->rp_map[w], sizeof(int) * Bp_new, "repack map") == TO_OK;
+    ok = ok && g_malloc(h, (void**)&h->rp_map[w], rp_map_bytes(Bp_new), "repack map") == TO_OK;
     if (!ok) {  // no memory for a working set: the repack is an optimisation — the solve goes on where it is (return value 1: declined)
       (void)hipGetLastError();
       for (void*& q : h->rp_work[w]) { if (q) g_free(h, q); q = nullptr; }
       if (h->rp_map[w]) { g_free(h, h->rp_map[w]); h->rp_map[w] = nullptr; }
       return 1;
     }
-    h->rp_cap[w] = Bp_new;
+    h->rp_sized[w].slots = need; h->rp_sized[w].cap = Bp_new;
   }
   RpArgs mv, hm;
   mv.n = hm.n = (int)h->rp_arr.size();
@@ -392,7 +394,7 @@ int rp_move(to_handle* h, int count) {
   auto dbg_sync = [&](const char* what) {
     if (!dbg) return;
     const hipError_t e = hipStreamSynchronize(h->stream);
-    std::fprintf(stderr, "[sync-debug] rp_move level %d -> %d count %d (B %d Bp %d, cap %d / %d) after %s: %s\n", lvl, lvl + 1, count, a.P.B, a.P.Bp, h->rp_cap[0], h->rp_cap[1], what, hipGetErrorString(e));
+    std::fprintf(stderr, "[sync-debug] rp_move level %d -> %d count %d (B %d Bp %d, cap %d / %d) after %s: %s\n", lvl, lvl + 1, count, a.P.B, a.P.Bp, h->rp_sized[0].cap, h->rp_sized[1].cap, what, hipGetErrorString(e));
   };
   dbg_sync("memsets");
   if (lvl > 0)  // what has finished in the set we leave goes home first (level 0 IS home)
@@ -1367,7 +1369,10 @@ int to_set_cost_linear_batch(to_handle* h, int32_t id, const double* q, const do
   if (c.kind == TO_COST_ERROR_QUADRATIC) return fail(TO_ERR_UNSUPPORTED, "per-trajectory linear terms: not for ErrorQuadratic (its q slot carries x_ref)");
   DevProblem& P = h->a.P;
   const int n = P.n, m = P.m, nz = n + m, L = (int)h->costs.size() * nz, B = P.B;
-  if (!h->d_gl) TRY(dev_alloc(h, &h->d_gl, (size_t)L * P.Bp));  // zero-filled: every cost starts with its descriptor's terms
+  if (!h->d_gl) {  // zero-filled: every cost starts with its descriptor's terms
+    TRY(dev_alloc(h, &h->d_gl, (size_t)L * P.Bp));
+    h->gl_set.assign(h->costs.size(), 0);  // sized with the array: to_set_cost indexes it whenever d_gl exists, also behind a failed upload below
+  }
   std::vector<double> delta;
   if (q) {  // stored as the difference from the descriptor's q: the kernels ADD it to what the shared code path computes
     delta.resize((size_t)n * B);
@@ -1380,7 +1385,6 @@ int to_set_cost_linear_batch(to_handle* h, int32_t id, const double* q, const do
     TRY(upload_vec(h, delta.data(), h->d_gl, m, L, id * nz + n));
   }
   P.gl = h->d_gl;
-  h->gl_set.resize(h->costs.size(), 0);
   h->gl_set[id] = 1;
   return TO_OK;
 }
