@@ -18,6 +18,8 @@
  *   to_expand / to_backward / to_forward / to_ilqr_solve / to_al_solve
  *                               <- the Altro.jl iLQR / AL loops that consume a Problem
  *                                  (out of tree; SURVEY.md §8a rows E1,S1-S4)
+ *   to_policy_rollout           <- rollout!(prob) src/problem.jl:330-340 and Altro's rollout!(solver, α), from S start states
+ *                                  per trajectory instead of the problem's x0
  *   to_set_* / to_get_*         <- initial_controls!/initial_states!/set_initial_state!/states/controls
  *                                  src/problem.jl:198-310
  *
@@ -56,8 +58,9 @@ extern "C" {
  * a descriptor stamped with another version.  5: TO_MODEL_INFEASIBLE, to_infeasible_controls, to_set_cost_linear_batch, to_get_cost_to_go.
  * 6: to_solve_progress / to_solve_wait_below (pipelined solves over several handles), to_set_constraint_params_batch /
  * to_clear_constraint_params_batch (one GoalConstraint target per trajectory); TO_STATE_LIMIT / TO_CONTROL_LIMIT are
- * emitted; TRAJOPT_RCCL_LIB, TRAJOPT_GUARD. */
-#define TO_ABI_VERSION 6
+ * emitted; TRAJOPT_RCCL_LIB, TRAJOPT_GUARD.  7: to_policy_rollout with to_policy_opts / to_policy_result (closed-loop rollouts of
+ * S perturbed samples per trajectory under the solved feedback law). */
+#define TO_ABI_VERSION 7
 
 #define TO_MAX_N 16       /* max state dimension            */
 #define TO_MAX_M 8        /* max control dimension          */
@@ -437,6 +440,45 @@ int to_get_gains(to_handle* h, double* K, double* d, double* dV, double* rho);
  * with the Q-function blocks of knot k (to_get_cost_expansion holds l_xx etc.; Q = l + [A B]'S_{k+1}[A B]).  Needs to_expand + to_backward
  * (phase API) on a handle whose backward pass keeps its expansion in memory (not inside a fused solve). */
 int to_get_cost_to_go(to_handle* h, double* S, double* s);
+
+/* ---- closed-loop policy rollouts ----------------------------------------------------------------
+ * The solved time-varying feedback law, applied: S samples per trajectory, sample s of trajectory b started at x0s[:, s, b], simulated
+ * over the whole horizon under   u_k = ū_k + α d_k + K_k (x_k (-) x̄_k)   with the handle's nominal (X, U) and the gains of its last
+ * backward pass.  It extends rollout! (src/problem.jl:330-340) and Altro's rollout!(solver, α), which apply that law from the
+ * problem's own x0 only (inside the line search): this is the step between two MPC re-solves (S = 1, the measured state) and the
+ * Monte-Carlo robustness check of a solved trajectory (S large; start-state errors, actuator saturation, a plant that differs from
+ * the planning model).  Per sample, in this order (the forward pass's):  x_1 = x0s[:, s, b];  for k = 1 .. N-1:  dx = state_diff(x_k,
+ * x̄_k);  u_k = ū_k + α d_k + K_k dx, clamped to [u_min, u_max];  stage cost (cost_dt_scaling honoured), violation and |dx| at (x_k, u_k);
+ * x_{k+1} = one step of the plant;  then cost, violation and |dx| of the terminal knot.
+ * Limits: the test of to_rollout — after every step, the state it arrives at against max_state_value first, then the control it
+ * applied against max_control_value.  The first sample to fail gets status TO_STATE_LIMIT / TO_CONTROL_LIMIT, k_limit = the (1-based)
+ * knot whose step failed, and J = c_max = dx_max = +inf; its X / U behind that knot are unspecified.  Other samples are not affected.
+ * The handle's own state (X, U, duals, penalties, per-trajectory parameters) is not modified; refresh_gains = 1 leaves the expansion
+ * and the gains exactly as to_expand followed by to_backward would.  Hybrid models and model vectors take x0s at the storage
+ * dimensions (to_dims), the padding zero.  Errors: S < 1 -> TO_ERR_ARGUMENT; NULL x0s / out -> TO_ERR_NULL; a solve in flight on the
+ * handle -> TO_ERR_ARGUMENT. */
+typedef struct {
+  int32_t refresh_gains;      /* 1: run the expansion + backward pass on the handle's current (X, U) first (what to_expand + to_backward do);
+                                 0: use the gains of the last backward pass, i.e. what to_get_gains returns now */
+  int32_t reserved;
+  double alpha;               /* feed-forward scale: 0 = pure tracking law (TVLQR), 1 = the full iLQR step */
+  const double* u_min;        /* [m] or NULL: saturation, applied to u after the feedback law */
+  const double* u_max;        /* [m] or NULL */
+  const double* plant_params; /* [16] or NULL: model_params of the SIMULATED plant (the policy stays the planning model's).  Entries that
+                                 select dimensions or the attitude representation (double integrator D, hybrid S, quadrotor rotation,
+                                 infeasible base id) must equal the problem's: TO_ERR_ARGUMENT otherwise.  Model vectors: NULL only. */
+} to_policy_opts;
+typedef struct {              /* HOST arrays, any may be NULL; sample index fastest, then trajectory */
+  double* J;        /* [S,B]  objective cost of the closed-loop trajectory, cost(prob) semantics (no AL terms; the trajectory's own q/r if set) */
+  double* c_max;    /* [S,B]  max constraint violation along it, to_max_violation semantics (the trajectory's own constraint parameters if set) */
+  double* dx_max;   /* [S,B]  max over knots 1..N of |x_k (-) xbar_k|_inf (error state) */
+  int32_t* status;  /* [S,B]  0 = completed; TO_STATE_LIMIT / TO_CONTROL_LIMIT = left max_state_value / max_control_value */
+  int32_t* k_limit; /* [S,B]  1-based knot of that event, 0 otherwise */
+  double* X;        /* [n,N,S,B]   closed-loop states   (only stored when non-NULL) */
+  double* U;        /* [m,N-1,S,B] applied controls */
+} to_policy_result;
+int to_policy_rollout(to_handle* h, int32_t S, const double* x0s /* [n,S,B] */, const to_policy_opts* opts /* NULL = {1,0,0.0,NULL,NULL,NULL} */,
+                      const to_policy_result* out);
 
 /* raw (non error-state) per-knot cost derivatives of the objective at the current trajectory
  * (RD.gradient! / RD.hessian!): grad[(n+m),N,B], hess[(n+m),(n+m),N,B] */

@@ -20,7 +20,7 @@ const TO = TrajectoryOptimization
 const lib = get(ENV, "TRAJOPT_HIP_LIBRARY", "libtrajopt_hip")   # trajectoryoptimization.jl_amd/csrc/libtrajopt_hip.so
 
 # ------------------------------------------------------------------------------------------------ header mirrors
-const TO_ABI_VERSION = Int32(6)
+const TO_ABI_VERSION = Int32(7)
 const MAXN, MAXM, MAXP, MAXPAR, MAXIND = 16, 8, 40, 400, 48
 const PROFILE_SLOTS = 4
 
@@ -131,6 +131,25 @@ mutable struct SolveStats            # == to_solve_stats
     batch_steps::Int32
     reserved::Int32
     solve_ms::Float64
+end
+
+struct PolicyOpts                    # == to_policy_opts
+    refresh_gains::Int32
+    reserved::Int32
+    alpha::Float64
+    u_min::Ptr{Float64}
+    u_max::Ptr{Float64}
+    plant_params::Ptr{Float64}
+end
+
+struct PolicyResult                  # == to_policy_result (host arrays, sample index fastest, then trajectory)
+    J::Ptr{Float64}
+    c_max::Ptr{Float64}
+    dx_max::Ptr{Float64}
+    status::Ptr{Int32}
+    k_limit::Ptr{Int32}
+    X::Ptr{Float64}
+    U::Ptr{Float64}
 end
 
 @enum SolverStatus::Int32 UNSOLVED = 0 LINESEARCH_FAIL SOLVE_SUCCEEDED MAX_ITERATIONS MAX_ITERATIONS_OUTER MAXIMUM_COST STATE_LIMIT CONTROL_LIMIT NO_PROGRESS COST_INCREASE REGULARIZATION_MAX PROJECTION_FAIL
@@ -593,6 +612,37 @@ function gains(p::BatchProblem)
     (K = K, d = d, dV = dV, rho = rho)
 end
 """
+    policy_rollout(p::BatchProblem, X0s; alpha = 0.0, refresh_gains = true, u_min = nothing, u_max = nothing, plant = nothing, trajectories = false)
+Closed-loop rollouts of the solved feedback law `u = ū_k + α d_k + K_k (x ⊖ x̄_k)` (`to_policy_rollout`; `rollout!(prob)`, src/problem.jl:330-340,
+and Altro's `rollout!(solver, α)` from other start states): `X0s :: (n, S, B)`, sample `s` of trajectory `b` starts at `X0s[:, s, b]`.  The step
+between two MPC re-solves (S = 1, the measured state) and the Monte-Carlo check of a solved trajectory (S large).  `u_min` / `u_max`: a
+number or a length-m vector, applied after the law; `plant`: the 16 model parameters of the simulated plant (`modelparams` of a model
+of the problem's type).  Returns `(J, c_max, dx_max, status, k_limit)`, each `(S, B)`, plus `X :: (n, N, S, B)` and `U :: (m, N-1, S, B)`
+when `trajectories` (else `nothing`).
+"""
+function policy_rollout(p::BatchProblem, X0s::Array{Float64,3}; alpha::Real = 0.0, refresh_gains::Bool = true, u_min = nothing,
+                        u_max = nothing, plant::Union{Nothing,Vector{Float64}} = nothing, trajectories::Bool = false)
+    size(X0s, 1) == p.n && size(X0s, 3) == p.B && size(X0s, 2) >= 1 || throw(DimensionMismatch("X0s must be (n, S, B)"))
+    S = size(X0s, 2)
+    clampvec(v) = v === nothing ? Float64[] : (v isa Real ? fill(Float64(v), p.m) : Vector{Float64}(v))
+    lo, hi = clampvec(u_min), clampvec(u_max)
+    (isempty(lo) || length(lo) == p.m) && (isempty(hi) || length(hi) == p.m) || throw(DimensionMismatch("u_min / u_max must have length m"))
+    plant === nothing || length(plant) == 16 || throw(DimensionMismatch("plant must hold the 16 model parameters"))
+    J, c_max, dx_max = zeros(S, p.B), zeros(S, p.B), zeros(S, p.B)
+    status, k_limit = zeros(Int32, S, p.B), zeros(Int32, S, p.B)
+    X = trajectories ? zeros(p.n, p.N, S, p.B) : nothing
+    U = trajectories ? zeros(p.m, p.N - 1, S, p.B) : nothing
+    pp = plant === nothing ? Float64[] : plant
+    GC.@preserve lo hi pp J c_max dx_max status k_limit X U begin
+        opts = Ref(PolicyOpts(Int32(refresh_gains), Int32(0), Float64(alpha), isempty(lo) ? Ptr{Float64}(C_NULL) : pointer(lo),
+            isempty(hi) ? Ptr{Float64}(C_NULL) : pointer(hi), isempty(pp) ? Ptr{Float64}(C_NULL) : pointer(pp)))
+        out = Ref(PolicyResult(pointer(J), pointer(c_max), pointer(dx_max), pointer(status), pointer(k_limit),
+            trajectories ? pointer(X) : Ptr{Float64}(C_NULL), trajectories ? pointer(U) : Ptr{Float64}(C_NULL)))
+        check(ccall((:to_policy_rollout, lib), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ref{PolicyOpts}, Ref{PolicyResult}), p.handle, Int32(S), X0s, opts, out))
+    end
+    (J = J, c_max = c_max, dx_max = dx_max, status = status, k_limit = k_limit, X = X, U = U)
+end
+"""
     TO.set_goal_state!(p::BatchProblem, Xf::Matrix)        # Xf :: (n, B): one goal per trajectory
 `set_LQR_goal!(cost, xf_b)` (src/cost_functions.jl:249-252: q = -Q xf, nothing else) on every cost of the objective for every
 trajectory of the batch — batched MPC / goal sweeps on one handle (SURVEY §8b) — and, with `constraint = true` (the reference's default,
@@ -781,7 +831,7 @@ function profile(p::BatchProblem)
     (kernel_ms = ms, launches = launches)
 end
 
-export LinearMap, MassDoubleIntegrator, BatchProblem, SolverOpts, solver_options, default_options, solve_ilqr!, solve_al!, solve_pn!, solve_altro!, solve_async!, wait_solve!, dynamics_defect, expand!, backwardpass!, forwardpass!,
+export LinearMap, MassDoubleIntegrator, BatchProblem, policy_rollout, PolicyOpts, PolicyResult, SolverOpts, solver_options, default_options, solve_ilqr!, solve_al!, solve_pn!, solve_altro!, solve_async!, wait_solve!, dynamics_defect, expand!, backwardpass!, forwardpass!,
     stage_costs, al_cost, dynamics_jacobians, cost_expansion, gains, cost_gradient_hessian, discrete_jacobian, duals, set_duals!,
     reset_duals!, dual_update!, comm_unique_id, comm_init_rank!, allgather!, allgather_stats, comm_shards, comm_destroy!, solver_path, knot_dims, device_count, build_id
 

@@ -13,7 +13,7 @@ import ctypes as C
 import os
 from pathlib import Path
 
-TO_ABI_VERSION = 6
+TO_ABI_VERSION = 7
 TO_MAX_N, TO_MAX_M, TO_MAX_P = 16, 8, 40
 TO_MAX_CON_PARAMS, TO_MAX_CON_INDS = 400, 48
 
@@ -140,6 +140,21 @@ class SolveStats(C.Structure):
     ]
 
 
+class PolicyOpts(C.Structure):
+    _fields_ = [
+        ("refresh_gains", C.c_int32), ("reserved", C.c_int32), ("alpha", C.c_double),
+        ("u_min", C.POINTER(C.c_double)), ("u_max", C.POINTER(C.c_double)), ("plant_params", C.POINTER(C.c_double)),
+    ]
+
+
+class PolicyResult(C.Structure):
+    _fields_ = [
+        ("J", C.POINTER(C.c_double)), ("c_max", C.POINTER(C.c_double)), ("dx_max", C.POINTER(C.c_double)),
+        ("status", C.POINTER(C.c_int32)), ("k_limit", C.POINTER(C.c_int32)),
+        ("X", C.POINTER(C.c_double)), ("U", C.POINTER(C.c_double)),
+    ]
+
+
 _H = C.c_void_p
 _PD = C.POINTER(C.c_double)
 _PI = C.POINTER(C.c_int32)
@@ -222,6 +237,7 @@ HIP_ONLY = {
     "solve_wait": [_H],
     "solve_progress": [_H, _PI, _PI, _PI],
     "solve_wait_below": [_H, C.c_int32],
+    "policy_rollout": [_H, C.c_int32, _PD, C.POINTER(PolicyOpts), C.POINTER(PolicyResult)],  # the oracle has no closed-loop rollout
 }
 
 

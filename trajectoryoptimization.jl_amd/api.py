@@ -42,7 +42,7 @@ __all__ = [
     "GoalConstraint", "BoundConstraint", "NormConstraint", "CircleConstraint", "SphereConstraint", "CollisionConstraint", "QuatVecEq",
     "LinearConstraint", "StateBound", "ControlBound", "IndexedConstraint", "change_dimension",
     "ConstraintList", "add_constraint", "num_constraints", "constraint_hessians",
-    "KnotPoint", "Problem", "rollout", "cost", "states", "controls", "initial_controls", "initial_states",
+    "KnotPoint", "Problem", "rollout", "policy_rollout", "PolicyRollout", "cost", "states", "controls", "initial_controls", "initial_states",
     "set_initial_state", "set_goal_state", "update_trajectory", "get_constraints", "get_objective", "get_model",
     "get_initial_state", "get_final_state", "get_trajectory", "gettimes",
     "SolverOptions", "iLQRSolver", "ALSolver", "ALTROSolver", "ProjectedNewtonSolver", "dynamics_defect", "solve", "SolvePipeline", "iterations", "status", "max_violation",
@@ -1345,6 +1345,63 @@ def controls(prob):
 def rollout(prob):
     """rollout!(prob)  (src/problem.jl:330-340)."""
     prob._call("rollout")
+
+
+class PolicyRollout:
+    """Result of ``policy_rollout``: ``J``, ``c_max``, ``dx_max`` (float) and ``status``, ``k_limit`` (int32), each [B, S]; ``X`` [B, S, N, n]
+    and ``U`` [B, S, N-1, m] when the trajectories were asked for, else None."""
+
+    def __init__(self, J, c_max, dx_max, status, k_limit, X=None, U=None):
+        self.J, self.c_max, self.dx_max, self.status, self.k_limit, self.X, self.U = J, c_max, dx_max, status, k_limit, X, U
+
+
+def policy_rollout(prob, X0s, alpha=0.0, refresh_gains=True, u_min=None, u_max=None, plant=None, trajectories=False):
+    """Closed-loop rollouts of the solved feedback law (to_policy_rollout; extends rollout!(prob), src/problem.jl:330-340, and Altro's
+    rollout!(solver, α)): sample ``s`` of trajectory ``b`` starts at ``X0s[b, s]`` and is simulated under
+    ``u = ū_k + alpha d_k + K_k (x ⊖ x̄_k)`` with the problem's nominal trajectory and gains.
+
+    ``X0s`` is [B, S, n] (hybrid models / model vectors: the storage dimension, padding zero).  ``refresh_gains=True`` runs the expansion
+    and the backward pass at the current trajectory first; False uses the gains of the last backward pass.  ``u_min`` / ``u_max``: scalar
+    or [m] saturation applied after the law.  ``plant``: a model of the problem's class whose parameters the SIMULATION uses (the law
+    stays the planning model's).  Returns a ``PolicyRollout``."""
+    if "policy_rollout" not in prob._lib._fn:
+        raise NotImplementedError("policy_rollout needs the HIP library (the CPU oracle has no closed-loop rollout)")
+    a = np.asarray(X0s, dtype=np.float64)
+    if a.ndim != 3 or a.shape[0] != prob.B or a.shape[2] != prob.n or a.shape[1] < 1:
+        raise DimensionMismatch(f"X0s must be [B={prob.B}, S >= 1, n={prob.n}]; got {a.shape}")
+    a = np.ascontiguousarray(a)
+    B, S, N, n, m = prob.B, a.shape[1], prob.N, prob.n, prob.m
+    o = capi.PolicyOpts()
+    o.refresh_gains, o.alpha = (1 if refresh_gains else 0), float(alpha)
+    keep = []
+
+    def clampvec(v, name):
+        v = np.asarray(v, dtype=np.float64)
+        v = np.full(m, float(v)) if v.ndim == 0 else _vec(v, m, name)
+        keep.append(np.ascontiguousarray(v))
+        return prob._pd(keep[-1])
+    if u_min is not None:
+        o.u_min = clampvec(u_min, "u_min")
+    if u_max is not None:
+        o.u_max = clampvec(u_max, "u_max")
+    if plant is not None:
+        if type(plant) is not type(prob.model) or plant.dims() != prob.model.dims():
+            raise ArgumentError(f"plant must be a {type(prob.model).__name__} with the problem's dimensions; got {type(plant).__name__}")
+        pp = np.zeros(16)
+        p = plant.params()
+        pp[: len(p)] = p
+        keep.append(pp)
+        o.plant_params = prob._pd(pp)
+    J, cm, dxm = np.empty((B, S)), np.empty((B, S)), np.empty((B, S))
+    st, kl = np.empty((B, S), np.int32), np.empty((B, S), np.int32)
+    X = np.empty((B, S, N, n)) if trajectories else None
+    U = np.empty((B, S, N - 1, m)) if trajectories else None
+    r = capi.PolicyResult()
+    r.J, r.c_max, r.dx_max, r.status, r.k_limit = prob._pd(J), prob._pd(cm), prob._pd(dxm), prob._pi(st), prob._pi(kl)
+    if trajectories:
+        r.X, r.U = prob._pd(X), prob._pd(U)
+    prob._call("policy_rollout", S, prob._pd(a), C.byref(o), C.byref(r))
+    return PolicyRollout(J, cm, dxm, st, kl, X, U)
 
 
 def cost(prob):

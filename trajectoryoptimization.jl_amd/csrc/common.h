@@ -80,6 +80,25 @@ struct KArgs {
                   // k_accept_roll (k_forward.h) then re-rolls the accepted candidates.  Set per batch step by the solve loop.
 };
 
+// One launch of the closed-loop policy rollout (k_policy.h): S samples per trajectory, sample index c = b*S + s.  Waves are numbered
+// over the whole batch — uniform map: wave g = b*WPT + s/64, lane s%64; packed map: wave g = b/TPW, lane s*TPW + b%TPW — and a launch
+// covers the waves [g0, g0 + gridDim.x) (every wave of the batch, or one chunk of them when the trajectories are wanted).
+struct PolicyArgs {
+  int S;
+  int TPW;     // packed map: trajectories per wave (64 / S); 0: uniform map
+  int WPT;     // uniform map: waves per trajectory (ceil(S / 64))
+  int g0;      // first wave of this launch
+  int store;   // 1: closed-loop states / controls go to Xw / Uw
+  int clamp;   // 1: u is clamped to [u_min, u_max] after the feedback law
+  double alpha;
+  double u_min[TO_MAX_M], u_max[TO_MAX_M];
+  double mp[16];       // model parameters of the simulated plant
+  const double* x0s;   // [n, S, B] start states, host layout
+  double *J, *cmax, *dxmax;  // [S*B] per-sample results, sample fastest
+  int *status, *klim;
+  double *Xw, *Uw;     // sample-fastest staging of this launch: [wave - g0][N*n][64], [wave - g0][(N-1)*m][64]
+};
+
 // gains row of one knot of one trajectory: m rows of (ne gains + 1 feed-forward) doubles
 template <class M> struct Gains { static constexpr int RSK = M::m * (M::ne + 1); };
 

@@ -115,6 +115,13 @@ struct to_handle_s {
   int rp_B = 0, rp_Bp = 0;  // the batch of the handle while a solve works on a smaller set
   double rp_at = 0.7;    // ... the fraction of the working set that has to be left for a move (TRAJOPT_REPACK_AT)
   int rp_min = 16384;    // repack once the active count has halved, while the set holds at least this many (TRAJOPT_REPACK=0: never)
+  // closed-loop policy rollouts (to_policy_rollout): start states and per-sample results, sized for the largest S*B seen so far, and
+  // the sample-fastest staging of one chunk of waves when the trajectories are wanted
+  double *pol_x0s = nullptr, *pol_J = nullptr, *pol_cmax = nullptr, *pol_dxmax = nullptr;
+  int *pol_status = nullptr, *pol_klim = nullptr;
+  size_t pol_cap = 0;        // samples the arrays above hold
+  double *pol_xw = nullptr, *pol_uw = nullptr;
+  int pol_waves = 0;         // waves the staging holds
   // asynchronous solves (to_*_solve_async / to_solve_wait)
   std::thread worker;
   std::atomic<bool> inflight{false};
@@ -181,6 +188,7 @@ struct ModelOps {
   int (*pn_launch)(to_handle*, int slot0, int count, hipStream_t stream, const to_solver_opts* opts) = nullptr;  // ... and its launches
   int (*defect)(to_handle*, double* out) = nullptr;             // max dynamics / initial-condition defect of the nominal trajectory
   int (*infeasible_controls)(to_handle*) = nullptr;             // InfeasibleModel only: slack controls from the current states (k_misc.h)
+  int (*policy_rollout)(to_handle*, const PolicyArgs& pa, int waves) = nullptr;  // closed-loop policy rollout of `waves` waves from pa.g0 (k_policy.h)
   int (*accept_roll)(to_handle*) = nullptr;  // accept by re-rolling the stored controls (k_forward.h; models without write-through)
   int (*forward[32])(to_handle*) = {};  // by kernel variant (k_forward.h MODE bits); variants a model never uses stay null
   int (*forward2[32])(to_handle*) = {};  // the same variants as two-wave workgroups (k_forward2; models with LDS-staged gains)
@@ -213,6 +221,7 @@ void fill_ops_pn(ModelOps* table);
 void fill_ops_vector(ModelOps* table);
 void fill_ops_infeasible_a(ModelOps* table);
 void fill_ops_infeasible_b(ModelOps* table);
+void fill_ops_policy(ModelOps* table);
 
 // handle-owned device memory (red zones around it in guard mode); g_free accepts what g_malloc returned
 int g_malloc(to_handle* h, void** p, size_t bytes, const char* name);

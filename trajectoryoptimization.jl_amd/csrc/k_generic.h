@@ -281,6 +281,20 @@ __global__ void k_to_host(const double* __restrict__ d, double* __restrict__ h, 
   if (b >= B) return;
   h[(size_t)e + (size_t)cnt * b] = EL(TILE_PTR(d, L), e0 + e);
 }
+// policy rollout (k_policy.h): the sample-fastest staging blocks W[wave - g0][L][64] of one launch -> host layout out[e + L*(c - c0)]
+// for the samples c0 .. c0 + cnt - 1 that launch covers (c = b*S + s; PolicyArgs in common.h gives the wave and lane of a sample).
+// grid (ceil(cnt / 64), min(L, 65535)): consecutive threads read consecutive lanes of a row.
+__global__ void k_policy_to_host(const double* __restrict__ W, double* __restrict__ out, int L, int S, int TPW, int WPT, int g0, long long c0,
+                                 long long cnt) {
+  const long long i = (long long)blockIdx.x * 64 + threadIdx.x;
+  if (i >= cnt) return;
+  const long long c = c0 + i;
+  const int b = (int)(c / S), s = (int)(c - (long long)b * S);
+  const int g = TPW ? b / TPW : b * WPT + s / 64;
+  const int lane = TPW ? s * TPW + (b - g * TPW) : s % 64;
+  const double* w = W + ((size_t)(g - g0) * (size_t)L) * 64 + lane;
+  for (int e = blockIdx.y; e < L; e += gridDim.y) out[(size_t)e + (size_t)L * i] = w[(size_t)e * 64];
+}
 __global__ void k_fill_uniform(double* d, const double* u, int dim, int L, int B) {
   TILE_LANE();
   const int e = blockIdx.y;

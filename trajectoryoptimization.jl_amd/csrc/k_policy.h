@@ -1,0 +1,168 @@
+// k_policy.h — closed-loop policy rollouts (to_policy_rollout): S perturbed samples per solved trajectory under the time-varying
+// feedback law of the last backward pass,  u = ū_k + α d_k + K_k (x ⊖ x̄_k),  optionally saturated and on a plant whose parameters
+// differ from the planning model's.  The operator extends rollout! (src/problem.jl:330-340) / Altro's rollout!(solver, α), which
+// apply the same law from the problem's own x0 only.
+//
+// Lanes are SAMPLES.  Two lane maps share one body (PolicyArgs, common.h):
+//   uniform (S > 32)  a wave = 64 samples of ONE trajectory b = wave / WPT.  b comes from blockIdx, so x̄_k, ū_k and the gains row
+//                     Kt + (b (N-1) + k) RSK have wave-uniform addresses: they are read once per wave, a knot ahead, through the
+//                     constant address space (scalar loads, like the descriptor tables of problem_dev.h) — rows of more than 12
+//                     doubles with one vector load per wave (every lane asks for the same address), the Quadrotor's 52-double
+//                     row by the forward pass's LDS DMA (stage_gains with one row per wave).
+//   packed  (S <= 32) a wave = TPW = 64 / S trajectories x S samples, hardware lane s * TPW + t (the forward pass's map, k_forward.h:
+//                     lane t < TPW holds trajectory t, which is what stage_gains expects); per-lane pointers into the tiled nominal.
+// Lanes without a sample (tail of the last wave of a trajectory, tail of a packed wave) roll out a copy of a live one and store
+// nothing but their own column of the wave's staging block; a sample beyond max_state_value / max_control_value keeps stepping.
+// The loop has no lane-divergent region.
+#pragma once
+#include "common.h"
+#include "k_forward.h"
+
+namespace to {
+
+template <bool SC>
+__device__ __forceinline__ double policy_ld(const double* p) {
+  if constexpr (SC) return *(DoubleC*)p;  // wave-uniform address of data no kernel in flight writes: scalar load
+  else return *p;
+}
+
+// nominal state / control of one knot and, for the models that do not stage gains through LDS, its gains row
+template <class M, bool XSC, bool KSC, bool WITHK>
+struct PolicyKnot {
+  static constexpr int n = M::n, m = M::m, RSK = Gains<M>::RSK;
+  double x[n], u[m], kd[WITHK ? RSK : 1];
+  __device__ __forceinline__ void load_x(const double* pXk) {
+#pragma unroll
+    for (int i = 0; i < n; ++i) x[i] = policy_ld<XSC>(&EL(pXk, i));
+  }
+  __device__ __forceinline__ void load_uk(const double* pUk, const double* pKk) {
+#pragma unroll
+    for (int j = 0; j < m; ++j) u[j] = policy_ld<XSC>(&EL(pUk, j));
+    if constexpr (WITHK) {
+#pragma unroll
+      for (int i = 0; i < RSK; ++i) kd[i] = policy_ld<KSC>(pKk + i);
+    }
+  }
+};
+
+template <class M, bool UNIFORM, int FI>
+__global__ void __launch_bounds__(64) k_policy_rollout(KArgs a, PolicyArgs pa) {
+  constexpr int n = M::n, m = M::m, ne = M::ne, RSK = Gains<M>::RSK;
+  constexpr bool KLDS = M::lds_gains;
+  constexpr bool KSC = UNIFORM && !KLDS && RSK <= 12;
+  extern __shared__ double kbuf[];
+  const DevProblem& P = a.P;
+  const int N = P.N, S = pa.S, hw = threadIdx.x;
+  const int g = pa.g0 + blockIdx.x;
+  int b, s, t = 0;
+  if constexpr (UNIFORM) { b = g / pa.WPT; s = (g - b * pa.WPT) * 64 + hw; }
+  else { s = hw / pa.TPW; t = hw - s * pa.TPW; b = g * pa.TPW + t; }
+  const bool live = s < S && b < P.B;
+  s = s < S ? s : S - 1;
+  b = b < P.B ? b : P.B - 1;
+  const size_t c = (size_t)b * S + s;  // sample index: sample fastest, then trajectory
+  const int tile = b >> 6, lane = b & 63;
+  const int TW = UNIFORM ? 1 : pa.TPW;
+  const int kbuf_len = KLDS ? gains_lds_doubles<M>(TW) : 0, krow = t * RSK;
+  const double* Xc = TILE_PTR(a.Xs, N * n);  // the nominal
+  const double* Uc = TILE_PTR(a.Us, (N - 1) * m);
+  const double* pK = a.Kt + ((size_t)b * (N - 1)) * RSK;
+  // closed-loop states / controls: block [wave of this launch][element][64], every lane its own column (whole 512-byte rows)
+  double* pXo = pa.Xw + ((size_t)blockIdx.x * (size_t)(N * n)) * 64 + hw;
+  double* pUo = pa.Uw + ((size_t)blockIdx.x * (size_t)((N - 1) * m)) * 64 + hw;
+  const double* gl0 = TILE_PTR(P.gl, P.n_costs * (n + m));
+  const double* cp0 = TILE_PTR(P.cp, P.n_cp);
+  double mp[16];  // the PLANT's parameters; the law's x̄, ū, K, d are the planning model's
+#pragma unroll
+  for (int i = 0; i < 16; ++i) mp[i] = in_vgpr(pa.mp[i]);
+  const int integrator = P.integrator;
+  const double max_x = P.opts.max_state_value, max_u = P.opts.max_control_value;
+  const double alpha = pa.alpha;
+  const bool has_cons = P.n_cons > 0, store = pa.store != 0, clamp = pa.clamp != 0;
+  double xb[n];
+  {
+    const double* px0 = pa.x0s + c * n;
+#pragma unroll
+    for (int i = 0; i < n; ++i) xb[i] = px0[i];
+  }
+  if constexpr (KLDS) stage_gains<M>(a.Kt, b, TW, 0, N, kbuf, hw);
+  PolicyKnot<M, UNIFORM, KSC, !KLDS> nxt;
+  nxt.load_x(Xc);
+  nxt.load_uk(Uc, pK);
+  const double *pXn = Xc + n * 64, *pUn = Uc + m * 64, *pKn = pK + RSK;  // knot k+1 of the nominal
+  double J = 0.0, cm = 0.0, dxm = 0.0;
+  int lim = 0, klim = 0;
+  for (int k = 0; k < N - 1; ++k) {
+    if constexpr (KLDS) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this knot's gains row has landed in LDS
+    const PolicyKnot<M, UNIFORM, KSC, !KLDS> cur = nxt;
+    const double* kcur = kbuf + (size_t)(k & 1) * kbuf_len + krow;
+    // the next knot's nominal and gains are requested first: nothing issued here is needed before the next iteration
+    if (k + 1 < N - 1) {
+      if constexpr (KLDS) stage_gains<M>(a.Kt, b, TW, k + 1, N, kbuf + (size_t)((k + 1) & 1) * kbuf_len, hw);
+      nxt.load_uk(pUn, pKn);
+    }
+    nxt.load_x(pXn);  // (k + 1 = N - 1: the terminal knot's x̄, for its |dx|)
+    pXn += n * 64; pUn += m * 64; pKn += RSK;
+    if (store) {
+#pragma unroll
+      for (int i = 0; i < n; ++i) EL(pXo, i) = xb[i];
+      pXo += n * 64;
+    }
+    double dx[ne], ub[m], xn[n];
+    state_diff<M>(xb, cur.x, dx);
+#pragma unroll
+    for (int i = 0; i < ne; ++i) { const double v = fabs(dx[i]); if (!(v <= dxm)) dxm = v; }
+#pragma unroll
+    for (int j = 0; j < m; ++j) {
+      double kr[ne + 1];
+#pragma unroll
+      for (int i = 0; i <= ne; ++i) kr[i] = KLDS ? kcur[j * (ne + 1) + i] : cur.kd[KLDS ? 0 : j * (ne + 1) + i];
+      if constexpr (KLDS) __builtin_amdgcn_sched_barrier(0);
+      double du = kr[ne] * alpha;
+#pragma unroll
+      for (int i = 0; i < ne; ++i) du += kr[i] * dx[i];
+      double uj = cur.u[j] + du;
+      if (clamp) uj = fmin(fmax(uj, pa.u_min[j]), pa.u_max[j]);  // (wave-uniform branch)
+      ub[j] = uj;
+      if (store) EL(pUo, j) = uj;
+    }
+    pUo += m * 64;
+    J += knot_cost<M, true>(P, k, xb, ub, nullptr, nullptr, false, gl0, cp0);
+    if (has_cons) { const double v = knot_violation<M>(P, k, xb, ub, cp0); if (!(v <= cm)) cm = v; }
+    model_step<M, double, FI>(mp, integrator, k, xb, ub, P.dt[k], xn);
+    double mx = 0.0, mu = 0.0;
+#pragma unroll
+    for (int i = 0; i < n; ++i) { xb[i] = xn[i]; const double v = fabs(xn[i]); mx = !(v <= mx) ? v : mx; }
+#pragma unroll
+    for (int j = 0; j < m; ++j) { const double v = fabs(ub[j]); mu = !(v <= mu) ? v : mu; }
+    // k_rollout's test: the state the step arrives at first, then the control; the lane keeps stepping (its values are never used)
+    const int ev = !(mx <= max_x) ? TO_STATE_LIMIT : !(mu <= max_u) ? TO_CONTROL_LIMIT : 0;
+    klim = (lim == 0 && ev != 0) ? k + 1 : klim;
+    lim = lim == 0 ? ev : lim;
+  }
+  {  // terminal knot: nxt.x holds x̄_N
+    if (store) {
+#pragma unroll
+      for (int i = 0; i < n; ++i) EL(pXo, i) = xb[i];
+    }
+    double dx[ne], u0[m];
+    state_diff<M>(xb, nxt.x, dx);
+#pragma unroll
+    for (int i = 0; i < ne; ++i) { const double v = fabs(dx[i]); if (!(v <= dxm)) dxm = v; }
+#pragma unroll
+    for (int j = 0; j < m; ++j) u0[j] = 0.0;
+    J += knot_cost<M, true>(P, N - 1, xb, u0, nullptr, nullptr, false, gl0, cp0);
+    if (has_cons) { const double v = knot_violation<M>(P, N - 1, xb, u0, cp0); if (!(v <= cm)) cm = v; }
+  }
+  if constexpr (KLDS) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  if (live) {
+    const double inf = __builtin_inf();
+    pa.J[c] = lim ? inf : J;
+    pa.cmax[c] = lim ? inf : cm;
+    pa.dxmax[c] = lim ? inf : dxm;
+    pa.status[c] = lim;
+    pa.klim[c] = klim;
+  }
+}
+
+}  // namespace to

@@ -6,6 +6,7 @@
 #include "k_forward.h"
 #include "k_scan.h"
 #include "k_misc.h"
+#include "k_policy.h"
 
 namespace to {
 
@@ -231,6 +232,25 @@ int op_accept_roll(to_handle* h) {
     if (h->a.P.integrator == INTEG_RK4) { hipLaunchKernelGGL((k_accept_roll<M, INTEG_RK4>), grid_b(h), dim3(BLOCK), 0, h->stream, h->a); done = true; }
   }
   if (!done) hipLaunchKernelGGL((k_accept_roll<M, -1>), grid_b(h), dim3(BLOCK), 0, h->stream, h->a);
+  HIPCHECK(hipGetLastError());
+  return TO_OK;
+}
+
+// closed-loop policy rollout (k_policy.h): pa.TPW == 0 selects the uniform lane map; grid = the waves of this launch
+template <class M>
+int op_policy_rollout(to_handle* h, const PolicyArgs& pa, int waves) {
+  const bool uniform = pa.TPW == 0;
+  const size_t lds = M::lds_gains ? sizeof(double) * 2 * gains_lds_doubles<M>(uniform ? 1 : pa.TPW) : 0;  // two gains buffers
+  bool rk4 = false;
+  if constexpr (M::pin_rk4) rk4 = h->a.P.integrator == INTEG_RK4;
+  if constexpr (M::pin_rk4) {
+    if (rk4 && uniform) hipLaunchKernelGGL((k_policy_rollout<M, true, INTEG_RK4>), dim3(waves), dim3(BLOCK), lds, h->stream, h->a, pa);
+    else if (rk4) hipLaunchKernelGGL((k_policy_rollout<M, false, INTEG_RK4>), dim3(waves), dim3(BLOCK), lds, h->stream, h->a, pa);
+  }
+  if (!rk4) {
+    if (uniform) hipLaunchKernelGGL((k_policy_rollout<M, true, -1>), dim3(waves), dim3(BLOCK), lds, h->stream, h->a, pa);
+    else hipLaunchKernelGGL((k_policy_rollout<M, false, -1>), dim3(waves), dim3(BLOCK), lds, h->stream, h->a, pa);
+  }
   HIPCHECK(hipGetLastError());
   return TO_OK;
 }

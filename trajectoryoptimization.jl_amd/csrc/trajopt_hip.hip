@@ -119,6 +119,7 @@ const ModelOps* model_ops(int key) {
     fill_ops_quadatt_misc(g_ops); fill_ops_quadmrp_expand(g_ops); fill_ops_quadrp_expand(g_ops);
     fill_ops_quadmrp_forward(g_ops); fill_ops_quadrp_forward(g_ops);
     fill_ops_hybrid(g_ops); fill_ops_small_forward2(g_ops); fill_ops_small_scan(g_ops); fill_ops_pn(g_ops); fill_ops_vector(g_ops); fill_ops_infeasible_a(g_ops); fill_ops_infeasible_b(g_ops);
+    fill_ops_policy(g_ops);
   });
   return (key >= 0 && key < N_MODEL_KEYS) ? &g_ops[key] : nullptr;
 }
@@ -133,6 +134,14 @@ int dev_alloc_named(to_handle* h, const char* name, T** p, size_t count, bool ze
   return TO_OK;
 }
 #define dev_alloc(h, p, ...) dev_alloc_named(h, #p, p, __VA_ARGS__)
+// gives back an array of dev_alloc_named before to_destroy does (arrays that are re-sized)
+template <class T>
+void dev_release(to_handle* h, T** p) {
+  if (!*p) return;
+  h->allocs.erase(std::remove(h->allocs.begin(), h->allocs.end(), (void*)*p), h->allocs.end());
+  g_free(h, *p);
+  *p = nullptr;
+}
 
 int ensure_stage(to_handle* h, size_t bytes) {
   if (h->stage_bytes >= bytes) return TO_OK;
@@ -1492,14 +1501,16 @@ int to_stage_costs(to_handle* h, double* Jk) {
   HIPCHECK(hipStreamSynchronize(h->stream));
   return TO_OK;
 }
-int to_expand(to_handle* h) {
-  CHECK_H(h); CHECK_IDLE(h); TRY(use_device(h));
+static int phase_expand(to_handle* h) {
   TRY(launch_set_active(h, 1)); TRY(launch_expand(h));
   HIPCHECK(hipStreamSynchronize(h->stream));
   return check_guards(h, "to_expand");
 }
-int to_backward(to_handle* h) {
+int to_expand(to_handle* h) {
   CHECK_H(h); CHECK_IDLE(h); TRY(use_device(h));
+  return phase_expand(h);
+}
+static int phase_backward(to_handle* h) {
   TRY(launch_set_active(h, 1));
   const DevProblem& P = h->a.P;
   if (h->scan == 2 && h->a.h_diag && P.expand_variant == 0) {
@@ -1509,6 +1520,123 @@ int to_backward(to_handle* h) {
   } else TRY(launch_backward(h));
   HIPCHECK(hipStreamSynchronize(h->stream));
   return check_guards(h, "to_backward");
+}
+int to_backward(to_handle* h) {
+  CHECK_H(h); CHECK_IDLE(h); TRY(use_device(h));
+  return phase_backward(h);
+}
+
+// ---- closed-loop policy rollouts (k_policy.h) -------------------------------------------------------------------------------------
+// Entries of model_params that select dimensions or the attitude representation: a simulated plant must share them with the problem.
+static int check_plant_params(const to_handle* h, const double* pp) {
+  const double* mp = h->a.P.mp;
+  const int key = h->model_key;
+  auto same = [&](int i) { return pp[i] == mp[i]; };
+  bool ok = true;
+  if (key <= 2 || key == 7) ok = same(1);                 // double integrator: D; hybrid double integrator: S
+  else if (key >= 4 && key <= 6) ok = same(10);           // Quadrotor: rotation
+  else if (key == 8) return fail(TO_ERR_ARGUMENT, "to_policy_rollout: a model vector takes no plant_params (its models live in the step table)");
+  else if (key == 9 || key == 10) ok = same(15) && same(1);
+  else if (key == 11) ok = same(15);
+  if (!ok) return fail(TO_ERR_ARGUMENT, "to_policy_rollout: plant_params change the model's dimensions or attitude representation");
+  return TO_OK;
+}
+int to_policy_rollout(to_handle* h, int32_t S, const double* x0s, const to_policy_opts* opts, const to_policy_result* out) {
+  CHECK_H(h); CHECK_IDLE(h);
+  if (!x0s) return fail(TO_ERR_NULL, "to_policy_rollout: x0s is NULL");
+  if (!out) return fail(TO_ERR_NULL, "to_policy_rollout: out is NULL");
+  if (S < 1) return fail(TO_ERR_ARGUMENT, "to_policy_rollout: S must be >= 1");
+  if (!h->ops->policy_rollout) return fail(TO_ERR_UNSUPPORTED, "policy rollout not compiled for this model");
+  to_policy_opts o = {1, 0, 0.0, nullptr, nullptr, nullptr};
+  if (opts) o = *opts;
+  if (o.refresh_gains != 0 && o.refresh_gains != 1) return fail(TO_ERR_ARGUMENT, "to_policy_rollout: refresh_gains must be 0 or 1");
+  if (!std::isfinite(o.alpha)) return fail(TO_ERR_ARGUMENT, "to_policy_rollout: alpha must be finite");
+  if (o.plant_params) TRY(check_plant_params(h, o.plant_params));
+  const DevProblem& P = h->a.P;
+  const int n = P.n, m = P.m, N = P.N, B = P.B;
+  PolicyArgs pa;
+  std::memset(&pa, 0, sizeof(pa));
+  // lane map: packed while a wave holds at least two trajectories, one trajectory per wave beyond (TRAJOPT_POLICY_MAP=packed forces the
+  // per-lane body up to S = 64: the A/B of tools/policy_rollout_probe.py)
+  bool packed = S <= 32;
+  if (const char* env = std::getenv("TRAJOPT_POLICY_MAP")) {
+    if (!std::strcmp(env, "packed") && S <= 64) packed = true;
+    if (!std::strcmp(env, "uniform")) packed = false;
+  }
+  pa.S = S; pa.TPW = packed ? 64 / S : 0; pa.WPT = (S + 63) / 64;
+  const long long waves_ll = packed ? ((long long)B + pa.TPW - 1) / pa.TPW : (long long)B * pa.WPT;
+  if (waves_ll > 0x7fffffffLL / 64) return fail(TO_ERR_ARGUMENT, "to_policy_rollout: S * B is too large for one call");
+  const int waves = (int)waves_ll;
+  const size_t SB = (size_t)S * B;
+  pa.alpha = o.alpha;
+  pa.clamp = (o.u_min || o.u_max) ? 1 : 0;
+  for (int j = 0; j < TO_MAX_M; ++j) {
+    pa.u_min[j] = (o.u_min && j < m) ? o.u_min[j] : -HUGE_VAL;
+    pa.u_max[j] = (o.u_max && j < m) ? o.u_max[j] : HUGE_VAL;
+    if (!(pa.u_min[j] <= pa.u_max[j])) return fail(TO_ERR_ARGUMENT, "to_policy_rollout: u_min must not exceed u_max");
+  }
+  std::memcpy(pa.mp, o.plant_params ? o.plant_params : P.mp, sizeof(pa.mp));
+  TRY(use_device(h));
+  if (o.refresh_gains) { TRY(phase_expand(h)); TRY(phase_backward(h)); }
+  if (h->pol_cap < SB) {
+    HIPCHECK(hipStreamSynchronize(h->stream));
+    dev_release(h, &h->pol_x0s); dev_release(h, &h->pol_J); dev_release(h, &h->pol_cmax); dev_release(h, &h->pol_dxmax);
+    dev_release(h, &h->pol_status); dev_release(h, &h->pol_klim);
+    h->pol_cap = 0;
+    TRY(dev_alloc(h, &h->pol_x0s, SB * n, false));
+    TRY(dev_alloc(h, &h->pol_J, SB, false)); TRY(dev_alloc(h, &h->pol_cmax, SB, false)); TRY(dev_alloc(h, &h->pol_dxmax, SB, false));
+    TRY(dev_alloc(h, &h->pol_status, SB, false)); TRY(dev_alloc(h, &h->pol_klim, SB, false));
+    h->pol_cap = SB;
+  }
+  pa.x0s = h->pol_x0s; pa.J = h->pol_J; pa.cmax = h->pol_cmax; pa.dxmax = h->pol_dxmax; pa.status = h->pol_status; pa.klim = h->pol_klim;
+  HIPCHECK(hipMemcpyAsync(h->pol_x0s, x0s, SB * n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  if (!out->X && !out->U) {
+    TRY(h->ops->policy_rollout(h, pa, waves));
+  } else {
+    // trajectories: chunks of waves through a bounded staging pair (sample-fastest blocks, then host layout): only the caller's arrays
+    // grow with S * B * N.  TRAJOPT_POLICY_CHUNK_WAVES overrides the chunk (tests of the chunked path).
+    const size_t Lx = (size_t)N * n, Lu = (size_t)(N - 1) * m;
+    long long chunk = std::max<long long>(1, (32ll << 20) / (long long)(64 * (Lx + Lu) * sizeof(double)));
+    if (const char* env = std::getenv("TRAJOPT_POLICY_CHUNK_WAVES")) chunk = std::max(1, std::atoi(env));
+    chunk = std::min<long long>(chunk, waves);
+    if (h->pol_waves < chunk) {
+      HIPCHECK(hipStreamSynchronize(h->stream));
+      dev_release(h, &h->pol_xw); dev_release(h, &h->pol_uw);
+      h->pol_waves = 0;
+      TRY(dev_alloc(h, &h->pol_xw, (size_t)chunk * Lx * 64, false)); TRY(dev_alloc(h, &h->pol_uw, (size_t)chunk * Lu * 64, false));
+      h->pol_waves = (int)chunk;
+    }
+    TRY(ensure_stage(h, (size_t)chunk * 64 * (Lx + Lu) * sizeof(double)));
+    pa.store = 1; pa.Xw = h->pol_xw; pa.Uw = h->pol_uw;
+    auto first_sample = [&](long long g) -> long long {  // sample index of lane 0 of wave g (the waves enumerate the samples in order)
+      if (g >= waves) return (long long)SB;
+      if (packed) return std::min<long long>((long long)SB, g * pa.TPW * (long long)S);
+      const long long b = g / pa.WPT, w = g - b * pa.WPT;
+      return b * S + w * 64;
+    };
+    for (long long g0 = 0; g0 < waves; g0 += chunk) {
+      const int ng = (int)std::min<long long>(chunk, waves - g0);
+      pa.g0 = (int)g0;
+      TRY(h->ops->policy_rollout(h, pa, ng));
+      const long long c0 = first_sample(g0), cnt = first_sample(g0 + ng) - c0;
+      double* hx = h->stage;
+      double* hu = h->stage + (size_t)cnt * Lx;
+      const unsigned gx = (unsigned)((cnt + 63) / 64);
+      if (out->X) hipLaunchKernelGGL(k_policy_to_host, dim3(gx, (unsigned)std::min<size_t>(Lx, 65535)), dim3(BLOCK), 0, h->stream, h->pol_xw, hx, (int)Lx, S, pa.TPW, pa.WPT, pa.g0, c0, cnt);
+      if (out->U) hipLaunchKernelGGL(k_policy_to_host, dim3(gx, (unsigned)std::min<size_t>(Lu, 65535)), dim3(BLOCK), 0, h->stream, h->pol_uw, hu, (int)Lu, S, pa.TPW, pa.WPT, pa.g0, c0, cnt);
+      HIPCHECK(hipGetLastError());
+      if (out->X) HIPCHECK(hipMemcpyAsync(out->X + (size_t)c0 * Lx, hx, (size_t)cnt * Lx * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+      if (out->U) HIPCHECK(hipMemcpyAsync(out->U + (size_t)c0 * Lu, hu, (size_t)cnt * Lu * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+      HIPCHECK(hipStreamSynchronize(h->stream));  // the staging pair is re-used by the next chunk
+    }
+  }
+  if (out->J) HIPCHECK(hipMemcpyAsync(out->J, h->pol_J, SB * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (out->c_max) HIPCHECK(hipMemcpyAsync(out->c_max, h->pol_cmax, SB * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (out->dx_max) HIPCHECK(hipMemcpyAsync(out->dx_max, h->pol_dxmax, SB * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (out->status) HIPCHECK(hipMemcpyAsync(out->status, h->pol_status, SB * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  if (out->k_limit) HIPCHECK(hipMemcpyAsync(out->k_limit, h->pol_klim, SB * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  HIPCHECK(hipStreamSynchronize(h->stream));
+  return check_guards(h, "to_policy_rollout");
 }
 int to_forward(to_handle* h, int32_t* ls_index, double* J_new) {
   CHECK_H(h); CHECK_IDLE(h); TRY(use_device(h));
