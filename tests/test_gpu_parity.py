@@ -1756,3 +1756,39 @@ def test_packed_expansion_three_parameter_attitudes(rot, hip, oracle, monkeypatc
     info = (ctypes.c_int32 * 8)()
     ph._call("solver_path", info)
     assert info[0] == 1          # MFMA backward pass: the tangent-matrix (packed) expansion ran
+
+
+def test_solver_path_of_created_handles(hip, monkeypatch):
+    """to_solver_path of freshly created handles (no solves) against rows of the table that tests/test_path_plan_host.py pins for the
+    host-compiled path selection (csrc/path_plan.h; tests/host_shim/path_plan_harness.cpp ROWS, same names): what the built library
+    reports is what the CPU-tested function decides.  Short horizons keep the large batches small; two rows have a knob set.  The
+    thresholds scale with the compute units: the rows hold for 256 of them."""
+    import torch
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    if cus != 256:
+        pytest.skip(f"the pinned rows are those of a device with 256 compute units; this one has {cus}")
+    cart = lambda B, con=False: configs.cartpole_problem(batch=B, N=11, tf=0.5, constrained=con, lib=hip)
+    quad = lambda B: configs.quadrotor_problem(batch=B, N=11, tf=0.25, lib=hip)
+
+    def hybrid():
+        from test_hybrid_dims import hybrid_problem
+        return hybrid_problem(hip, batch=200)[0]
+    rows = [
+        ("cartpole B1024 N11", lambda: cart(1024), {}, [0, 1, 0, 4, 2, 1, 1, 0]),
+        ("cartpole B12288 N11 con0", lambda: cart(12288), {}, [0, 1, 0, 4, 2, 1, 1, 0]),
+        ("cartpole B12288 N11 con1", lambda: cart(12288, True), {}, [2, 1, 1, 4, 2, 0, 1, 0]),
+        ("cartpole B20480 N11 con0", lambda: cart(20480), {}, [2, 1, 1, 4, 2, 0, 1, 2]),
+        ("cartpole B32768 N11 con1", lambda: cart(32768, True), {}, [2, 1, 1, 4, 2, 0, 1, 2]),
+        ("quadrotor B4096 N11", lambda: quad(4096), {}, [1, 0, 1, 16, 2, 0, 1, 1]),
+        ("hybrid B200", hybrid, {}, [0, 1, 0, 4, 2, 1, 1, 0]),
+        ("cartpole B1024 SCAN=0", lambda: cart(1024), {"TRAJOPT_SCAN": "0"}, [0, 1, 0, 4, 2, 0, 1, 0]),
+        ("quadrotor B4096 LS_REPACK=0", lambda: quad(4096), {"TRAJOPT_LS_REPACK": "0"}, [1, 0, 1, 16, 2, 0, 1, 0]),
+    ]
+    for name, make, env, want in rows:
+        with monkeypatch.context() as mp:
+            for k, v in env.items():
+                mp.setenv(k, v)
+            p = make()
+        info = (ctypes.c_int32 * 8)()
+        p._call("solver_path", info)
+        assert list(info) == want, name

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "common.h"
+#include "path_plan.h"
 #include "rp_plan.h"
 
 namespace to {
@@ -50,23 +51,8 @@ struct to_handle_s {
   size_t stage_bytes = 0;
   int* counter_host = nullptr;  // pinned
   int counter_len = 0;
-  int cw_base = 1, tw_base = 64;  // forward-wave shape: base, and the deep one (0: none) used once the active trajectories fit
-  int cw_deep = 0, tw_deep = 0, deep_max_active = 0;
-  int fwd2 = 2;           // forward pass as two-wave workgroups (roller + accountant, k_forward2): 0 never, 1 always, 2 per step (TRAJOPT_FWD2)
-  int simds = 1024;       // SIMDs of the device (4 per CU)
-  int scan = 0;           // solve loop: scan backward pass (k_scan.h) ahead of the fused cooperative kernel while the active trajectories are few (TRAJOPT_SCAN=0/1)
-  int scan_max_active = 0;
-  int fused_coop = 0;     // solve loop, cooperative path with diagonal cost blocks: one k_expand_backward_coop launch (TRAJOPT_FUSED_COOP=0 to split)
-  int fused_lane = 0;     // solve loop: one k_expand_backward_lane launch instead of expansion + backward pass (lane path; TRAJOPT_FUSED_LANE=0 to split)
-  int compact = 0;        // solves run with active-list compaction (KArgs::compact; TRAJOPT_COMPACT=0 switches it off)
-  int expand_pack = 1;    // packed tangent-matrix expansion of the quaternion rigid body (k_expand.h PACK; TRAJOPT_EXPAND_PACK=0: the 4 x 16 kernel)
-  int expand_lane = 1;    // lane layout: expansion by k_expand_lane (one lane per (trajectory, knot)); 0 = column-per-lane kernel (A/B knob TRAJOPT_EXPAND_LANE)
-  int roll_min_active = -1;  // solve loop: batch steps with at least this many active trajectories store candidate controls only and accept
-                             // by k_accept_roll (-1: the measured default per solver, 0: never; TRAJOPT_ACCEPT_ROLL_MIN)
-  int roll_min_small = 32768;  // ... the default of the small (write-through) models
-  double roll_min_frac = 0.25;  // ... which also need at least this fraction of the batch active (TRAJOPT_ACCEPT_ROLL_FRAC)
-  int ls2_cwa = 0, ls2_cwb = 2;  // two-launch line search (common.h ls_phase): step sizes per round of launch A (0: off) / launch B (TRAJOPT_LS_TWO=a,b)
-  int ls2_blkA = 0, ls2_dump = 0;  // candidate blocks of launch A; the dump block behind launch B's
+  to::PathTraits traits;  // what `ops` tells the host logic (path_plan.h), built once at to_create
+  to::PathPlan plan;      // the kernel path of this handle's solves and the candidate-buffer sizes that follow from it (path_plan.h plan_paths)
   int accept_chunks = 1;  // grid.z of k_accept (a chunk is >= 32 elements of [X; U]: the copy is latency-bound per wave)
   // device copies of the descriptor tables
   to_cost_desc* d_costs = nullptr;
@@ -113,8 +99,6 @@ struct to_handle_s {
   to::RpSized rp_sized[2];  // what each working set's buffers were sized for (rp_plan.h: re-used only for the same arrays within the capacity)
   int rp_level = 0;      // 0: the kernels work on the home arrays; else on rp_work[(rp_level - 1) & 1]
   int rp_B = 0, rp_Bp = 0;  // the batch of the handle while a solve works on a smaller set
-  double rp_at = 0.7;    // ... the fraction of the working set that has to be left for a move (TRAJOPT_REPACK_AT)
-  int rp_min = 16384;    // repack once the active count has halved, while the set holds at least this many (TRAJOPT_REPACK=0: never)
   // closed-loop policy rollouts (to_policy_rollout): start states and per-sample results, sized for the largest S*B seen so far, and
   // the sample-fastest staging of one chunk of waves when the trajectories are wanted
   double *pol_x0s = nullptr, *pol_J = nullptr, *pol_cmax = nullptr, *pol_dxmax = nullptr;

@@ -106,11 +106,11 @@ int op_expand_fi(to_handle* h) {
   const dim3 grid((P.B + h->G - 1) / h->G, (P.N + kc - 1) / kc);
   const int lay = h->a.bwd_lane ? 3 : !h->a.bwd_mfma ? 0 : (h->a.h_compact ? 2 : 1);
   // lane layout: one lane per (trajectory, knot), all columns at once (k_expand_lane; instantiated in the lane translation units, ops_lane.h)
-  if (lay == 3 && h->expand_lane && h->ops->expand_lane_k) return h->ops->expand_lane_k(h);
+  if (lay == 3 && h->plan.expand_lane && h->ops->expand_lane_k) return h->ops->expand_lane_k(h);
 #define TO_EXPAND_CASE(V, LY) \
   if (var == V && lay == LY) { hipLaunchKernelGGL((k_expand<M, FI, V, LY>), grid, dim3(BLOCK), 0, h->stream, h->a); HIPCHECK(hipGetLastError()); return TO_OK; }
   if constexpr (M::mfma_backward && ExpandPack<M>::ok) {  // compact cost block of the quaternion rigid body: the packed expansion (k_expand.h)
-    if (lay == 2 && h->expand_pack && (var == 0 || var == 2)) {
+    if (lay == 2 && h->plan.expand_pack && (var == 0 || var == 2)) {
       const dim3 pgrid((P.B + EXPAND_PACK_G - 1) / EXPAND_PACK_G, (P.N + kc - 1) / kc);
       if (var == 0) hipLaunchKernelGGL((k_expand<M, FI, 0, 2, true>), pgrid, dim3(BLOCK), 0, h->stream, h->a);
       else hipLaunchKernelGGL((k_expand<M, FI, 2, 2, true>), pgrid, dim3(BLOCK), 0, h->stream, h->a);

@@ -223,6 +223,14 @@ bool diagonal_cost_blocks(const to_handle* h) {
   return h->a.P.ne == h->a.P.n;
 }
 
+// what the host logic needs to know of a model's launch table (path_plan.h)
+PathTraits path_traits(const ModelOps& o) {
+  PathTraits t{o.write_through, o.mfma_backward, o.coop_backward, o.lane_backward, o.ls_first_round, o.expand_backward != nullptr, o.expand_backward_coop != nullptr,
+               o.expand_backward_scan != nullptr, o.accept_roll != nullptr, o.expand_lane_k != nullptr, o.expand_const != nullptr, 0u, 0u};
+  for (int i = 0; i < 32; ++i) { if (o.forward[i]) t.forward |= 1u << i; if (o.forward2[i]) t.forward2 |= 1u << i; }
+  return t;
+}
+
 int upload_tables(to_handle* h) {
   {  // kernel-variant flags derived from the tables (refreshed whenever a cost or constraint is replaced)
     DevProblem& P = h->a.P;
@@ -256,7 +264,7 @@ int upload_tables(to_handle* h) {
   }
   // packed expansion (k_expand.h): whenever the compact cost block is (back) in use, the constant columns of [A B] are in place —
   // another variant of the expansion (general: full cost block) writes them from its dual numbers, equal to rounding only
-  if (h->a.Mt && h->a.h_compact && h->expand_pack && h->ops->expand_const) TRY(h->ops->expand_const(h));
+  if (h->a.Mt && h->a.h_compact && h->plan.expand_pack && h->ops->expand_const) TRY(h->ops->expand_const(h));
   HIPCHECK(hipMemcpyAsync(h->d_costs, h->costs.data(), h->costs.size() * sizeof(to_cost_desc), hipMemcpyHostToDevice, h->stream));
   if (!h->cons.empty()) HIPCHECK(hipMemcpyAsync(h->d_cons, h->cons.data(), h->cons.size() * sizeof(DevCon), hipMemcpyHostToDevice, h->stream));
   HIPCHECK(hipStreamSynchronize(h->stream));
@@ -280,22 +288,40 @@ int launch_accept(to_handle* h) {  // materialise accepted candidate slots on sl
   return TO_OK;
 }
 // forward pass: ONE launch runs the whole line search (CW step sizes per round, concurrently, inside each wave) and the
-// per-trajectory state machine (k_forward.h).  Kernel variants: bit0 simple stage cost, bit1 constraints, bit2
-// compile-time RK4 (models that pin it), bit3 dense costs / generic constraints.
+// per-trajectory state machine (k_forward.h), in the kernel variant path_plan.h forward_mode picks
 int launch_forward(to_handle* h, bool accept = true, bool two_wave = false) {
-  const KArgs& a = h->a;
-  // (bit3 also with per-trajectory linear cost terms, DevProblem::gl: only the general variants read them)
-  int mode = (a.P.simple_stage ? 1 : 0) | (a.P.n_cons > 0 ? 2 : 0) | (a.P.integrator == INTEG_RK4 ? 4 : 0) | (((a.P.expand_variant & 5) || a.P.gl || a.P.cp) ? 8 : 0);
-  if (!h->ops->forward[mode]) mode &= ~4;  // the model does not pin RK4
-  if (a.P.unit_soc && h->ops->forward[mode | 16]) mode |= 16;
-  if (!h->ops->forward[mode]) mode = (mode | 8) & ~1 & ~16;  // the general variant (any cost kind, stage cost read per knot): a superset
-  if (!h->ops->forward[mode]) return fail(TO_ERR_UNSUPPORTED, "forward-pass variant not compiled for this model");
-  if ((two_wave || h->fwd2 == 1) && h->ops->forward2[mode]) TRY(h->ops->forward2[mode](h));
+  const DevProblem& P = h->a.P;  // (the general variants also with per-trajectory linear cost terms / constraint parameters: only they read them)
+  const int mode = forward_mode(P.simple_stage, P.n_cons > 0, P.integrator == INTEG_RK4, (P.expand_variant & 5) || P.gl || P.cp, P.unit_soc, h->traits.forward);
+  if (mode < 0) return fail(TO_ERR_UNSUPPORTED, "forward-pass variant not compiled for this model");
+  if ((two_wave || h->plan.fwd2 == 1) && h->ops->forward2[mode]) TRY(h->ops->forward2[mode](h));
   else TRY(h->ops->forward[mode](h));
   if (accept) TRY(launch_accept(h));  // inside a solve the next expansion writes the accepted step through instead
   return TO_OK;
 }
 int launch_outer(to_handle* h) { return h->ops->outer(h); }
+// stream compaction (k_generic.h; grid: path_plan.h compact_grid): the list of the trajectories that go on, for the next step's kernels ...
+int launch_compact(to_handle* h) {
+  const KArgs& a = h->a;
+  int per, nb;
+  if (a.P.Bp <= COMPACT_ONE_LAUNCH) hipLaunchKernelGGL(k_compact, dim3(1), dim3(1024), 0, h->stream, a);
+  else if (!compact_grid(a.P.Bp, &per, &nb)) return fail(TO_ERR_UNSUPPORTED, "batch too large for the compaction kernels (16 777 216 trajectories)");
+  else {
+    hipLaunchKernelGGL(k_compact_count, dim3(nb), dim3(1024), 0, h->stream, a, per);
+    hipLaunchKernelGGL(k_compact_write, dim3(nb), dim3(1024), 0, h->stream, a, per);
+  }
+  HIPCHECK(hipGetLastError());
+  return TO_OK;
+}
+// ... and, in the two-launch line search, of the trajectories whose `pending` flag launch A left set (-> plist / pcount)
+int launch_flag_list(to_handle* h) {
+  const KArgs& a = h->a;
+  int per, nb;
+  if (!compact_grid(a.P.Bp, &per, &nb)) return fail(TO_ERR_UNSUPPORTED, "batch too large for the compaction kernels (16 777 216 trajectories)");
+  hipLaunchKernelGGL(k_flags_count, dim3(nb), dim3(1024), 0, h->stream, a.pending, a.P.Bp, per, a.ccount);
+  hipLaunchKernelGGL(k_flags_write, dim3(nb), dim3(1024), 0, h->stream, a.pending, a.P.Bp, per, a.ccount, a.plist, a.pcount);
+  HIPCHECK(hipGetLastError());
+  return TO_OK;
+}
 int launch_violation(to_handle* h, double* out) { return h->ops->violation(h, out); }
 
 // stats of the last solve; with_defect: c_max also counts the dynamics / initial-condition defects (a polished trajectory is
@@ -467,7 +493,7 @@ int solve(to_handle* h, to_solve_stats* st, int al_mode) {
   rp_finish(h, false);   // (an error path may leave the handle on a working set: back to the home arrays, without the copy)
   h->a.control = 0;  // on every exit path: the phase API must never find the state machine armed
   h->a.compact = 0;  // ... nor take its trajectories from a solve's active list
-  h->a.CW = h->cw_base; h->a.TW = h->tw_base;
+  h->a.CW = h->plan.cw_base; h->a.TW = h->plan.tw_base;
   h->a.store_x = 1;      // ... and stores whole candidates
   return rc;
 }
@@ -640,7 +666,7 @@ int solve_impl(to_handle* h, to_solve_stats* st, int al_mode) {
   a.al_mode = al_mode;
   a.control = 1;
   h->rp_arr.clear();  // the table of carried arrays is rebuilt per solve (per-trajectory cost terms may have appeared)
-  a.compact = h->compact;
+  a.compact = h->plan.compact;
   const int max_steps = (al_mode ? P.opts.iterations_total : P.opts.iterations) + 1;
   if (h->counter_len < max_steps) {
     int* c = nullptr;
@@ -662,16 +688,7 @@ int solve_impl(to_handle* h, to_solve_stats* st, int al_mode) {
   TRY(launch_cost(h, 1, a.J, nullptr));
   if (a.compact) {  // the initial rollout may have ended trajectories (TO_STATE_LIMIT / TO_CONTROL_LIMIT): the list of step 0 without them
     a.step = -1;
-    if (P.Bp <= 16384) hipLaunchKernelGGL(k_compact, dim3(1), dim3(1024), 0, h->stream, a);
-    else {
-      int per = ((P.Bp + 255) / 256 + 1023) / 1024 * 1024;
-      if (per > 65536) per = 65536;
-      const int nb = (P.Bp + per - 1) / per;
-      if (nb > 256) return fail(TO_ERR_UNSUPPORTED, "batch too large for the compaction kernels (16 777 216 trajectories)");
-      hipLaunchKernelGGL(k_compact_count, dim3(nb), dim3(1024), 0, h->stream, a, per);
-      hipLaunchKernelGGL(k_compact_write, dim3(nb), dim3(1024), 0, h->stream, a, per);
-    }
-    HIPCHECK(hipGetLastError());
+    TRY(launch_compact(h));
   }
   int steps = 0;
   if (h->profile) {
@@ -693,77 +710,34 @@ int solve_impl(to_handle* h, to_solve_stats* st, int al_mode) {
       const int step = launched + c;
       a.step = step;
       if (h->profile) HIPCHECK(hipEventRecord(h->ev[4 * step + 0], h->stream));
-      const bool fcoop = h->fused_coop && a.h_diag && (P.expand_variant == 0 || P.expand_variant == 2);
-      if (!h->fused_lane && !fcoop) TRY(launch_expand(h));
+      // what this step launches (path_plan.h), from the last active count the host has seen (results do not depend on it)
+      const PathPlan& pl = h->plan;
+      const StepPlan sp = plan_step(pl, h->traits, a.h_diag, P.expand_variant, a.compact, last_active, P.B);
+      if (sp.kind == STEP_SPLIT) TRY(launch_expand(h));
       if (h->profile) HIPCHECK(hipEventRecord(h->ev[4 * step + 1], h->stream));
-      if (h->fused_lane) TRY(h->ops->expand_backward(h));  // expansion in the registers of the lane that runs the recursion
-      else if (fcoop && h->scan && P.expand_variant == 0 && last_active <= h->scan_max_active)
-        TRY(h->ops->expand_backward_scan(h));  // unconstrained, diagonal cost blocks: the recursion as a scan over the horizon (k_scan.h)
-      else if (fcoop) TRY(h->ops->expand_backward_coop(h));  // expansion by a second wave of the workgroup, through an LDS ring
-      else TRY(launch_backward(h));
+      switch (sp.kind) {
+        case STEP_FUSED_LANE: TRY(h->ops->expand_backward(h)); break;
+        case STEP_SCAN: TRY(h->ops->expand_backward_scan(h)); break;
+        case STEP_FUSED_COOP: TRY(h->ops->expand_backward_coop(h)); break;
+        case STEP_SPLIT: TRY(launch_backward(h)); break;
+      }
       if (h->profile) HIPCHECK(hipEventRecord(h->ev[4 * step + 2], h->stream));
-      // forward-wave shape of this step, from the last active count the host has seen (results do not depend on it)
-      const bool deep = h->cw_deep && last_active <= h->deep_max_active;
-      a.CW = deep ? h->cw_deep : h->cw_base; a.TW = deep ? h->tw_deep : h->tw_base;
-      // ... and its workgroup shape: two waves per candidate group (roller + accountant, k_forward2) shorten the rollout's latency
-      // chain by a third, but need twice the wave slots — taken once both waves of every workgroup get a SIMD of their own
-      // (C3: 610 vs 812 us per step with the chip full, 480 vs 320 us once the batch has drained)
-      const bool two = h->fwd2 == 2 && (long long)2 * ((last_active + a.TW - 1) / a.TW) <= (long long)h->simds;
-      // ... and what it stores per candidate: with the chip full the pass is bound by its stores, 3/4 of them candidate states
-      // that are read once (the accepted one) or never — from roll_min active trajectories on only the controls go out and the accepted
-      // candidates are rolled out again (k_accept_roll: bit-identical states, one more latency chain of N-1 steps)
-      // (measured, always vs never, whole solve: C5 +0.9 / +4.6 / +7.7 / +7.3 % at B = 2048 / 4096 / 8192 / 16384, C3 -3 / -1 / +1.9 / +4.4 %:
-      // the copy by k_accept grows with the accepted trajectories — 93 us at 4096, 227 us at 8192 — the second rollout does not,
-      // and an AL line search goes through more rounds, each of which stores its candidates, than an unconstrained one)
-      // Small models (write-through; 4 step sizes x 16 trajectories per wave): at the large-batch plateau the forward pass wrote 19 KB per
-      // active trajectory for 4 KB of result and the next expansion gathered the accepted candidate through 4x-amplified sectors;
-      // with the controls only and the re-roll both kernels stream the nominal (TRAJOPT_ACCEPT_ROLL_MIN overrides every default)
-      // (round 6: 2048 for iLQR solves too — alone, C3 at B = 4096 runs 1.12 M it/s with either threshold, and next to other solves on
-      // the device (pipelined handles) the candidate-state stores and k_accept's copy cost the others bandwidth: 1.57 -> 1.70 M it/s over three
-      // handles; the forward phase's counter traffic drops with it)
-      const int roll_min = h->roll_min_active >= 0 ? h->roll_min_active : h->ops->write_through ? h->roll_min_small : 2048;
-      // ... and, for those models, only while the batch is still DENSE: the active list is in index order, so once half of the batch has
-      // converged a wave's 64 trajectories sit in several tiles and every store of the re-roll becomes scattered 8-byte writes (r05 trace,
-      // Cartpole at B = 1 048 576: the re-roll takes 0.9 ms with every trajectory active and 1.8 ms with a quarter of them); the
-      // write-through of the next expansion makes the same scattered stores, but behind 2 000 instructions per knot
-      const bool dense = !h->ops->write_through || (double)last_active >= h->roll_min_frac * (double)P.B;
-      a.store_x = (roll_min > 0 && h->ops->accept_roll && !two && last_active >= roll_min && dense) ? 0 : 1;
-      if (!a.store_x && h->ls2_cwa && a.compact && h->fwd2 != 1) {
-        // two-launch line search (common.h ls_phase): launch A — one round for everybody; flags -> list; launch B — the rest of the
-        // search for the flagged trajectories only; then the accept.  Same candidates, same first accepted step size: bit-identical.
+      a.CW = sp.CW; a.TW = sp.TW; a.store_x = sp.store_x;
+      if (sp.two_launch) {  // launch A — one round for everybody; flags -> list; launch B — the rest of the search for the flagged ones; the accept
         const int cw0 = a.CW, tw0 = a.TW, dump0 = a.dump_wave;
-        a.dump_wave = h->ls2_dump;
-        a.CW = h->ls2_cwa; a.TW = 64 / h->ls2_cwa; a.ls_phase = 1; a.blk0 = 0;
+        a.dump_wave = pl.ls2_dump;
+        a.CW = pl.ls2_cwa; a.TW = 64 / pl.ls2_cwa; a.ls_phase = 1; a.blk0 = 0;
         TRY(launch_forward(h, false, false));
-        {
-          int per = ((P.Bp + 255) / 256 + 1023) / 1024 * 1024;
-          if (per > 65536) per = 65536;
-          const int nb = (P.Bp + per - 1) / per;
-          if (nb > 256) return fail(TO_ERR_UNSUPPORTED, "batch too large for the compaction kernels (16 777 216 trajectories)");
-          hipLaunchKernelGGL(k_flags_count, dim3(nb), dim3(1024), 0, h->stream, a.pending, P.Bp, per, a.ccount);
-          hipLaunchKernelGGL(k_flags_write, dim3(nb), dim3(1024), 0, h->stream, a.pending, P.Bp, per, a.ccount, a.plist, a.pcount);
-          HIPCHECK(hipGetLastError());
-        }
-        a.CW = h->ls2_cwb; a.TW = 64 / h->ls2_cwb; a.ls_phase = 2; a.ls_c0 = h->ls2_cwa; a.blk0 = h->ls2_blkA;
+        TRY(launch_flag_list(h));
+        a.CW = pl.ls2_cwb; a.TW = 64 / pl.ls2_cwb; a.ls_phase = 2; a.ls_c0 = pl.ls2_cwa; a.blk0 = pl.ls2_blkA;
         TRY(launch_forward(h, false, false));
         a.ls_phase = 0; a.blk0 = 0; a.CW = cw0; a.TW = tw0; a.dump_wave = dump0;
         TRY(launch_accept(h));
       } else
-      TRY(launch_forward(h, !h->ops->write_through || !a.store_x, two));
+      TRY(launch_forward(h, !h->ops->write_through || !a.store_x, sp.two_wave));
       a.store_x = 1;
       if (al_mode) TRY(launch_outer(h));
-      if (a.compact) {  // the list of the trajectories that go on, for the next step's kernels
-        if (P.Bp <= 16384) hipLaunchKernelGGL(k_compact, dim3(1), dim3(1024), 0, h->stream, a);
-        else {  // two launches of up to 256 workgroups, each owning `per` flags (a multiple of 1024, at most 64 slices of 1024)
-          int per = ((P.Bp + 255) / 256 + 1023) / 1024 * 1024;
-          if (per > 65536) per = 65536;
-          const int nb = (P.Bp + per - 1) / per;
-          if (nb > 256) return fail(TO_ERR_UNSUPPORTED, "batch too large for the compaction kernels (16 777 216 trajectories)");
-          hipLaunchKernelGGL(k_compact_count, dim3(nb), dim3(1024), 0, h->stream, a, per);
-          hipLaunchKernelGGL(k_compact_write, dim3(nb), dim3(1024), 0, h->stream, a, per);
-        }
-        HIPCHECK(hipGetLastError());
-      }
+      if (a.compact) TRY(launch_compact(h));
       if (h->profile) HIPCHECK(hipEventRecord(h->ev[4 * step + 3], h->stream));
       if (h->guard) {
         if (step == 0) if (const char* env = std::getenv("TRAJOPT_GUARD_SELFTEST")) if (std::atoi(env))  // one double behind the nominal states
@@ -789,10 +763,10 @@ int solve_impl(to_handle* h, to_solve_stats* st, int al_mode) {
   int early_thr = (al_mode && h->pn_early > 0) ? P.B / early_div : -1, early_left = h->pn_early;
   bool snapshot_pending = false;
   // repacked working set (above): iLQR solves of the small models on the fused lane path with compaction
-  bool repack = !al_mode && h->fused_lane && a.compact && h->ops->write_through && h->rp_min > 0;
+  bool repack = !al_mode && a.compact && working_set_repack(h->plan, h->traits);
   if (max_steps > 0) TRY(enqueue_chunk());
   while (!done && waited < nchunks) {
-    if (repack && last_active >= 1 && (double)last_active <= h->rp_at * (double)a.P.B && a.P.B >= h->rp_min) {
+    if (repack && last_active >= 1 && (double)last_active <= h->plan.rp_at * (double)a.P.B && a.P.B >= h->plan.rp_min) {
       // the exact count is needed on the host (B of every later launch): drain the queue once — a handful of times per solve
       HIPCHECK(hipStreamSynchronize(h->stream));
       for (; checked < launched; ++checked) {
@@ -835,7 +809,7 @@ int solve_impl(to_handle* h, to_solve_stats* st, int al_mode) {
     }
   }
   TRY(launch_accept(h));  // trajectories keep the slot of their last accepted step until here
-  a.CW = h->cw_base; a.TW = h->tw_base;
+  a.CW = h->plan.cw_base; a.TW = h->plan.tw_base;
   TRY(rp_finish(h, true));  // a repacked working set goes home
   HIPCHECK(hipEventRecord(e1, h->stream));
   HIPCHECK(hipEventSynchronize(e1));
@@ -988,10 +962,11 @@ int to_create(const to_problem_desc* desc, const to_solver_opts* opts, int devic
   h->device = device;
   h->model_key = key;
   if (const char* env = std::getenv("TRAJOPT_GUARD")) h->guard = std::atoi(env) != 0;
-  h->R = (ne + m) <= 4 ? 4 : (ne + m) <= 8 ? 8 : 16;
+  h->R = coop_lanes(ne, m);
   h->G = 64 / h->R;
   h->ops = model_ops(key);
   if (!h->ops || !h->ops->rollout || !h->ops->expand || !h->ops->backward) { delete h; return fail(TO_ERR_UNSUPPORTED, "model kernels not linked"); }
+  h->traits = path_traits(*h->ops);
   h->costs.assign(desc->costs, desc->costs + desc->n_costs);
   h->cons = cons; h->dt = dt; h->cost_index = cost_index; h->step_table = step_table;
   auto bail = [&](int rc) { std::string e = g_err; to_destroy(h); g_err = e; return rc; };
@@ -1021,140 +996,26 @@ int to_create(const to_problem_desc* desc, const to_solver_opts* opts, int devic
     std::memset(P.mp, 0, sizeof(P.mp));
     std::memcpy(&P.mp[0], &bits, sizeof(bits));
   }
-  TRYB(upload_tables(h));
   P.dt = (DoubleC*)h->d_dt; P.cost_index = (IntC*)h->d_cost_index; P.costs = (CostC*)h->d_costs; P.cons = (ConC*)h->d_cons;
-  // Line-search candidates evaluated concurrently per trajectory, CW (a power of two): a forward wave holds CW
-  // candidates x 64/CW trajectories, so the launch has Bp*CW/64 waves — enough to cover the 1024 SIMDs of the chip for
-  // small batches, at most the model's ls_first_round (4 for the small models, 16 for the Quadrotor; the default search
-  // depth is 20: further in-kernel rounds cover the rest).
-  {
-    int cw = std::max(1, std::min(h->ops->ls_first_round, 1024 / (P.Bp / BLOCK)));  // one forward wave per SIMD (measured: C5 0.71 M it/s with 8, 0.68 M with 16)
-    // ... the models that search narrowly anyway (the small ones: 4 step sizes) keep their full first round at every batch size:
-    // a trajectory that rejects everything offered costs its wave a second full pass, which is worse than the extra lanes —
-    // measured at B = 131 072 (fused lane path): 25.4 / 29.6 / 37.4 M trajectory-iterations/s with 1 / 2 / 4 step sizes per
-    // round (forward pass 959 -> 582 us per batch step from 2 to 4), and 18.7 -> 21.8 M at B = 32 768
-    if (h->ops->ls_first_round <= 4) cw = h->ops->ls_first_round;
-    if (const char* env = std::getenv("TRAJOPT_LS_CANDIDATES")) cw = std::max(1, std::min(16, std::atoi(env)));  // tuning knob
-    int lg = 0;
-    while ((2 << lg) <= cw) ++lg;
-    h->cw_base = 1 << lg; h->tw_base = 64 / h->cw_base;
-    // The small (write-through) models take any width: their lane map is the static one in every round (k_forward.h) and nothing in it
-    // needs a power of two — lanes CW*TW .. 63 ride along without a candidate.  THREE step sizes x 21 trajectories per wave: the C2-shaped
-    // Cartpole solves accept within the first three step sizes in 99.5 % of their line searches (alpha = 1 / 0.5 / 0.25: 18 / 40 / 42 %,
-    // measured on the oracle), so a wave serves 21 trajectories instead of 16 per pass for one extra pass in ~10 % of the waves.
-    if (h->ops->write_through && cw >= 1 && cw <= 16) { h->cw_base = cw; h->tw_base = 64 / cw; }
-    a.CW = h->cw_base; a.TW = h->tw_base;
-    // Deep shape: the WHOLE search depth in one round (20 step sizes x 3 trajectories per wave by default).  A trajectory
-    // that rejects the first CW step sizes otherwise costs the batch a second full rollout pass (the Quadrotor solves do so
-    // in half of their steps: forward 1.0 ms instead of 0.55 ms).  It needs 64/TW = 21 waves per 64 trajectories instead of
-    // 16, so the solve loop switches to it once the active trajectories fit the chip that way (one wave per SIMD).
-    const int total = P.opts.iterations_linesearch;
-    const char* deep_env = std::getenv("TRAJOPT_LS_DEEP");  // 0: never switch to the deep shape (tests of the round logic)
-    // Only while a wave still holds >= 2 trajectories that way (total <= 32): with 33..64 step sizes a deep wave would carry
-    // ONE trajectory and the candidate arrays 64x the nominal storage (several GB on C5) — those depths run as further
-    // rounds of the base shape instead.
-    if (!h->ops->write_through && total > h->cw_base && total <= 32 && !(deep_env && std::atoi(deep_env) == 0)) {
-      hipDeviceProp_t prop;
-      HIPB(hipGetDeviceProperties(&prop, device));
-      h->cw_deep = total; h->tw_deep = 64 / total;
-      h->deep_max_active = prop.multiProcessorCount * 4 * h->tw_deep;
-    }
+  {  // the kernel path of this handle (path_plan.h), from the model's traits, the problem's shape and the TRAJOPT_* knobs as they are now
+    PathShape sh{B, P.Bp, N, ne, m, P.n_cons, P.opts.iterations_linesearch, diagonal_cost_blocks(h), 256};
+    HIPB(hipDeviceGetAttribute(&sh.cus, hipDeviceAttributeMultiprocessorCount, device));
+    h->plan = plan_paths(h->traits, sh, read_path_knobs([](const char* name) -> const char* { return std::getenv(name); }));
   }
-  // backward-pass flavour: one wave per trajectory on the matrix cores (tangent-matrix expansion) where the model has it,
-  // else the cooperative LDS kernel on the column layout.  TRAJOPT_BACKWARD=coop|mfma overrides (A/B measurements).
-  // Models that have the cooperative kernel as well (small ones: several trajectories per wave) default to it: measured on
-  // the Cartpole at B = 1024, 78 us cooperative vs 90 us MFMA per backward pass (the 5x5 blocks fill 2 % of a 16x16 tile).
-  a.bwd_mfma = (h->ops->mfma_backward && !h->ops->coop_backward) ? 1 : 0;
-  // Small models: the cooperative kernel (R lanes per trajectory, LDS exchanges) has the shorter critical path — 78 vs 111 us
-  // per pass on the Cartpole at B = 1024, a single lane issues every FMA of a knot itself — and the lane kernel the fewer
-  // instructions: it takes over once the cooperative waves would stack three deep on every SIMD (measured at B = 32 768:
-  // 12.0 vs 9.8 M trajectory-iterations/s).
-  {
-    int cus = 256;
-    HIPB(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device));
-    h->simds = 4 * cus;
-    const long coop_waves = ((long)B + h->G - 1) / h->G;
-    // (with the expansions fused into both kernels the crossover sits at ~12 000 Cartpole trajectories: measured fused lane vs
-    // fused cooperative 10.8 vs 9.9 M it/s at B = 12 288, 7.9 vs 9.3 M at B = 8 192)
-    // (and where the scan kernel runs ahead of the cooperative one — unconstrained problems with diagonal cost blocks — at
-    // ~20 000: scan + cooperative vs fused lane 15.2 vs 11.2 M it/s at B = 12 288, 17.1 vs 14.4 at 16 384, 19.4 vs 20.4 at 24 576)
-    const bool scan_path = h->ops->expand_backward_scan && h->cons.empty() && N <= 126 && diagonal_cost_blocks(h) &&
-                           !(std::getenv("TRAJOPT_SCAN") && !std::atoi(std::getenv("TRAJOPT_SCAN")));
-    const long lane_from = scan_path ? 10L : (h->ops->expand_backward ? 6L : 12L);
-    a.bwd_lane = (h->ops->lane_backward && coop_waves >= lane_from * cus) ? 1 : 0;
-  }
-  if (const char* env = std::getenv("TRAJOPT_BACKWARD")) {
-    if (!std::strcmp(env, "coop") && h->ops->coop_backward) { a.bwd_mfma = 0; a.bwd_lane = 0; }
-    if (!std::strcmp(env, "mfma") && h->ops->mfma_backward) { a.bwd_mfma = 1; a.bwd_lane = 0; }
-    if (!std::strcmp(env, "lane") && h->ops->lane_backward) { a.bwd_mfma = 0; a.bwd_lane = 1; }
-  }
-  if (const char* env = std::getenv("TRAJOPT_EXPAND_LANE")) h->expand_lane = std::atoi(env) != 0;
-  h->fused_coop = (!a.bwd_lane && !a.bwd_mfma && h->ops->expand_backward_coop) ? 1 : 0;  // used while the cost blocks are diagonal (KArgs::h_diag)
-  if (const char* env = std::getenv("TRAJOPT_FUSED_COOP")) if (!std::atoi(env)) h->fused_coop = 0;
-  h->roll_min_active = -1;
-  if (const char* env = std::getenv("TRAJOPT_ACCEPT_ROLL_MIN")) h->roll_min_active = std::atoi(env);
-  if (const char* env = std::getenv("TRAJOPT_ACCEPT_ROLL_FRAC")) h->roll_min_frac = std::atof(env);
-  if (const char* env = std::getenv("TRAJOPT_REPACK")) h->rp_min = std::atoi(env);  // 0: never; n: while the working set holds >= n trajectories
-  if (const char* env = std::getenv("TRAJOPT_REPACK_AT")) h->rp_at = std::min(0.95, std::max(0.05, std::atof(env)));
-  if (const char* env = std::getenv("TRAJOPT_EXPAND_PACK")) h->expand_pack = std::atoi(env) != 0;
-  h->fwd2 = 2;  // 0: one-wave forward pass only; 1: two-wave always (phase API included); 2: per batch step, by the active count
-  if (const char* env = std::getenv("TRAJOPT_FWD2")) h->fwd2 = std::atoi(env);
-  if (h->fwd2 < 0 || h->fwd2 > 2) h->fwd2 = 2;
-  a.coop_merge = 1;
-  if (const char* env = std::getenv("TRAJOPT_COOP_MERGE")) a.coop_merge = std::atoi(env) != 0;
-  // scan (parallel-in-time) backward pass ahead of the fused cooperative kernel, over the whole range of batches the cooperative
-  // path serves (measured, Cartpole: 40.7 vs 95.2 us per step at B = 1024, 76 vs 103 at 4096, 119 vs 164 at 8192)
-  h->scan = (h->fused_coop && h->ops->expand_backward_scan && N <= 126) ? 1 : 0;
-  if (const char* env = std::getenv("TRAJOPT_SCAN")) { if (!std::atoi(env)) h->scan = 0; else if (h->scan && std::atoi(env) == 2) h->scan = 2; }
-  h->scan_max_active = 1 << 30;
-  if (const char* env = std::getenv("TRAJOPT_SCAN_MAX")) h->scan_max_active = std::atoi(env);
-  h->fused_lane = (a.bwd_lane && h->ops->expand_backward) ? 1 : 0;
-  if (const char* env = std::getenv("TRAJOPT_FUSED_LANE")) if (!std::atoi(env)) h->fused_lane = 0;
-  TRYB(upload_tables(h));  // again: h_compact depends on bwd_mfma
+  const PathPlan& pl = h->plan;
+  a.bwd_mfma = pl.bwd_mfma; a.bwd_lane = pl.bwd_lane; a.coop_merge = pl.coop_merge; a.CW = pl.cw_base; a.TW = pl.tw_base;
+  a.store_x = 1; a.dump_wave = pl.dump_wave; a.repack_block0 = pl.repack_block0;
+  TRYB(upload_tables(h));  // (behind the plan: h_compact / h_diag depend on the backward-pass flavour)
   h->accept_chunks = std::max(1, std::min(128, (N * n + (N - 1) * P.m + 31) / 32));
   TRYB(dev_alloc(h, &a.Xs, (size_t)N * n * (Bp + 64)));  // (+ one spare tile: where k_accept_roll's lanes without an accepted step store)
   TRYB(dev_alloc(h, &a.Us, (size_t)(N - 1) * m * Bp));
-  {  // candidates, forward-wave-major (common.h): 64 lanes per wave in either shape
-    size_t waves = (Bp + h->tw_base - 1) / h->tw_base;
-    if (h->cw_deep) waves = std::max(waves, (Bp + h->tw_deep - 1) / h->tw_deep);
-    a.store_x = 1;
-    a.dump_wave = (int)waves;  // one spare block: the store target of lanes that hold no candidate (k_forward.h)
-    // ... and, for the models whose search goes through several rounds of the base shape, a second block per wave for
-    // the repacked last round (k_forward.h LsRound; TRAJOPT_LS_REPACK=0 switches it off)
-    size_t extra = 0;
-    const char* rp_env = std::getenv("TRAJOPT_LS_REPACK");
-    a.repack_block0 = 0;
-    if (!h->ops->write_through && !(rp_env && std::atoi(rp_env) == 0)) {
-      extra = waves;  // as many as either wave shape launches: a search deeper than the deep shape (options changed after creation) repacks there too
-      a.repack_block0 = (int)waves + 1;
-    }
-    // two-launch line search (small models, dense large batches: the steps that store candidate controls only): launch A's blocks,
-    // launch B's behind them, one dump block — control candidates only, so only Uc grows
-    size_t ublocks = waves + 1 + extra;
-    h->ls2_cwa = 0;
-    if (h->ops->write_through && h->ops->accept_roll && Bp >= 32768) {
-      int ca = 2, cb = 2;  // measured default (r05, Cartpole at B = 1 048 576: 74.1 M it/s with 2 + 2, 71.5 with 1 + 2, 70.9 with one launch; TRAJOPT_LS_TWO=a,b overrides, a = 0: off)
-      if (const char* env = std::getenv("TRAJOPT_LS_TWO")) { ca = std::atoi(env); const char* c2 = std::strchr(env, ','); cb = c2 ? std::atoi(c2 + 1) : 2; }
-      if (ca >= 1 && ca <= 16 && cb >= 1 && cb <= 16 && ca < P.opts.iterations_linesearch) {
-        h->ls2_cwa = ca; h->ls2_cwb = cb;
-        const size_t nA = (Bp + (64 / ca) - 1) / (64 / ca), nB = (Bp + (64 / cb) - 1) / (64 / cb);
-        h->ls2_blkA = (int)nA; h->ls2_dump = (int)(nA + nB);
-        ublocks = std::max(ublocks, nA + nB + 1);
-      }
-    }
-    TRYB(dev_alloc(h, &a.Xc, (size_t)N * n * (waves + 1 + extra) * 64));
-    TRYB(dev_alloc(h, &a.Uc, (size_t)(N - 1) * m * ublocks * 64));
-  }
-  if (h->ls2_cwa) { TRYB(dev_alloc(h, &a.pending, Bp)); TRYB(dev_alloc(h, &a.plist, Bp)); TRYB(dev_alloc(h, &a.pcount, 1)); }
+  TRYB(dev_alloc(h, &a.Xc, (size_t)N * n * pl.x_blocks * 64));  // candidates, forward-wave-major (common.h)
+  TRYB(dev_alloc(h, &a.Uc, (size_t)(N - 1) * m * pl.u_blocks * 64));
+  if (pl.ls2_cwa) { TRYB(dev_alloc(h, &a.pending, Bp)); TRYB(dev_alloc(h, &a.plist, Bp)); TRYB(dev_alloc(h, &a.pcount, 1)); }
   TRYB(dev_alloc(h, &a.x0, (size_t)n * Bp));
   TRYB(dev_alloc(h, &a.acc, Bp));
   TRYB(dev_alloc(h, &a.accp, Bp));
   TRYB(dev_alloc(h, &a.alist, 2 * (size_t)Bp)); TRYB(dev_alloc(h, &a.acount, 2)); TRYB(dev_alloc(h, &a.ccount, 256));
-  // active-list compaction: the fused lane path (large batches of the small models) and the MFMA path (Quadrotor: its expansion
-  // waves hold four trajectories each and the solves end with long straggler tails — 141 batch steps for a mean of 52
-  // iterations on C3); the cooperative small-batch path is latency-bound and keeps its fixed mapping;
-  h->compact = (h->fused_lane || a.bwd_mfma) ? 1 : 0;
-  if (const char* env = std::getenv("TRAJOPT_COMPACT")) if (!std::atoi(env)) h->compact = 0;  // armed only inside a solve
   TRYB(dev_alloc(h, &a.oflag, Bp)); TRYB(dev_alloc(h, &a.ost, Bp));
   TRYB(dev_alloc(h, &a.olist, 2 * (size_t)Bp)); TRYB(dev_alloc(h, &a.ocount, 2));
   TRYB(dev_alloc(h, &a.knotbuf, (size_t)N * Bp));
@@ -1204,7 +1065,7 @@ int to_create(const to_problem_desc* desc, const to_solver_opts* opts, int devic
       HIPB(hipStreamSynchronize(h->stream));
     }
   }
-  if (a.Mt && a.h_compact && h->expand_pack && h->ops->expand_const) TRYB(h->ops->expand_const(h));
+  if (a.Mt && a.h_compact && h->plan.expand_pack && h->ops->expand_const) TRYB(h->ops->expand_const(h));
   HIPB(hipStreamSynchronize(h->stream));
 #undef TRYB
 #undef HIPB
@@ -1248,20 +1109,7 @@ void* to_stream(to_handle* h) { return h ? (void*)h->stream : nullptr; }
 
 int to_solver_path(const to_handle* h, int32_t* info) {
   CHECK_H(h); CHECK_P(info);
-  const KArgs& a = h->a;
-  info[0] = a.bwd_mfma ? 1 : a.bwd_lane ? 2 : 0;
-  const DevProblem& P = a.P;
-  const bool fcoop = h->fused_coop && a.h_diag && (P.expand_variant == 0 || P.expand_variant == 2);
-  info[1] = (h->fused_lane || (!a.bwd_mfma && !a.bwd_lane && fcoop)) ? 1 : 0;
-  info[2] = h->compact;
-  info[3] = h->cw_base;
-  bool has2 = false;
-  for (int i = 0; i < 32; ++i) has2 = has2 || h->ops->forward2[i] != nullptr;
-  info[4] = (h->fwd2 && has2) ? 2 : 1;  // (two-wave workgroups are used while the active trajectories leave room for them)
-  info[5] = (h->scan && fcoop && P.expand_variant == 0 && !a.bwd_mfma && !a.bwd_lane) ? 1 : 0;
-  info[6] = (h->ops->accept_roll && h->roll_min_active != 0) ? 1 : 0;  // full-chip batch steps store candidate controls only (k_accept_roll)
-  info[7] = a.repack_block0 != 0 ? 1 : 0;                               // repacked last line-search round
-  if (h->fused_lane && h->compact && h->ops->write_through && h->rp_min > 0 && P.B >= h->rp_min) info[7] |= 2;  // repacked working set (iLQR solves)
+  path_report(h->plan, h->traits, h->a.h_diag, h->a.P.expand_variant, h->a.P.B, info);
   return TO_OK;
 }
 int to_knot_dims(const to_handle* h, int32_t* nx, int32_t* nu) {
@@ -1513,7 +1361,7 @@ int to_expand(to_handle* h) {
 static int phase_backward(to_handle* h) {
   TRY(launch_set_active(h, 1));
   const DevProblem& P = h->a.P;
-  if (h->scan == 2 && h->a.h_diag && P.expand_variant == 0) {
+  if (h->plan.scan == 2 && scan_now(h->plan, h->a.h_diag, P.expand_variant)) {
     // TRAJOPT_SCAN=2 (tests): the phase API runs the solve loop's scan kernel so that its gains can be read back and compared
     // (it expands on its own: to_expand's arrays are not used)
     TRY(h->ops->expand_backward_scan(h));
