@@ -20,6 +20,7 @@
  *                                  (out of tree; SURVEY.md §8a rows E1,S1-S4)
  *   to_policy_rollout           <- rollout!(prob) src/problem.jl:330-340 and Altro's rollout!(solver, α), from S start states
  *                                  per trajectory instead of the problem's x0
+ *   to_policy_rollout_mc        <- the same with process / measurement noise drawn in the kernel and one plant per sample
  *   to_set_* / to_get_*         <- initial_controls!/initial_states!/set_initial_state!/states/controls
  *                                  src/problem.jl:198-310
  *
@@ -59,8 +60,12 @@ extern "C" {
  * 6: to_solve_progress / to_solve_wait_below (pipelined solves over several handles), to_set_constraint_params_batch /
  * to_clear_constraint_params_batch (one GoalConstraint target per trajectory); TO_STATE_LIMIT / TO_CONTROL_LIMIT are
  * emitted; TRAJOPT_RCCL_LIB, TRAJOPT_GUARD.  7: to_policy_rollout with to_policy_opts / to_policy_result (closed-loop rollouts of
- * S perturbed samples per trajectory under the solved feedback law). */
+ * S perturbed samples per trajectory under the solved feedback law).  7.1: to_policy_rollout_mc with to_policy_noise (process noise,
+ * measurement noise, one plant per sample), to_policy_noise_draws, to_abi_minor; no existing struct or symbol changed.
+ * Policy as amended with 7.1: the major version (TO_ABI_VERSION) changes when a struct or a symbol changes meaning, the minor
+ * (TO_ABI_MINOR) when symbols are added; a host that needs an added symbol checks to_abi_minor() >= the minor that introduced it. */
 #define TO_ABI_VERSION 7
+#define TO_ABI_MINOR 1
 
 #define TO_MAX_N 16       /* max state dimension            */
 #define TO_MAX_M 8        /* max control dimension          */
@@ -303,6 +308,7 @@ typedef struct to_handle_s to_handle;
 
 /* ---- library ------------------------------------------------------------------------------ */
 int to_abi_version(void);
+int to_abi_minor(void);   /* TO_ABI_MINOR of the library: additive symbols since the last major version */
 const char* to_build_id(void);             /* hash of the sources this binary was compiled from (build.py stamps it; tests and
                                               bench.py print it, build() recompiles when it differs from the tree) */
 const char* to_last_error(void);
@@ -479,6 +485,40 @@ typedef struct {              /* HOST arrays, any may be NULL; sample index fast
 } to_policy_result;
 int to_policy_rollout(to_handle* h, int32_t S, const double* x0s /* [n,S,B] */, const to_policy_opts* opts /* NULL = {1,0,0.0,NULL,NULL,NULL} */,
                       const to_policy_result* out);
+
+/* The stochastic policy rollout (ABI 7.1): to_policy_rollout's loop with three additions, each switched on by a non-NULL pointer.
+ * Per sample:  x_1 = x0s[:, s, b];  for k = 1 .. N-1:  dx = state_diff(x_k, x̄_k);  u_k = ū_k + α d_k + K_k (dx + v_k), clamped;  stage
+ * cost, violation and |dx| at (x_k, u_k) — the TRUE state and the APPLIED control, v_k enters the law only;  x_{k+1} = state_add(f(x_k,
+ * u_k), w_k) with f one step of the sample's plant;  the limit test of to_rollout on that noisy x_{k+1};  then the terminal knot.
+ *   measurement noise  v_k[i] = sigma_v[i] z,  z standard normal, i over the ne error-state coordinates.
+ *   process noise      w_k[i] = sigma_w[i] z,  added through the retraction state_add (the projected-Newton polish's: a unit quaternion
+ *                      stays one).  sigma_w is the standard deviation PER STEP: there is no dt scaling.
+ *   one plant per sample  the plant of sample s of trajectory b is plant_params[:, s, b]; every one is checked like
+ *                      to_policy_opts::plant_params (the error names the first offending (b, s)); setting both -> TO_ERR_ARGUMENT.
+ * Draws: Philox4x32-10, key (seed lo, seed hi), counter (traj_offset + b, sample_offset + s, k, kind * 256 + j) with kind 0 = w, 1 = v,
+ * k the 0-based step and j the index of a pair of normals.  One call gives r0..r3;  u1 = (((r1 << 32 | r0) >> 11) + 0.5) 2^-53, u2 likewise
+ * from (r2, r3);  z[2j] = sqrt(-2 ln u1) cos(2 pi u2),  z[2j+1] = sqrt(-2 ln u1) sin(2 pi u2);  coordinate i takes z[i], an odd ne discards
+ * the last normal.  A draw depends on (seed, trajectory, sample, knot) only: not on S, the lane map, the chunked download, or on how a
+ * batch is split over handles (traj_offset) and its samples over calls (sample_offset).
+ * noise == NULL, or all three pointers NULL: exactly to_policy_rollout (bit-identical).  A NULL sigma means that path is not executed; an
+ * all-zero sigma agrees to rounding only.
+ * Errors: a negative or non-finite sigma -> TO_ERR_ARGUMENT; sigma_w / sigma_v on TO_MODEL_HYBRID_DOUBLE_INTEGRATOR or TO_MODEL_VECTOR ->
+ * TO_ERR_UNSUPPORTED (their padded coordinates must stay exactly 0 and their live dimensions change per knot); everything
+ * to_policy_rollout refuses. */
+typedef struct {
+  uint64_t seed;               /* Philox key */
+  uint32_t traj_offset;        /* global index of this handle's trajectory 0 (shards of one batch) */
+  uint32_t sample_offset;      /* global index of sample 0 of this call (S split over several calls) */
+  const double* sigma_w;       /* [ne] or NULL: process noise, std dev per error-state coordinate, per step */
+  const double* sigma_v;       /* [ne] or NULL: measurement noise on the state difference the law sees */
+  const double* plant_params;  /* [16, S, B] (sample fastest, then trajectory) or NULL: one plant per sample */
+} to_policy_noise;
+int to_policy_rollout_mc(to_handle* h, int32_t S, const double* x0s /* [n,S,B] */, const to_policy_opts* opts, const to_policy_noise* noise,
+                         const to_policy_result* out);
+/* Stateless, like to_cone_projection: the 2*pairs standard normals that sample (traj, sample) draws at step k for noise kind `kind`,
+ * computed on `device` by the generator the rollout uses.  1 <= pairs <= 256, kind 0 or 1. */
+int to_policy_noise_draws(int device, uint64_t seed, uint32_t traj, uint32_t sample, uint32_t k, uint32_t kind, int32_t pairs,
+                          double* z /* [2*pairs] */);
 
 /* raw (non error-state) per-knot cost derivatives of the objective at the current trajectory
  * (RD.gradient! / RD.hessian!): grad[(n+m),N,B], hess[(n+m),(n+m),N,B] */

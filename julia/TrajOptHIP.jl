@@ -21,6 +21,7 @@ const lib = get(ENV, "TRAJOPT_HIP_LIBRARY", "libtrajopt_hip")   # trajectoryopti
 
 # ------------------------------------------------------------------------------------------------ header mirrors
 const TO_ABI_VERSION = Int32(7)
+const TO_ABI_MINOR = Int32(1)     # additive symbols since ABI 7 (include/trajopt_hip.h, ABI history)
 const MAXN, MAXM, MAXP, MAXPAR, MAXIND = 16, 8, 40, 400, 48
 const PROFILE_SLOTS = 4
 
@@ -152,11 +153,22 @@ struct PolicyResult                  # == to_policy_result (host arrays, sample 
     U::Ptr{Float64}
 end
 
+struct PolicyNoise                   # == to_policy_noise (ABI 7.1)
+    seed::UInt64
+    traj_offset::UInt32
+    sample_offset::UInt32
+    sigma_w::Ptr{Float64}
+    sigma_v::Ptr{Float64}
+    plant_params::Ptr{Float64}
+end
+
 @enum SolverStatus::Int32 UNSOLVED = 0 LINESEARCH_FAIL SOLVE_SUCCEEDED MAX_ITERATIONS MAX_ITERATIONS_OUTER MAXIMUM_COST STATE_LIMIT CONTROL_LIMIT NO_PROGRESS COST_INCREASE REGULARIZATION_MAX PROJECTION_FAIL
 
 # ------------------------------------------------------------------------------------------------ errors
 last_error() = unsafe_string(ccall((:to_last_error, lib), Cstring, ()))
 abi_version() = ccall((:to_abi_version, lib), Cint, ())
+"Additive symbols since the last major version (7.1: `policy_rollout_mc`, `policy_noise_draws`); only a library of ABI >= 7.1 exports it."
+abi_minor() = ccall((:to_abi_minor, lib), Cint, ())
 build_id() = unsafe_string(ccall((:to_build_id, lib), Cstring, ()))
 "A library of another ABI version is refused at load time (include/trajopt_hip.h: the version changes with every new symbol or field)."
 function __init__()
@@ -643,6 +655,58 @@ function policy_rollout(p::BatchProblem, X0s::Array{Float64,3}; alpha::Real = 0.
     (J = J, c_max = c_max, dx_max = dx_max, status = status, k_limit = k_limit, X = X, U = U)
 end
 """
+    policy_rollout_mc(p::BatchProblem, X0s; seed, sigma_w = nothing, sigma_v = nothing, plants = nothing, traj_offset = 0, sample_offset = 0,
+                      alpha = 0.0, refresh_gains = true, u_min = nothing, u_max = nothing, plant = nothing, trajectories = false)
+The stochastic `policy_rollout` (`to_policy_rollout_mc`, ABI 7.1): process noise `x_{k+1} = f(x_k, u_k) ⊕ w_k`, `w_k[i] = sigma_w[i] z` (per step, no
+dt scaling), measurement noise on the state difference the law sees (`sigma_v`), and one plant per sample (`plants :: (16, S, B)`).  Sigmas
+are a number or a length-ne vector of standard deviations per error-state coordinate; `nothing` switches the path off.  The normals are
+drawn in the kernel (Philox4x32-10) from `(seed, traj_offset + b, sample_offset + s, knot, kind)`, so shards of a batch and calls on part of
+the samples draw what one call on everything would.  Returns what `policy_rollout` returns.
+"""
+function policy_rollout_mc(p::BatchProblem, X0s::Array{Float64,3}; seed::Integer, sigma_w = nothing, sigma_v = nothing,
+                           plants::Union{Nothing,Array{Float64,3}} = nothing, traj_offset::Integer = 0, sample_offset::Integer = 0,
+                           alpha::Real = 0.0, refresh_gains::Bool = true, u_min = nothing, u_max = nothing,
+                           plant::Union{Nothing,Vector{Float64}} = nothing, trajectories::Bool = false)
+    abi_minor() >= 1 || error("libtrajopt_hip.so is older than ABI 7.1: no to_policy_rollout_mc")
+    size(X0s, 1) == p.n && size(X0s, 3) == p.B && size(X0s, 2) >= 1 || throw(DimensionMismatch("X0s must be (n, S, B)"))
+    S = size(X0s, 2)
+    ne = p.ne
+    clampvec(v) = v === nothing ? Float64[] : (v isa Real ? fill(Float64(v), p.m) : Vector{Float64}(v))
+    sigmavec(v) = v === nothing ? Float64[] : (v isa Real ? fill(Float64(v), ne) : Vector{Float64}(v))
+    lo, hi, sw, sv = clampvec(u_min), clampvec(u_max), sigmavec(sigma_w), sigmavec(sigma_v)
+    (isempty(lo) || length(lo) == p.m) && (isempty(hi) || length(hi) == p.m) || throw(DimensionMismatch("u_min / u_max must have length m"))
+    (isempty(sw) || length(sw) == ne) && (isempty(sv) || length(sv) == ne) || throw(DimensionMismatch("sigma_w / sigma_v must have length ne"))
+    plant === nothing || length(plant) == 16 || throw(DimensionMismatch("plant must hold the 16 model parameters"))
+    plants === nothing || size(plants) == (16, S, p.B) || throw(DimensionMismatch("plants must be (16, S, B)"))
+    plant === nothing || plants === nothing || throw(ArgumentError("plant and plants exclude each other"))
+    J, c_max, dx_max = zeros(S, p.B), zeros(S, p.B), zeros(S, p.B)
+    status, k_limit = zeros(Int32, S, p.B), zeros(Int32, S, p.B)
+    X = trajectories ? zeros(p.n, p.N, S, p.B) : nothing
+    U = trajectories ? zeros(p.m, p.N - 1, S, p.B) : nothing
+    pp = plant === nothing ? Float64[] : plant
+    pps = plants === nothing ? Float64[] : plants
+    ptr(v) = isempty(v) ? Ptr{Float64}(C_NULL) : pointer(v)
+    GC.@preserve lo hi sw sv pp pps J c_max dx_max status k_limit X U begin
+        opts = Ref(PolicyOpts(Int32(refresh_gains), Int32(0), Float64(alpha), ptr(lo), ptr(hi), ptr(pp)))
+        noise = Ref(PolicyNoise(UInt64(seed), UInt32(traj_offset), UInt32(sample_offset), ptr(sw), ptr(sv), ptr(pps)))
+        out = Ref(PolicyResult(pointer(J), pointer(c_max), pointer(dx_max), pointer(status), pointer(k_limit),
+            trajectories ? pointer(X) : Ptr{Float64}(C_NULL), trajectories ? pointer(U) : Ptr{Float64}(C_NULL)))
+        check(ccall((:to_policy_rollout_mc, lib), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ref{PolicyOpts}, Ref{PolicyNoise}, Ref{PolicyResult}),
+            p.handle, Int32(S), X0s, opts, noise, out))
+    end
+    (J = J, c_max = c_max, dx_max = dx_max, status = status, k_limit = k_limit, X = X, U = U)
+end
+"""
+    policy_noise_draws(seed, traj, sample, k, kind, pairs; device = 0)
+The `2 pairs` standard normals sample `(traj, sample)` draws at step `k` for noise kind `kind` (0 = w, 1 = v), from the device's generator.
+"""
+function policy_noise_draws(seed::Integer, traj::Integer, sample::Integer, k::Integer, kind::Integer, pairs::Integer; device::Integer = 0)
+    z = zeros(2 * pairs)
+    check(ccall((:to_policy_noise_draws, lib), Cint, (Cint, UInt64, UInt32, UInt32, UInt32, UInt32, Int32, Ptr{Float64}),
+        device, UInt64(seed), UInt32(traj), UInt32(sample), UInt32(k), UInt32(kind), Int32(pairs), z))
+    z
+end
+"""
     TO.set_goal_state!(p::BatchProblem, Xf::Matrix)        # Xf :: (n, B): one goal per trajectory
 `set_LQR_goal!(cost, xf_b)` (src/cost_functions.jl:249-252: q = -Q xf, nothing else) on every cost of the objective for every
 trajectory of the batch — batched MPC / goal sweeps on one handle (SURVEY §8b) — and, with `constraint = true` (the reference's default,
@@ -831,7 +895,7 @@ function profile(p::BatchProblem)
     (kernel_ms = ms, launches = launches)
 end
 
-export LinearMap, MassDoubleIntegrator, BatchProblem, policy_rollout, PolicyOpts, PolicyResult, SolverOpts, solver_options, default_options, solve_ilqr!, solve_al!, solve_pn!, solve_altro!, solve_async!, wait_solve!, dynamics_defect, expand!, backwardpass!, forwardpass!,
+export LinearMap, MassDoubleIntegrator, BatchProblem, policy_rollout, PolicyOpts, PolicyResult, policy_rollout_mc, policy_noise_draws, PolicyNoise, abi_minor, SolverOpts, solver_options, default_options, solve_ilqr!, solve_al!, solve_pn!, solve_altro!, solve_async!, wait_solve!, dynamics_defect, expand!, backwardpass!, forwardpass!,
     stage_costs, al_cost, dynamics_jacobians, cost_expansion, gains, cost_gradient_hessian, discrete_jacobian, duals, set_duals!,
     reset_duals!, dual_update!, comm_unique_id, comm_init_rank!, allgather!, allgather_stats, comm_shards, comm_destroy!, solver_path, knot_dims, device_count, build_id
 

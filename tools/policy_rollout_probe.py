@@ -4,7 +4,10 @@
 For the Cartpole at N = 101 and the Quadrotor at N = 201 (the BASELINE horizons), with LANES = B * S samples in flight:
   * wall time of the summary-only call (no trajectories, refresh_gains = 0) as (B = LANES / 64, S = 64) — the uniform lane map — and as
     (B = LANES, S = 1) — the packed map —, next to T.rollout (the open-loop kernel, one lane per trajectory) at B = LANES;
-  * at S = 64, the uniform map against the per-lane body forced onto the same samples (TRAJOPT_POLICY_MAP=packed).
+  * at S = 64, the uniform map against the per-lane body forced onto the same samples (TRAJOPT_POLICY_MAP=packed);
+  * the stochastic call (to_policy_rollout_mc) at the same shapes under the default lane map: process noise (w), plus measurement noise
+    (w+v), plus one plant per sample (w+v+plants: the planning model's parameters, copied per sample).  Its yardstick is the noise-free
+    row of the same shape; the cost of the noise is the difference.
 Every figure is the mean of REPS timed calls after one warm call (host wall clock around the blocking C call: upload of the start states,
 kernel, download of the five per-sample arrays).  The gains are those of one backward pass at the initial guess; start states are the
 nominal start plus 0.01 N(0, 1).  Prints one JSON line per measurement and a markdown table.
@@ -68,6 +71,15 @@ def main():
                 record(model=name, N=p.N, what="policy_rollout", B=B, S=S, lane_map=lane_map, ms=round(ms, 3), runs=[round(t, 3) for t in ts],
                        completed=float(np.mean(r.status == 0)))
             os.environ.pop("TRAJOPT_POLICY_MAP")
+            plants = np.zeros((B, S, 16))
+            plants[..., :len(p.model.params())] = p.model.params()
+            sg = 0.01 if name == "cartpole" else 0.002
+            for what, kw in (("w", dict(noise=T.PolicyNoise(1, sigma_w=sg))), ("w+v", dict(noise=T.PolicyNoise(1, sigma_w=sg, sigma_v=sg))),
+                             ("w+v+plants", dict(noise=T.PolicyNoise(1, sigma_w=sg, sigma_v=sg), plants=plants))):
+                ms, ts = timed(lambda: T.policy_rollout(p, X0s, refresh_gains=False, **kw), a.reps)
+                r = T.policy_rollout(p, X0s, refresh_gains=False, **kw)
+                record(model=name, N=p.N, what=f"policy_rollout {what}", B=B, S=S, lane_map="default", ms=round(ms, 3), runs=[round(t, 3) for t in ts],
+                       completed=float(np.mean(r.status == 0)))
             if S == 1:
                 ms, ts = timed(lambda: T.rollout(p), a.reps)
                 record(model=name, N=p.N, what="rollout (open loop)", B=B, S=1, lane_map="-", ms=round(ms, 3), runs=[round(t, 3) for t in ts], completed=1.0)

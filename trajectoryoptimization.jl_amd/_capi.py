@@ -14,6 +14,7 @@ import os
 from pathlib import Path
 
 TO_ABI_VERSION = 7
+TO_ABI_MINOR = 1   # additive symbols since ABI 7: to_policy_rollout_mc, to_policy_noise_draws, to_abi_minor
 TO_MAX_N, TO_MAX_M, TO_MAX_P = 16, 8, 40
 TO_MAX_CON_PARAMS, TO_MAX_CON_INDS = 400, 48
 
@@ -155,6 +156,13 @@ class PolicyResult(C.Structure):
     ]
 
 
+class PolicyNoise(C.Structure):
+    _fields_ = [
+        ("seed", C.c_uint64), ("traj_offset", C.c_uint32), ("sample_offset", C.c_uint32),
+        ("sigma_w", C.POINTER(C.c_double)), ("sigma_v", C.POINTER(C.c_double)), ("plant_params", C.POINTER(C.c_double)),
+    ]
+
+
 _H = C.c_void_p
 _PD = C.POINTER(C.c_double)
 _PI = C.POINTER(C.c_int32)
@@ -238,6 +246,9 @@ HIP_ONLY = {
     "solve_progress": [_H, _PI, _PI, _PI],
     "solve_wait_below": [_H, C.c_int32],
     "policy_rollout": [_H, C.c_int32, _PD, C.POINTER(PolicyOpts), C.POINTER(PolicyResult)],  # the oracle has no closed-loop rollout
+    "policy_rollout_mc": [_H, C.c_int32, _PD, C.POINTER(PolicyOpts), C.POINTER(PolicyNoise), C.POINTER(PolicyResult)],
+    "policy_noise_draws": [C.c_int, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, _PD],
+    "abi_minor": [],
 }
 
 
@@ -290,6 +301,9 @@ class Library:
 
     def abi_version(self):
         return self._fn["abi_version"]()
+
+    def abi_minor(self):
+        return self._fn["abi_minor"]()
 
     def device_count(self):
         n = C.c_int(0)

@@ -42,7 +42,7 @@ __all__ = [
     "GoalConstraint", "BoundConstraint", "NormConstraint", "CircleConstraint", "SphereConstraint", "CollisionConstraint", "QuatVecEq",
     "LinearConstraint", "StateBound", "ControlBound", "IndexedConstraint", "change_dimension",
     "ConstraintList", "add_constraint", "num_constraints", "constraint_hessians",
-    "KnotPoint", "Problem", "rollout", "policy_rollout", "PolicyRollout", "cost", "states", "controls", "initial_controls", "initial_states",
+    "KnotPoint", "Problem", "rollout", "policy_rollout", "PolicyRollout", "PolicyNoise", "policy_noise_draws", "cost", "states", "controls", "initial_controls", "initial_states",
     "set_initial_state", "set_goal_state", "update_trajectory", "get_constraints", "get_objective", "get_model",
     "get_initial_state", "get_final_state", "get_trajectory", "gettimes",
     "SolverOptions", "iLQRSolver", "ALSolver", "ALTROSolver", "ProjectedNewtonSolver", "dynamics_defect", "solve", "SolvePipeline", "iterations", "status", "max_violation",
@@ -1355,7 +1355,26 @@ class PolicyRollout:
         self.J, self.c_max, self.dx_max, self.status, self.k_limit, self.X, self.U = J, c_max, dx_max, status, k_limit, X, U
 
 
-def policy_rollout(prob, X0s, alpha=0.0, refresh_gains=True, u_min=None, u_max=None, plant=None, trajectories=False):
+class PolicyNoise:
+    """Noise of a stochastic ``policy_rollout`` (to_policy_noise): ``sigma_w`` process noise per step, ``sigma_v`` measurement noise on the
+    state difference the law sees — each None (off), a scalar or [ne] standard deviations per error-state coordinate.  The normals are
+    drawn in the kernel from Philox4x32-10 keyed by ``seed`` and counted by (``traj_offset`` + b, ``sample_offset`` + s, knot, kind): a
+    shard of a batch passes the global index of its trajectory 0, a call on part of the samples the index of its sample 0, and both draw
+    what the whole batch in one call would."""
+
+    def __init__(self, seed, sigma_w=None, sigma_v=None, traj_offset=0, sample_offset=0):
+        self.seed, self.sigma_w, self.sigma_v, self.traj_offset, self.sample_offset = int(seed), sigma_w, sigma_v, int(traj_offset), int(sample_offset)
+
+
+def policy_noise_draws(lib, seed, traj, sample, k, kind, pairs, device=0):
+    """The 2*pairs standard normals sample (traj, sample) draws at step ``k`` for noise kind ``kind`` (0 = w, 1 = v), computed on the device
+    by the generator of the stochastic rollout (to_policy_noise_draws)."""
+    z = np.empty(2 * int(pairs))
+    lib.call("policy_noise_draws", int(device), int(seed), int(traj), int(sample), int(k), int(kind), int(pairs), z.ctypes.data_as(C.POINTER(C.c_double)))
+    return z
+
+
+def policy_rollout(prob, X0s, alpha=0.0, refresh_gains=True, u_min=None, u_max=None, plant=None, trajectories=False, noise=None, plants=None):
     """Closed-loop rollouts of the solved feedback law (to_policy_rollout; extends rollout!(prob), src/problem.jl:330-340, and Altro's
     rollout!(solver, α)): sample ``s`` of trajectory ``b`` starts at ``X0s[b, s]`` and is simulated under
     ``u = ū_k + alpha d_k + K_k (x ⊖ x̄_k)`` with the problem's nominal trajectory and gains.
@@ -1363,8 +1382,11 @@ def policy_rollout(prob, X0s, alpha=0.0, refresh_gains=True, u_min=None, u_max=N
     ``X0s`` is [B, S, n] (hybrid models / model vectors: the storage dimension, padding zero).  ``refresh_gains=True`` runs the expansion
     and the backward pass at the current trajectory first; False uses the gains of the last backward pass.  ``u_min`` / ``u_max``: scalar
     or [m] saturation applied after the law.  ``plant``: a model of the problem's class whose parameters the SIMULATION uses (the law
-    stays the planning model's).  Returns a ``PolicyRollout``."""
-    if "policy_rollout" not in prob._lib._fn:
+    stays the planning model's).  ``noise``: a ``PolicyNoise`` — process and measurement noise drawn in the kernel.  ``plants``: one plant
+    per sample, [B][S] models of the problem's class or a [B, S, 16] array of their parameters (not together with ``plant``).  With both
+    None the call is to_policy_rollout; otherwise to_policy_rollout_mc.  Returns a ``PolicyRollout``."""
+    mc = noise is not None or plants is not None
+    if ("policy_rollout_mc" if mc else "policy_rollout") not in prob._lib._fn:
         raise NotImplementedError("policy_rollout needs the HIP library (the CPU oracle has no closed-loop rollout)")
     a = np.asarray(X0s, dtype=np.float64)
     if a.ndim != 3 or a.shape[0] != prob.B or a.shape[2] != prob.n or a.shape[1] < 1:
@@ -1392,6 +1414,43 @@ def policy_rollout(prob, X0s, alpha=0.0, refresh_gains=True, u_min=None, u_max=N
         pp[: len(p)] = p
         keep.append(pp)
         o.plant_params = prob._pd(pp)
+    nz = capi.PolicyNoise()
+    if noise is not None:
+        if not isinstance(noise, PolicyNoise):
+            raise ArgumentError(f"noise must be a PolicyNoise; got {type(noise).__name__}")
+        ne = prob.errstate_dim
+
+        def sigmavec(v, name):
+            v = np.asarray(v, dtype=np.float64)
+            if v.ndim > 1 or (v.ndim == 1 and v.shape[0] != ne):
+                raise DimensionMismatch(f"{name} must be a scalar or [ne={ne}]; got {v.shape}")
+            keep.append(np.ascontiguousarray(np.full(ne, float(v)) if v.ndim == 0 else v))
+            return prob._pd(keep[-1])
+        nz.seed, nz.traj_offset, nz.sample_offset = noise.seed, noise.traj_offset, noise.sample_offset
+        if noise.sigma_w is not None:
+            nz.sigma_w = sigmavec(noise.sigma_w, "sigma_w")
+        if noise.sigma_v is not None:
+            nz.sigma_v = sigmavec(noise.sigma_v, "sigma_v")
+    if plants is not None:
+        if plant is not None:
+            raise ArgumentError("plant (one plant) and plants (one per sample) exclude each other")
+        if isinstance(plants, np.ndarray) and plants.dtype != object:
+            pp = np.asarray(plants, dtype=np.float64)
+            if pp.shape != (B, S, 16):
+                raise DimensionMismatch(f"plants must be [B={B}, S={S}, 16] parameters or [B][S] models; got {pp.shape}")
+        else:
+            rows = [list(row) for row in plants]
+            if len(rows) != B or any(len(row) != S for row in rows):
+                raise DimensionMismatch(f"plants must be [B={B}, S={S}, 16] parameters or [B][S] models; got {len(rows)} rows of {sorted({len(row) for row in rows})}")
+            pp = np.zeros((B, S, 16))
+            for b, row in enumerate(rows):
+                for s, mod in enumerate(row):
+                    if type(mod) is not type(prob.model) or mod.dims() != prob.model.dims():
+                        raise ArgumentError(f"plants[{b}][{s}] must be a {type(prob.model).__name__} with the problem's dimensions; got {type(mod).__name__}")
+                    q = mod.params()
+                    pp[b, s, : len(q)] = q
+        keep.append(np.ascontiguousarray(pp))
+        nz.plant_params = prob._pd(keep[-1])
     J, cm, dxm = np.empty((B, S)), np.empty((B, S)), np.empty((B, S))
     st, kl = np.empty((B, S), np.int32), np.empty((B, S), np.int32)
     X = np.empty((B, S, N, n)) if trajectories else None
@@ -1400,7 +1459,10 @@ def policy_rollout(prob, X0s, alpha=0.0, refresh_gains=True, u_min=None, u_max=N
     r.J, r.c_max, r.dx_max, r.status, r.k_limit = prob._pd(J), prob._pd(cm), prob._pd(dxm), prob._pi(st), prob._pi(kl)
     if trajectories:
         r.X, r.U = prob._pd(X), prob._pd(U)
-    prob._call("policy_rollout", S, prob._pd(a), C.byref(o), C.byref(r))
+    if not mc:
+        prob._call("policy_rollout", S, prob._pd(a), C.byref(o), C.byref(r))
+    else:
+        prob._call("policy_rollout_mc", S, prob._pd(a), C.byref(o), C.byref(nz), C.byref(r))
     return PolicyRollout(J, cm, dxm, st, kl, X, U)
 
 

@@ -97,6 +97,12 @@ struct PolicyArgs {
   double *J, *cmax, *dxmax;  // [S*B] per-sample results, sample fastest
   int *status, *klim;
   double *Xw, *Uw;     // sample-fastest staging of this launch: [wave - g0][N*n][64], [wave - g0][(N-1)*m][64]
+  // to_policy_rollout_mc only (read by the NZ != 0 instances of k_policy_rollout; noise.h has the counter convention)
+  const double* plants;     // [16, S*B] model parameters of every sample's own plant (NZ bit 2), sample index c as above
+  double sigma_w[TO_MAX_N]; // process noise, std dev per error-state coordinate and step (NZ bit 0)
+  double sigma_v[TO_MAX_N]; // measurement noise on the state difference the law sees (NZ bit 1)
+  unsigned long long seed;
+  unsigned traj_offset, sample_offset;  // global index of trajectory 0 of the handle / of sample 0 of the call
 };
 
 // gains row of one knot of one trajectory: m rows of (ne gains + 1 feed-forward) doubles

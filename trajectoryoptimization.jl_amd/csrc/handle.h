@@ -106,6 +106,8 @@ struct to_handle_s {
   size_t pol_cap = 0;        // samples the arrays above hold
   double *pol_xw = nullptr, *pol_uw = nullptr;
   int pol_waves = 0;         // waves the staging holds
+  double* pol_plants = nullptr;  // to_policy_rollout_mc: [16, S*B] one plant per sample
+  size_t pol_plants_cap = 0;     // samples it holds
   // asynchronous solves (to_*_solve_async / to_solve_wait)
   std::thread worker;
   std::atomic<bool> inflight{false};
@@ -173,6 +175,9 @@ struct ModelOps {
   int (*defect)(to_handle*, double* out) = nullptr;             // max dynamics / initial-condition defect of the nominal trajectory
   int (*infeasible_controls)(to_handle*) = nullptr;             // InfeasibleModel only: slack controls from the current states (k_misc.h)
   int (*policy_rollout)(to_handle*, const PolicyArgs& pa, int waves) = nullptr;  // closed-loop policy rollout of `waves` waves from pa.g0 (k_policy.h)
+  // ... its stochastic instances (ops_policy_mc.hip): nz = the kernel's NZ, 1 .. 7; noise_mask = the bits of nz this model has instances for
+  int (*policy_rollout_mc)(to_handle*, const PolicyArgs& pa, int waves, int nz) = nullptr;
+  int policy_noise_mask = 0;
   int (*accept_roll)(to_handle*) = nullptr;  // accept by re-rolling the stored controls (k_forward.h; models without write-through)
   int (*forward[32])(to_handle*) = {};  // by kernel variant (k_forward.h MODE bits); variants a model never uses stay null
   int (*forward2[32])(to_handle*) = {};  // the same variants as two-wave workgroups (k_forward2; models with LDS-staged gains)
@@ -206,6 +211,7 @@ void fill_ops_vector(ModelOps* table);
 void fill_ops_infeasible_a(ModelOps* table);
 void fill_ops_infeasible_b(ModelOps* table);
 void fill_ops_policy(ModelOps* table);
+void fill_ops_policy_mc(ModelOps* table);
 
 // handle-owned device memory (red zones around it in guard mode); g_free accepts what g_malloc returned
 int g_malloc(to_handle* h, void** p, size_t bytes, const char* name);

@@ -2,6 +2,7 @@
 // Non-template __global__ functions: include from ONE translation unit only (trajopt_hip.hip).
 #pragma once
 #include "common.h"
+#include "noise.h"
 
 namespace to {
 
@@ -294,6 +295,10 @@ __global__ void k_policy_to_host(const double* __restrict__ W, double* __restric
   const int lane = TPW ? s * TPW + (b - g * TPW) : s % 64;
   const double* w = W + ((size_t)(g - g0) * (size_t)L) * 64 + lane;
   for (int e = blockIdx.y; e < L; e += gridDim.y) out[(size_t)e + (size_t)L * i] = w[(size_t)e * 64];
+}
+// to_policy_noise_draws: one wave over the pairs, lane j writes the j-th pair of standard normals of (traj, sample, k, kind) (noise.h)
+__global__ void k_policy_noise_draws(unsigned long long seed, unsigned traj, unsigned sample, unsigned k, unsigned kind, int pairs, double* z) {
+  for (int j = threadIdx.x; j < pairs; j += 64) normal_pair(seed, traj, sample, k, kind, (uint32_t)j, &z[2 * j], &z[2 * j + 1]);
 }
 __global__ void k_fill_uniform(double* d, const double* u, int dim, int L, int B) {
   TILE_LANE();

@@ -14,9 +14,16 @@
 // Lanes without a sample (tail of the last wave of a trajectory, tail of a packed wave) roll out a copy of a live one and store
 // nothing but their own column of the wave's staging block; a sample beyond max_state_value / max_control_value keeps stepping.
 // The loop has no lane-divergent region.
+//
+// NZ (to_policy_rollout_mc; NZ = 0 is to_policy_rollout's kernel, text and code unchanged): bit 0 process noise  x_{k+1} = state_add(f(x_k,
+// u_k), w_k), bit 1 measurement noise (the law sees dx_k + v_k; dx_max, J, c_max stay those of the true state and the applied control),
+// bit 2 one plant per sample (mp[] loaded per lane from PolicyArgs::plants instead of broadcast from PolicyArgs::mp).  The normals come
+// from noise.h, counted by (global trajectory, global sample, k, kind, pair): every lane, dead ones included, draws its own, pair by
+// pair as they are consumed — no array of normals is live across the RK step — and the sigmas are wave-uniform kernel arguments.
 #pragma once
 #include "common.h"
 #include "k_forward.h"
+#include "noise.h"
 
 namespace to {
 
@@ -45,8 +52,9 @@ struct PolicyKnot {
   }
 };
 
-template <class M, bool UNIFORM, int FI>
+template <class M, bool UNIFORM, int FI, int NZ = 0>
 __global__ void __launch_bounds__(64) k_policy_rollout(KArgs a, PolicyArgs pa) {
+  constexpr bool NOISE_W = (NZ & 1) != 0, NOISE_V = (NZ & 2) != 0, LANE_PLANT = (NZ & 4) != 0;
   constexpr int n = M::n, m = M::m, ne = M::ne, RSK = Gains<M>::RSK;
   constexpr bool KLDS = M::lds_gains;
   constexpr bool KSC = UNIFORM && !KLDS && RSK <= 12;
@@ -73,8 +81,17 @@ __global__ void __launch_bounds__(64) k_policy_rollout(KArgs a, PolicyArgs pa) {
   const double* gl0 = TILE_PTR(P.gl, P.n_costs * (n + m));
   const double* cp0 = TILE_PTR(P.cp, P.n_cp);
   double mp[16];  // the PLANT's parameters; the law's x̄, ū, K, d are the planning model's
+  if constexpr (LANE_PLANT) {
+    const double* pp = pa.plants + c * 16;
 #pragma unroll
-  for (int i = 0; i < 16; ++i) mp[i] = in_vgpr(pa.mp[i]);
+    for (int i = 0; i < 16; ++i) mp[i] = pp[i];
+  } else {
+#pragma unroll
+    for (int i = 0; i < 16; ++i) mp[i] = in_vgpr(pa.mp[i]);
+  }
+  // counter of this lane's draws (noise.h): the GLOBAL trajectory and sample, so that neither the lane map nor a split of the batch
+  // over handles or of the samples over calls changes a draw
+  [[maybe_unused]] const uint32_t ctraj = pa.traj_offset + (uint32_t)b, csample = pa.sample_offset + (uint32_t)s;
   const int integrator = P.integrator;
   const double max_x = P.opts.max_state_value, max_u = P.opts.max_control_value;
   const double alpha = pa.alpha;
@@ -112,6 +129,15 @@ __global__ void __launch_bounds__(64) k_policy_rollout(KArgs a, PolicyArgs pa) {
     state_diff<M>(xb, cur.x, dx);
 #pragma unroll
     for (int i = 0; i < ne; ++i) { const double v = fabs(dx[i]); if (!(v <= dxm)) dxm = v; }
+    if constexpr (NOISE_V) {  // what the law sees: dx_k + v_k (dxm above is the true one)
+#pragma unroll
+      for (int j = 0; j < (ne + 1) / 2; ++j) {
+        double z0, z1;
+        normal_pair(pa.seed, ctraj, csample, (uint32_t)k, 1u, (uint32_t)j, &z0, &z1);
+        dx[2 * j] += pa.sigma_v[2 * j] * z0;
+        if (2 * j + 1 < ne) dx[2 * j + 1] += pa.sigma_v[2 * j + 1] * z1;
+      }
+    }
 #pragma unroll
     for (int j = 0; j < m; ++j) {
       double kr[ne + 1];
@@ -130,6 +156,19 @@ __global__ void __launch_bounds__(64) k_policy_rollout(KArgs a, PolicyArgs pa) {
     J += knot_cost<M, true>(P, k, xb, ub, nullptr, nullptr, false, gl0, cp0);
     if (has_cons) { const double v = knot_violation<M>(P, k, xb, ub, cp0); if (!(v <= cm)) cm = v; }
     model_step<M, double, FI>(mp, integrator, k, xb, ub, P.dt[k], xn);
+    if constexpr (NOISE_W) {  // x_{k+1} = state_add(f(x_k, u_k), w_k): no dt scaling; the limit test below sees the noisy state
+      double w[ne], xf[n];
+#pragma unroll
+      for (int j = 0; j < (ne + 1) / 2; ++j) {
+        double z0, z1;
+        normal_pair(pa.seed, ctraj, csample, (uint32_t)k, 0u, (uint32_t)j, &z0, &z1);
+        w[2 * j] = pa.sigma_w[2 * j] * z0;
+        if (2 * j + 1 < ne) w[2 * j + 1] = pa.sigma_w[2 * j + 1] * z1;
+      }
+#pragma unroll
+      for (int i = 0; i < n; ++i) xf[i] = xn[i];
+      state_add<M>(xf, w, xn);
+    }
     double mx = 0.0, mu = 0.0;
 #pragma unroll
     for (int i = 0; i < n; ++i) { xb[i] = xn[i]; const double v = fabs(xn[i]); mx = !(v <= mx) ? v : mx; }

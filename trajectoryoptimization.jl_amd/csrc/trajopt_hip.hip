@@ -120,6 +120,7 @@ const ModelOps* model_ops(int key) {
     fill_ops_quadmrp_forward(g_ops); fill_ops_quadrp_forward(g_ops);
     fill_ops_hybrid(g_ops); fill_ops_small_forward2(g_ops); fill_ops_small_scan(g_ops); fill_ops_pn(g_ops); fill_ops_vector(g_ops); fill_ops_infeasible_a(g_ops); fill_ops_infeasible_b(g_ops);
     fill_ops_policy(g_ops);
+    fill_ops_policy_mc(g_ops);
   });
   return (key >= 0 && key < N_MODEL_KEYS) ? &g_ops[key] : nullptr;
 }
@@ -884,6 +885,7 @@ constexpr int kNcclInt32 = 2;   // ncclInt32
 extern "C" {
 
 int to_abi_version(void) { return TO_ABI_VERSION; }
+int to_abi_minor(void) { return TO_ABI_MINOR; }
 #ifndef TO_BUILD_ID
 #define TO_BUILD_ID "unstamped"
 #endif
@@ -1376,7 +1378,7 @@ int to_backward(to_handle* h) {
 
 // ---- closed-loop policy rollouts (k_policy.h) -------------------------------------------------------------------------------------
 // Entries of model_params that select dimensions or the attitude representation: a simulated plant must share them with the problem.
-static int check_plant_params(const to_handle* h, const double* pp) {
+static int check_plant_params(const to_handle* h, const double* pp, const std::string& where = "") {
   const double* mp = h->a.P.mp;
   const int key = h->model_key;
   auto same = [&](int i) { return pp[i] == mp[i]; };
@@ -1386,10 +1388,12 @@ static int check_plant_params(const to_handle* h, const double* pp) {
   else if (key == 8) return fail(TO_ERR_ARGUMENT, "to_policy_rollout: a model vector takes no plant_params (its models live in the step table)");
   else if (key == 9 || key == 10) ok = same(15) && same(1);
   else if (key == 11) ok = same(15);
-  if (!ok) return fail(TO_ERR_ARGUMENT, "to_policy_rollout: plant_params change the model's dimensions or attitude representation");
+  if (!ok) return fail(TO_ERR_ARGUMENT, "to_policy_rollout: plant_params" + where + " change the model's dimensions or attitude representation");
   return TO_OK;
 }
-int to_policy_rollout(to_handle* h, int32_t S, const double* x0s, const to_policy_opts* opts, const to_policy_result* out) {
+// Both entry points: noise == NULL (or nothing set in it) is to_policy_rollout itself, the NZ = 0 kernel and nothing else.
+static int policy_rollout_impl(to_handle* h, int32_t S, const double* x0s, const to_policy_opts* opts, const to_policy_noise* noise,
+                               const to_policy_result* out) {
   CHECK_H(h); CHECK_IDLE(h);
   if (!x0s) return fail(TO_ERR_NULL, "to_policy_rollout: x0s is NULL");
   if (!out) return fail(TO_ERR_NULL, "to_policy_rollout: out is NULL");
@@ -1404,6 +1408,34 @@ int to_policy_rollout(to_handle* h, int32_t S, const double* x0s, const to_polic
   const int n = P.n, m = P.m, N = P.N, B = P.B;
   PolicyArgs pa;
   std::memset(&pa, 0, sizeof(pa));
+  int nz = 0;  // the kernel's NZ: bit 0 process noise, bit 1 measurement noise, bit 2 one plant per sample
+  if (noise) {
+    const int ne = P.ne;
+    if ((noise->sigma_w || noise->sigma_v) && (h->model_key == 7 || h->model_key == 8))
+      return fail(TO_ERR_UNSUPPORTED, "to_policy_rollout_mc: sigma_w / sigma_v on a hybrid model or a model vector (their padded coordinates must stay "
+                                      "exactly 0 and their live dimensions change per knot)");
+    for (int kind = 0; kind < 2; ++kind) {
+      const double* sg = kind == 0 ? noise->sigma_w : noise->sigma_v;
+      if (!sg) continue;
+      for (int i = 0; i < ne; ++i) {
+        if (!std::isfinite(sg[i]) || sg[i] < 0.0)
+          return fail(TO_ERR_ARGUMENT, std::string("to_policy_rollout_mc: ") + (kind == 0 ? "sigma_w" : "sigma_v") + " must be finite and >= 0");
+        (kind == 0 ? pa.sigma_w : pa.sigma_v)[i] = sg[i];
+      }
+      nz |= 1 << kind;
+    }
+    if (noise->plant_params) {
+      if (o.plant_params) return fail(TO_ERR_ARGUMENT, "to_policy_rollout_mc: plant_params given both in the options (one plant) and in the noise (one per sample)");
+      for (int b = 0; b < B; ++b)
+        for (int s = 0; s < S; ++s)
+          TRY(check_plant_params(h, noise->plant_params + ((size_t)b * S + s) * 16, " of sample (b = " + std::to_string(b) + ", s = " + std::to_string(s) + ")"));
+      nz |= 4;
+    }
+    pa.seed = noise->seed; pa.traj_offset = noise->traj_offset; pa.sample_offset = noise->sample_offset;
+    if (nz && (!h->ops->policy_rollout_mc || (nz & ~h->ops->policy_noise_mask)))
+      return fail(TO_ERR_UNSUPPORTED, "to_policy_rollout_mc: not compiled for this model");
+  }
+  auto launch = [&](const PolicyArgs& a, int w) { return nz ? h->ops->policy_rollout_mc(h, a, w, nz) : h->ops->policy_rollout(h, a, w); };
   // lane map: packed while a wave holds at least two trajectories, one trajectory per wave beyond (TRAJOPT_POLICY_MAP=packed forces the
   // per-lane body up to S = 64: the A/B of tools/policy_rollout_probe.py)
   bool packed = S <= 32;
@@ -1438,8 +1470,19 @@ int to_policy_rollout(to_handle* h, int32_t S, const double* x0s, const to_polic
   }
   pa.x0s = h->pol_x0s; pa.J = h->pol_J; pa.cmax = h->pol_cmax; pa.dxmax = h->pol_dxmax; pa.status = h->pol_status; pa.klim = h->pol_klim;
   HIPCHECK(hipMemcpyAsync(h->pol_x0s, x0s, SB * n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  if (nz & 4) {
+    if (h->pol_plants_cap < SB) {
+      HIPCHECK(hipStreamSynchronize(h->stream));
+      dev_release(h, &h->pol_plants);
+      h->pol_plants_cap = 0;
+      TRY(dev_alloc(h, &h->pol_plants, SB * 16, false));
+      h->pol_plants_cap = SB;
+    }
+    pa.plants = h->pol_plants;
+    HIPCHECK(hipMemcpyAsync(h->pol_plants, noise->plant_params, SB * 16 * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  }
   if (!out->X && !out->U) {
-    TRY(h->ops->policy_rollout(h, pa, waves));
+    TRY(launch(pa, waves));
   } else {
     // trajectories: chunks of waves through a bounded staging pair (sample-fastest blocks, then host layout): only the caller's arrays
     // grow with S * B * N.  TRAJOPT_POLICY_CHUNK_WAVES overrides the chunk (tests of the chunked path).
@@ -1465,7 +1508,7 @@ int to_policy_rollout(to_handle* h, int32_t S, const double* x0s, const to_polic
     for (long long g0 = 0; g0 < waves; g0 += chunk) {
       const int ng = (int)std::min<long long>(chunk, waves - g0);
       pa.g0 = (int)g0;
-      TRY(h->ops->policy_rollout(h, pa, ng));
+      TRY(launch(pa, ng));
       const long long c0 = first_sample(g0), cnt = first_sample(g0 + ng) - c0;
       double* hx = h->stage;
       double* hu = h->stage + (size_t)cnt * Lx;
@@ -1485,6 +1528,29 @@ int to_policy_rollout(to_handle* h, int32_t S, const double* x0s, const to_polic
   if (out->k_limit) HIPCHECK(hipMemcpyAsync(out->k_limit, h->pol_klim, SB * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
   HIPCHECK(hipStreamSynchronize(h->stream));
   return check_guards(h, "to_policy_rollout");
+}
+int to_policy_rollout(to_handle* h, int32_t S, const double* x0s, const to_policy_opts* opts, const to_policy_result* out) {
+  return policy_rollout_impl(h, S, x0s, opts, nullptr, out);
+}
+int to_policy_rollout_mc(to_handle* h, int32_t S, const double* x0s, const to_policy_opts* opts, const to_policy_noise* noise,
+                         const to_policy_result* out) {
+  return policy_rollout_impl(h, S, x0s, opts, noise, out);
+}
+// the generator alone (k_policy_noise_draws), so that a parity failure of the stochastic rollout can be localised to it or to the loop
+int to_policy_noise_draws(int device, uint64_t seed, uint32_t traj, uint32_t sample, uint32_t k, uint32_t kind, int32_t pairs, double* z) {
+  CHECK_P(z);
+  if (pairs < 1 || pairs > 256) return fail(TO_ERR_ARGUMENT, "to_policy_noise_draws: pairs must be in 1 .. 256 (the counter holds kind * 256 + pair)");
+  if (kind > 1) return fail(TO_ERR_ARGUMENT, "to_policy_noise_draws: kind must be 0 (process noise) or 1 (measurement noise)");
+  HIPCHECK(hipSetDevice(device));
+  struct DevBuf {  // freed on every exit path
+    void* p = nullptr;
+    ~DevBuf() { if (p) hipFree(p); }
+  } bz;
+  HIPCHECK(hipMalloc(&bz.p, (size_t)2 * pairs * sizeof(double)));
+  hipLaunchKernelGGL(k_policy_noise_draws, dim3(1), dim3(64), 0, 0, (unsigned long long)seed, traj, sample, k, kind, (int)pairs, (double*)bz.p);
+  HIPCHECK(hipGetLastError());
+  HIPCHECK(hipMemcpy(z, bz.p, (size_t)2 * pairs * sizeof(double), hipMemcpyDeviceToHost));
+  return TO_OK;
 }
 int to_forward(to_handle* h, int32_t* ls_index, double* J_new) {
   CHECK_H(h); CHECK_IDLE(h); TRY(use_device(h));
