@@ -85,7 +85,13 @@ typedef enum {
   TO_ERR_CONE = -7                /* ErrorException("Invalid second-order cone projection") src/cones.jl:124    */
 } to_status_code;
 
-/* ---- per-trajectory solver status (Altro.jl TerminationStatus order) --------------------- */
+/* ---- per-trajectory solver status (Altro.jl TerminationStatus order) ---------------------
+ * TO_LINESEARCH_FAIL and TO_COST_INCREASE are declared for the numbering only: neither this library nor the CPU oracle ever
+ * reports them.  A failed line search keeps the nominal trajectory, raises the regularisation (bp_reg_fp) and counts towards
+ * dJ_counter_limit; what a solve reports in the end is TO_NO_PROGRESS, TO_REGULARIZATION_MAX or TO_MAX_ITERATIONS.
+ * TO_REGULARIZATION_MAX: a backward pass had to raise rho beyond bp_reg_max (the iteration is not counted), or a failed line
+ * search left it there (the iteration is counted).  An AL solve ends at the first inner status other than SOLVE_SUCCEEDED,
+ * MAX_ITERATIONS and NO_PROGRESS and reports it. */
 typedef enum {
   TO_UNSOLVED = 0,
   TO_LINESEARCH_FAIL = 1,
@@ -400,6 +406,8 @@ int to_backward(to_handle* h);   /* Riccati recursion -> K, d, dV; regularises p
 /* ls_index: index of the accepted step size alpha = decrease^index; -1 = line search failed (nominal kept, regularisation
  * raised).  At a stationary point (predicted decrease <= 1e-12 (1+|J|)) the ZERO step is taken: ls_index = 0 with
  * J_new == J and an unchanged trajectory; inside a solve such a step counts towards dJ_counter_limit. */
+/* After a to_backward that ran into bp_reg_max for a trajectory (rho > bp_reg_max in to_get_gains; its gains are those of
+ * an abandoned attempt) to_forward takes no step for it: ls_index = -1, J_new = J, trajectory and rho unchanged. */
 int to_forward(to_handle* h, int32_t* ls_index /* [B], -1 = failed */, double* J_new /* [B] */);
 int to_ilqr_solve(to_handle* h, to_solve_stats* stats);
 int to_al_solve(to_handle* h, to_solve_stats* stats);

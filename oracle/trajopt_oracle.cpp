@@ -79,6 +79,9 @@ struct Traj {
   int iterations = 0, iterations_outer = 0, iterations_pn = 0, status = TO_UNSOLVED, ls_index = -1;
   int dJ_zero_counter = 0;
   bool ls_failed = false, zero_step = false;
+  /* phase API: the last oracle_backward ran into bp_reg_max (gains of an abandoned attempt).  Cleared by the next oracle_expand and
+   * at the start of every solve, where the device clears its bpfail (k_set_active from to_expand / to_backward, the solves' initialisation kernel). */
+  bool bp_failed = false;
 };
 
 }  // namespace
@@ -884,7 +887,7 @@ bool ilqr_step(const Problem& P, Traj& t, double cost_tol, int max_iters, double
 }
 
 void ilqr_solve(const Problem& P, Traj& t, double cost_tol, int max_iters) {
-  t.rho = P.opts.bp_reg_initial; t.drho = 0.0; t.dJ_zero_counter = 0; t.status = TO_UNSOLVED;
+  t.rho = P.opts.bp_reg_initial; t.drho = 0.0; t.dJ_zero_counter = 0; t.status = TO_UNSOLVED; t.bp_failed = false;
   rollout(P, t);
   double J_prev = total_cost(P, t, t.X.data(), t.U.data(), true);
   t.J = J_prev;
@@ -1128,16 +1131,22 @@ int oracle_stage_costs(oracle_handle* h, double* Jk) {
   for_batch(h, [&](Traj& t, int b) { for (int k = 0; k < h->P.N; ++k) Jk[(size_t)b * h->P.N + k] = objective_knot(h->P, t.X.data(), t.U.data(), k, t.gl.empty() ? nullptr : t.gl.data()); });
   return TO_OK;
 }
-int oracle_expand(oracle_handle* h) { CHECK_H(h); for_batch(h, [&](Traj& t, int) { expand(h->P, t); }); return TO_OK; }
+int oracle_expand(oracle_handle* h) { CHECK_H(h); for_batch(h, [&](Traj& t, int) { t.bp_failed = false; expand(h->P, t); }); return TO_OK; }
 int oracle_backward(oracle_handle* h) {
   CHECK_H(h);
-  for_batch(h, [&](Traj& t, int) { if (!(std::getenv("ORACLE_RICCATI_SCAN") ? backward_scan(h->P, t) : backward(h->P, t))) t.status = TO_REGULARIZATION_MAX; });
+  for_batch(h, [&](Traj& t, int) {
+    t.bp_failed = !(std::getenv("ORACLE_RICCATI_SCAN") ? backward_scan(h->P, t) : backward(h->P, t));
+    if (t.bp_failed) t.status = TO_REGULARIZATION_MAX;
+  });
   return TO_OK;
 }
 int oracle_forward(oracle_handle* h, int32_t* ls_index, double* J_new) {
   CHECK_H(h);
   for_batch(h, [&](Traj& t, int b) {
     double Jp = total_cost(h->P, t, t.X.data(), t.U.data(), true);
+    /* after a backward pass that ended in REGULARIZATION_MAX there is no step to take (a solve ends there, ilqr_step): the
+     * gains are those of an abandoned attempt.  Report a failed search, leave trajectory and regularisation as they are. */
+    if (t.bp_failed) { t.ls_index = -1; if (ls_index) ls_index[b] = -1; if (J_new) J_new[b] = Jp; return; }
     double J = forward(h->P, t, Jp);
     if (ls_index) ls_index[b] = t.ls_index;
     if (J_new) J_new[b] = J;

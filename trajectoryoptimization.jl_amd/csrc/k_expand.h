@@ -730,6 +730,7 @@ __global__ void __launch_bounds__(64, TO_FUSED_LANE_WAVES) k_expand_backward_lan
   double rho = a.rho[b], drho = a.drho[b];
   double dV0 = 0.0, dV1 = 0.0;
   bool failed = false;
+  int kfail = -1;  // the knot at which a pass ran into bp_reg_max
   double S[ne][ne], s[ne];
   while (true) {  // one pass of the recursion; a Cholesky failure raises rho and starts over
     {  // terminal knot: S = Qxx_N, s = qx_N
@@ -790,11 +791,21 @@ __global__ void __launch_bounds__(64, TO_FUSED_LANE_WAVES) k_expand_backward_lan
         for (int j = 0; j < nc; ++j) Mk[i][j] = Me[i * nc + j];
       if (!lane_riccati_knot<M>(Mk, H, g, S, s, rho, live, pK + (size_t)k * RSK, dV0, dV1)) {
         reg_increase(P.opts, rho, drho);
-        if (rho > P.opts.bp_reg_max) failed = true; else restart = true;
+        if (rho > P.opts.bp_reg_max) { failed = true; kfail = kv; } else restart = true;
         break;
       }
     }
     if (!restart) break;
+  }
+  // A pass that ran into bp_reg_max ends at knot kfail: the step accepted by the last forward pass has been written through down
+  // to that knot only, and no later expansion will do the rest (the solve of this trajectory ends here) — finish the copy.
+  if (failed && wt) {
+    for (int k = kfail - 1; k >= 0; --k) {
+#pragma unroll
+      for (int i = 0; i < n; ++i) EL(X0, k * n + i) = EL(X, k * n + i);
+#pragma unroll
+      for (int i = 0; i < m; ++i) EL(U0, k * m + i) = EL(U, k * m + i);
+    }
   }
   if (!failed) reg_decrease(P.opts, rho, drho);
   if (live) {
