@@ -63,7 +63,11 @@ extern "C" {
  * S perturbed samples per trajectory under the solved feedback law).  7.1: to_policy_rollout_mc with to_policy_noise (process noise,
  * measurement noise, one plant per sample), to_policy_noise_draws, to_abi_minor; no existing struct or symbol changed.
  * Policy as amended with 7.1: the major version (TO_ABI_VERSION) changes when a struct or a symbol changes meaning, the minor
- * (TO_ABI_MINOR) when symbols are added; a host that needs an added symbol checks to_abi_minor() >= the minor that introduced it. */
+ * (TO_ABI_MINOR) when symbols are added; a host that needs an added symbol checks to_abi_minor() >= the minor that introduced it.
+ * Departure from that rule, once: to_set_model_params_batch / to_get_model_params_batch / to_clear_model_params_batch (one plant per
+ * trajectory on the planning side) were added WITHOUT raising TO_ABI_MINOR, which stays 1.  A host detects them by symbol lookup —
+ * dlsym() in C, Libdl.dlsym(lib, sym; throw_error = false) in Julia, an optional binding in the Python mirror — and treats a library
+ * without them as one that plans every trajectory on to_problem_desc::model_params. */
 #define TO_ABI_VERSION 7
 #define TO_ABI_MINOR 1
 
@@ -396,6 +400,22 @@ int to_clear_cost_linear_batch(to_handle* h);
  * them.  Other kinds: TO_ERR_UNSUPPORTED. */
 int to_set_constraint_params_batch(to_handle* h, int32_t con_id, const double* params /* [p*B] */);
 int to_clear_constraint_params_batch(to_handle* h);
+/* One set of MODEL parameters per TRAJECTORY: every trajectory of the handle is planned on its own plant (a fleet of Cartpoles with
+ * different pole masses, Quadrotors with different payloads, a parameter sweep) — the planning-side counterpart of the per-sample plants of
+ * to_policy_rollout_mc.  params[16, B] (16 fastest, then trajectory): column b is read exactly like to_problem_desc::model_params.  Every
+ * column is validated like to_policy_opts::plant_params: entries that select dimensions or the attitude representation (double integrator
+ * D, Quadrotor rotation) must equal the problem's, every entry must be finite — TO_ERR_ARGUMENT otherwise, the message names the first
+ * offending trajectory.  Models: double integrator (D = 1, 2, 3), Cartpole, quaternion Quadrotor; TO_ERR_UNSUPPORTED, with the model's
+ * name, for Quadrotor{MRP} / {RodriguesParam}, the hybrid double integrator, model vectors and InfeasibleModel.  The setter leaves X, U,
+ * duals and gains as they are (like to_set_cost: roll out or solve afterwards).  While parameters are set, every phase entry point,
+ * every solve (asynchronous and pipelined ones included) and the projected-Newton polish use trajectory b's own parameters; the solves
+ * run the general kernel variants (to_solver_path reports no fused and no scan kernel and no repacked working set), and
+ * to_policy_rollout / to_policy_rollout_mc simulate trajectory b on its own parameters unless the caller names a plant.  to_get_... returns
+ * what was set, or the shared parameters repeated B times; to_clear_... returns the handle to the descriptor's model_params — a solve
+ * after it is bit-identical to the same solve on a fresh handle.  Not announced by TO_ABI_MINOR: look the symbols up (ABI history above). */
+int to_set_model_params_batch(to_handle* h, const double* params /* [16*B] */);
+int to_get_model_params_batch(to_handle* h, double* params /* [16*B] */);
+int to_clear_model_params_batch(to_handle* h);
 
 /* ---- the hot path, phase by phase ----------------------------------------------------------- */
 int to_rollout(to_handle* h);                                   /* rollout!  src/problem.jl:330-340 */

@@ -9,6 +9,7 @@
 module TrajOptHIP
 
 using LinearAlgebra
+import Libdl
 using StaticArrays
 import RobotDynamics
 import RobotZoo
@@ -742,6 +743,31 @@ or a `LinearConstraint`'s right-hand side `b_b` (`to_set_constraint_params_batch
 """
 set_constraint_params_batch!(p::BatchProblem, con_id::Integer, params::Matrix{Float64}) =
     check(ccall((:to_set_constraint_params_batch, lib), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}), p.handle, Int32(con_id - 1), params))
+"""
+    set_model_params_batch!(p, params)       # params :: (16, B)
+One set of model parameters per trajectory (`to_set_model_params_batch`): column `b` is read like `to_problem_desc::model_params`, and
+trajectory `b` is planned on it.  `model_params_batch(p)` returns what is set (the shared parameters repeated if nothing is),
+`clear_model_params_batch!(p)` returns to the problem's model.  These entry points were added without raising `TO_ABI_MINOR`: a library
+that lacks them is detected by symbol lookup (`has_model_params_batch()`).
+"""
+has_model_params_batch() = Libdl.dlsym(Libdl.dlopen(lib), :to_set_model_params_batch; throw_error = false) !== nothing
+function set_model_params_batch!(p::BatchProblem, params::Matrix{Float64})
+    has_model_params_batch() || error("libtrajopt_hip.so does not export to_set_model_params_batch")
+    size(params) == (16, p.B) || throw(DimensionMismatch("params must be (16, B)"))
+    check(ccall((:to_set_model_params_batch, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}), p.handle, params))
+    nothing
+end
+function model_params_batch(p::BatchProblem)
+    has_model_params_batch() || error("libtrajopt_hip.so does not export to_get_model_params_batch")
+    params = zeros(16, p.B)
+    check(ccall((:to_get_model_params_batch, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}), p.handle, params))
+    params
+end
+function clear_model_params_batch!(p::BatchProblem)
+    has_model_params_batch() || error("libtrajopt_hip.so does not export to_clear_model_params_batch")
+    check(ccall((:to_clear_model_params_batch, lib), Cint, (Ptr{Cvoid},), p.handle))
+    nothing
+end
 function clear_goal_state_batch!(p::BatchProblem)
     check(ccall((:to_clear_cost_linear_batch, lib), Cint, (Ptr{Cvoid},), p.handle))
     check(ccall((:to_clear_constraint_params_batch, lib), Cint, (Ptr{Cvoid},), p.handle))
@@ -895,7 +921,7 @@ function profile(p::BatchProblem)
     (kernel_ms = ms, launches = launches)
 end
 
-export LinearMap, MassDoubleIntegrator, BatchProblem, policy_rollout, PolicyOpts, PolicyResult, policy_rollout_mc, policy_noise_draws, PolicyNoise, abi_minor, SolverOpts, solver_options, default_options, solve_ilqr!, solve_al!, solve_pn!, solve_altro!, solve_async!, wait_solve!, dynamics_defect, expand!, backwardpass!, forwardpass!,
+export LinearMap, MassDoubleIntegrator, BatchProblem, set_model_params_batch!, model_params_batch, clear_model_params_batch!, has_model_params_batch, policy_rollout, PolicyOpts, PolicyResult, policy_rollout_mc, policy_noise_draws, PolicyNoise, abi_minor, SolverOpts, solver_options, default_options, solve_ilqr!, solve_al!, solve_pn!, solve_altro!, solve_async!, wait_solve!, dynamics_defect, expand!, backwardpass!, forwardpass!,
     stage_costs, al_cost, dynamics_jacobians, cost_expansion, gains, cost_gradient_hessian, discrete_jacobian, duals, set_duals!,
     reset_duals!, dual_update!, comm_unique_id, comm_init_rank!, allgather!, allgather_stats, comm_shards, comm_destroy!, solver_path, knot_dims, device_count, build_id
 

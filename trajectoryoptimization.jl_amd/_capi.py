@@ -249,7 +249,14 @@ HIP_ONLY = {
     "policy_rollout_mc": [_H, C.c_int32, _PD, C.POINTER(PolicyOpts), C.POINTER(PolicyNoise), C.POINTER(PolicyResult)],
     "policy_noise_draws": [C.c_int, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, _PD],
     "abi_minor": [],
+    # one plant per trajectory on the planning side (OPTIONAL_HIP below)
+    "set_model_params_batch": [_H, _PD],
+    "get_model_params_batch": [_H, _PD],
+    "clear_model_params_batch": [_H],
 }
+# Entry points added without raising TO_ABI_MINOR (include/trajopt_hip.h, ABI history): detected by symbol lookup.  A library that does
+# not export them still loads; the names are then absent from Library._fn and the wrappers in api.py raise UnsupportedError.
+OPTIONAL_HIP = ("set_model_params_batch", "get_model_params_batch", "clear_model_params_batch")
 
 
 class Library:
@@ -264,6 +271,8 @@ class Library:
         if hip:
             sigs.update(HIP_ONLY)
         for name, argtypes in sigs.items():
+            if name in OPTIONAL_HIP and not hasattr(self.dll, prefix + name):
+                continue
             f = getattr(self.dll, prefix + name)  # AttributeError if the symbol is missing: loud
             f.argtypes = argtypes
             f.restype = C.c_int

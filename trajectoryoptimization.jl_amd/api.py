@@ -42,7 +42,7 @@ __all__ = [
     "GoalConstraint", "BoundConstraint", "NormConstraint", "CircleConstraint", "SphereConstraint", "CollisionConstraint", "QuatVecEq",
     "LinearConstraint", "StateBound", "ControlBound", "IndexedConstraint", "change_dimension",
     "ConstraintList", "add_constraint", "num_constraints", "constraint_hessians",
-    "KnotPoint", "Problem", "rollout", "policy_rollout", "PolicyRollout", "PolicyNoise", "policy_noise_draws", "cost", "states", "controls", "initial_controls", "initial_states",
+    "KnotPoint", "Problem", "rollout", "policy_rollout", "PolicyRollout", "PolicyNoise", "policy_noise_draws", "set_model_params", "model_params", "clear_model_params", "cost", "states", "controls", "initial_controls", "initial_states",
     "set_initial_state", "set_goal_state", "update_trajectory", "get_constraints", "get_objective", "get_model",
     "get_initial_state", "get_final_state", "get_trajectory", "gettimes",
     "SolverOptions", "iLQRSolver", "ALSolver", "ALTROSolver", "ProjectedNewtonSolver", "dynamics_defect", "solve", "SolvePipeline", "iterations", "status", "max_violation",
@@ -1464,6 +1464,53 @@ def policy_rollout(prob, X0s, alpha=0.0, refresh_gains=True, u_min=None, u_max=N
     else:
         prob._call("policy_rollout_mc", S, prob._pd(a), C.byref(o), C.byref(nz), C.byref(r))
     return PolicyRollout(J, cm, dxm, st, kl, X, U)
+
+
+def _need_model_params_batch(prob):
+    if "set_model_params_batch" not in prob._lib._fn:
+        raise UnsupportedError("per-trajectory model parameters need a HIP library that exports to_set_model_params_batch "
+                               "(the CPU oracle plans every trajectory on the problem's model)")
+
+
+def set_model_params(prob, models):
+    """One plant per TRAJECTORY (to_set_model_params_batch): trajectory ``b`` is planned — rolled out, expanded, solved, polished — on
+    ``models[b]``.  ``models``: a list of B models of the problem's class and dimensions, or a [B, 16] array of their parameters (the
+    conventions of ``policy_rollout(..., plants=)``).  X, U, duals and gains stay as they are: roll out or solve afterwards.
+    ``policy_rollout`` then simulates every trajectory on its own model unless a plant is named."""
+    _need_model_params_batch(prob)
+    B = prob.B
+    if isinstance(models, np.ndarray) and models.dtype != object:
+        pp = np.asarray(models, dtype=np.float64)
+        if pp.shape != (B, 16):
+            raise DimensionMismatch(f"models must be [B={B}, 16] parameters or B models; got {pp.shape}")
+    else:
+        rows = list(models)
+        if len(rows) != B:
+            raise DimensionMismatch(f"models must be [B={B}, 16] parameters or B models; got {len(rows)}")
+        pp = np.zeros((B, 16))
+        for b, mod in enumerate(rows):
+            if type(mod) is not type(prob.model) or mod.dims() != prob.model.dims():
+                raise ArgumentError(f"models[{b}] must be a {type(prob.model).__name__} with the problem's dimensions; got {type(mod).__name__}")
+            q = mod.params()
+            pp[b, : len(q)] = q
+    if not np.all(np.isfinite(pp)):
+        raise ArgumentError(f"models: the parameters of trajectory {int(np.argwhere(~np.isfinite(pp))[0][0])} are not finite")
+    pp = np.ascontiguousarray(pp)
+    prob._call("set_model_params_batch", prob._pd(pp))
+
+
+def model_params(prob):
+    """[B, 16]: the model parameters every trajectory is planned on (to_get_model_params_batch; the problem's own, repeated, if none are set)."""
+    _need_model_params_batch(prob)
+    pp = np.empty((prob.B, 16))
+    prob._call("get_model_params_batch", prob._pd(pp))
+    return pp
+
+
+def clear_model_params(prob):
+    """Back to the problem's model for every trajectory (to_clear_model_params_batch)."""
+    _need_model_params_batch(prob)
+    prob._call("clear_model_params_batch")
 
 
 def cost(prob):

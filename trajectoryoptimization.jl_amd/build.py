@@ -37,6 +37,13 @@ for _f in ("ops_quad_forward_a", "ops_quad_forward_b", "ops_quad_forward_c", "op
 # sign of a zero); the NaN-sensitive tests in those kernels work on bit patterns (common.h not_positive).
 for _f in ("ops_small_lane", "ops_small_scan"):
     FILE_FLAGS.setdefault(_f + ".hip", []).extend(["-fno-honor-nans", "-fno-honor-infinities", "-fno-signed-zeros"])
+# One plant per trajectory (DevProblem::pm): the flagged instances live in translation units of their own and are compiled like the unflagged
+# kernels they mirror — the Quadrotor expansion without common-code sinking, the forward passes with -ffp-contract=on, the lane expansion
+# with the zero-folding flags.
+FILE_FLAGS["ops_plants_quad.hip"] = list(FILE_FLAGS["ops_quad_expand.hip"])
+for _f in ("ops_plants_forward", "ops_plants_quad_forward"):
+    FILE_FLAGS.setdefault(_f + ".hip", []).append("-ffp-contract=on")
+FILE_FLAGS["ops_plants_lane.hip"] = list(FILE_FLAGS["ops_small_lane.hip"])
 OBJDIR = CSRC / "build"
 
 

@@ -38,10 +38,11 @@ def cartpole_x0(batch, b_offset=0, seed=1):
 
 
 def cartpole_problem(batch=1024, N=101, tf=5.0, b_offset=0, constrained=False, integration=T.RK4,
-                     u_bnd=3.0, device=0, lib=None, options=None):
+                     u_bnd=3.0, device=0, lib=None, options=None, model=None):
     """C2 (examples/Cartpole.ipynb cells 3-15; docs/src/creating_problems.md:34-53): Q=1e-2 I, R=1e-1, Qf=100 I,
-    xf=[0,π,0,0], U0≡0.01.  ``constrained`` adds the notebook's |u|≤3 bound and goal constraint."""
-    model = T.Cartpole()
+    xf=[0,π,0,0], U0≡0.01.  ``constrained`` adds the notebook's |u|≤3 bound and goal constraint.  ``model``: another Cartpole
+    (default: RobotZoo's parameters)."""
+    model = model if model is not None else T.Cartpole()
     n, m = model.dims()
     xf = np.array([0.0, math.pi, 0.0, 0.0])
     obj = T.LQRObjective(np.full(n, 1e-2), np.full(m, 1e-1), np.full(n, 100.0), xf, N)
@@ -78,14 +79,16 @@ C5_PN_STEPS = 8
 
 
 def quadrotor_problem(batch=4096, N=201, tf=5.0, b_offset=0, constrained=False, goal_inds=None, u_norm_max=6.0,
-                      integration=T.RK4, device=0, lib=None, options=None, quatvec_goal=False):
+                      integration=T.RK4, device=0, lib=None, options=None, quatvec_goal=False, model=None):
     """C3/C4 (shape from test/quatcosts.jl:152-168 + src/lie_costs.jl:133-142): point-to-point with QuatLQRCost,
     xf = (r=[2,3,1], yaw 135°), stage Q=diag(1,1,1, 0,0,0,0, .1×6), R=1e-2 I, terminal Q×100, U0≡hover.
     ``constrained`` = C5: GoalConstraint(xf)@N + NormConstraint(‖u‖₂≤6, SecondOrderCone)@1..N-1.
     ``quatvec_goal`` = C5': the terminal attitude is pinned as well, the reference's way — QuatVecEq(qf)@N
     (src/constraints.jl:938-965: the vector part of the NORMALISED quaternion, so RK4's drift off the unit sphere does not make
-    it infeasible the way the full 13-state GoalConstraint is)."""
-    model = T.Quadrotor()
+    it infeasible the way the full 13-state GoalConstraint is).  ``model``: another Quadrotor to plan on; costs and U0 keep the hover
+    control of the default one."""
+    nominal = T.Quadrotor()
+    model = model if model is not None else nominal
     n, m = model.dims()
     th = math.radians(135.0) / 2
     xf = np.zeros(n)
@@ -93,7 +96,7 @@ def quadrotor_problem(batch=4096, N=201, tf=5.0, b_offset=0, constrained=False, 
     xf[3:7] = [math.cos(th), 0.0, 0.0, math.sin(th)]
     Qd = np.array([1.0, 1, 1, 0, 0, 0, 0, .1, .1, .1, .1, .1, .1])
     Rd = np.full(m, 1e-2)
-    uhover = model.hover_control()
+    uhover = nominal.hover_control()
     stage = T.QuatLQRCost(Qd, Rd, xf, uhover, w=1.0)
     term = T.QuatLQRCost(100.0 * Qd, Rd, xf, uhover, w=1.0, terminal=True)
     obj = T.Objective(stage, term, N)

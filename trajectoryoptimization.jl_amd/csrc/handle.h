@@ -62,6 +62,8 @@ struct to_handle_s {
   int* d_crow = nullptr;    // [64] compact_row table of the model (tangent-matrix getters)
   std::vector<char> gl_set; // [n_costs] cost i carries per-trajectory linear terms (all clear: DevProblem::gl goes back to null)
   double* d_gl = nullptr;   // per-trajectory linear cost terms (DevProblem::gl), tiled, L = n_costs * (n + m); allocated on first use
+  double* d_pm = nullptr;   // per-trajectory model parameters (DevProblem::pm), tiled, L = 16, one spare tile; allocated on first use
+  std::vector<double> pm_host;  // [16, B] host copy of what to_set_model_params_batch was given (empty: shared parameters)
   double* d_cp = nullptr;   // per-trajectory constraint parameters (DevProblem::cp), tiled, L = (n + m) * number of constraints; allocated on first use
   double* d_tmp = nullptr;  // [Bp] scratch for reductions / outputs
   double* d_tmp2 = nullptr;
@@ -181,6 +183,16 @@ struct ModelOps {
   int (*accept_roll)(to_handle*) = nullptr;  // accept by re-rolling the stored controls (k_forward.h; models without write-through)
   int (*forward[32])(to_handle*) = {};  // by kernel variant (k_forward.h MODE bits); variants a model never uses stay null
   int (*forward2[32])(to_handle*) = {};  // the same variants as two-wave workgroups (k_forward2; models with LDS-staged gains)
+  // One plant per trajectory (DevProblem::pm set, to_set_model_params_batch): the flagged instances of the kernels that read model
+  // parameters (ops_plants_*.hip).  A handle with pm set runs the general variants only (path_plan.h `plants`), so there is one
+  // expansion per layout, the general forward variants (index = the mode, bit 3 set) and no fused / scan / packed / two-wave instance.
+  int (*rollout_pm)(to_handle*) = nullptr;
+  int (*discrete_jacobian_pm)(to_handle*, double* F) = nullptr;
+  int (*expand_pm)(to_handle*) = nullptr;        // column and tangent-matrix layouts (k_expand, general variant)
+  int (*expand_lane_pm)(to_handle*) = nullptr;   // lane layout (k_expand_lane, general variant)
+  int (*forward_pm[32])(to_handle*) = {};
+  int (*pn_launch_pm)(to_handle*, int slot0, int count, hipStream_t stream, const to_solver_opts* opts) = nullptr;
+  int (*defect_pm)(to_handle*, double* out) = nullptr;
 };
 
 // each ops_*.hip fills the entries it instantiates; table indexed by model key (0..2 double integrator D=1..3, 3 Cartpole,
@@ -212,6 +224,12 @@ void fill_ops_infeasible_a(ModelOps* table);
 void fill_ops_infeasible_b(ModelOps* table);
 void fill_ops_policy(ModelOps* table);
 void fill_ops_policy_mc(ModelOps* table);
+void fill_ops_plants_small(ModelOps* table);
+void fill_ops_plants_lane(ModelOps* table);
+void fill_ops_plants_forward(ModelOps* table);
+void fill_ops_plants_quad(ModelOps* table);
+void fill_ops_plants_quad_forward(ModelOps* table);
+void fill_ops_plants_pn(ModelOps* table);
 
 // handle-owned device memory (red zones around it in guard mode); g_free accepts what g_malloc returned
 int g_malloc(to_handle* h, void** p, size_t bytes, const char* name);

@@ -13,7 +13,8 @@ namespace to {
 // with v_j = [G(x_k) e_j; 0] (j<ne) or [0; e_{j-ne}].
 // VAR bit0: dense QuadraticCost possible; bit1: constraints present; bit2: non-selector constraints possible.  Code the
 // problem cannot reach is compiled out: the all-purpose Quadrotor kernel needed 256 VGPRs + 140 AGPRs + 480 B of scratch.
-// one knot of the expansion for lane (g, j): x = x_k, u = u_k (zeros at the terminal knot), x1 = x_{k+1}
+// one knot of the expansion for lane (g, j): x = x_k, u = u_k (zeros at the terminal knot), x1 = x_{k+1}; mp = the model parameters the
+// dynamics are differentiated with (P.mp — wave-uniform, SGPRs — or the flagged instances' per-trajectory registers, DevProblem::pm)
 // LAY: where the columns go.  0: column layout (cooperative backward pass); 1: tangent-matrix layout, full cost block;
 // 2: tangent-matrix layout, compact cost block; 3: lane layout (one lane per trajectory backward pass) — all in k_backward.h.
 // PACK (rigid body — quaternion, MRP or Rodrigues attitude —, compact cost block): six of the sixteen columns of [Ā B̄] are CONSTANTS — the dynamics do
@@ -27,7 +28,7 @@ template <class M> struct ExpandPack { static constexpr bool ok = M::lie && (M::
 template <class M, int FIXED_INTEG, int VAR, int LAY, bool PACK = false>
 __device__ __forceinline__ void expand_knot(const KArgs& a, int gtile, int lane, int tile, int lane64, int b, int j, int k, bool valid,
                                             const double* x, const double* u, const double* x1, const ConExp<M::m>& ce0,
-                                            const ConExp<M::m>& ce1, bool table_cons, int jc = -1, bool valid_c = false) {
+                                            const ConExp<M::m>& ce1, bool table_cons, const double* mp, int jc = -1, bool valid_c = false) {
   constexpr int n = M::n, m = M::m, ne = M::ne, nz = n + m, nc = ne + m;
   static_assert(!PACK || (LAY == 2 && ExpandPack<M>::ok), "packed expansion: compact tangent-matrix layout of the rigid body");
   constexpr int NEP = Tm<M>::NEP, RS = Tm<M>::RS, NR = Tm<M>::NR;
@@ -72,7 +73,7 @@ __device__ __forceinline__ void expand_knot(const KArgs& a, int gtile, int lane,
     for (int i = 0; i < n; ++i) xd[i] = Dual(x[i], v[i]);
 #pragma unroll
     for (int i = 0; i < m; ++i) ud[i] = Dual(u[i], v[n + i]);
-    model_step<M, Dual, FIXED_INTEG>(P.mp, P.integrator, k, xd, ud, P.dt[k], xn);
+    model_step<M, Dual, FIXED_INTEG>(mp, P.integrator, k, xd, ud, P.dt[k], xn);
     double t[n], col[ne];
 #pragma unroll
     for (int i = 0; i < n; ++i) t[i] = xn[i].d;
@@ -276,8 +277,9 @@ __host__ __device__ constexpr int expand_kc() {
 #define TO_EXPAND_WAVES 1  // minimum waves per SIMD k_expand is compiled for (register cap 512 / waves)
 #endif
 constexpr int EXPAND_PACK_G = 6, EXPAND_PACK_R = 10;  // packed expansion: trajectories per wave x differentiated columns (lanes 60..63 idle)
-template <class M, int FIXED_INTEG, int VAR, int LAY, bool PACK = false>
+template <class M, int FIXED_INTEG, int VAR, int LAY, bool PACK = false, bool PM = false>
 __global__ void __launch_bounds__(64, TO_EXPAND_WAVES) k_expand(KArgs a) {
+  static_assert(!PM || !PACK, "per-trajectory model parameters: the general variants only (DESIGN.md §4c)");
   constexpr int n = M::n, m = M::m, ne = M::ne, nc = ne + m, KC = expand_kc<M, VAR>();
   constexpr int R = PACK ? EXPAND_PACK_R : Coop<M>::R, G = PACK ? EXPAND_PACK_G : Coop<M>::G;
   const int gtile = blockIdx.x, lane = threadIdx.x;
@@ -326,6 +328,10 @@ __global__ void __launch_bounds__(64, TO_EXPAND_WAVES) k_expand(KArgs a) {
   }
   const double* X = X_SLOT_PTR(a, b, c);
   const double* U = U_SLOT_PTR(a, b, c);
+  // PM: this trajectory's own model parameters, once, ahead of the knot loop (b is a valid trajectory for every lane: idle lanes compute along)
+  double pmr[PM ? 16 : 1];
+  const double* mp = P.mp;
+  if constexpr (PM) { load_plant(P, b, pmr); mp = pmr; }
   double x[n], u[m], x1[n], x2[n], un[m];
 #pragma unroll
   for (int i = 0; i < n; ++i) { x[i] = EL(X, k0 * n + i); x1[i] = (k0 + 1 < N) ? EL(X, (k0 + 1) * n + i) : 0.0; }
@@ -353,7 +359,7 @@ __global__ void __launch_bounds__(64, TO_EXPAND_WAVES) k_expand(KArgs a) {
         for (int i = 0; i < m; ++i) EL(U0, k * m + i) = u[i];
       }
     }
-    expand_knot<M, FIXED_INTEG, VAR, LAY, PACK>(a, gtile, lane, tile, lane64, b, j, k, valid, x, u, x1, ce0, ce1, table_cons, jc, lane_ok);
+    expand_knot<M, FIXED_INTEG, VAR, LAY, PACK>(a, gtile, lane, tile, lane64, b, j, k, valid, x, u, x1, ce0, ce1, table_cons, mp, jc, lane_ok);
     if (KC > 1) {
 #pragma unroll
       for (int i = 0; i < n; ++i) { x[i] = x1[i]; x1[i] = x2[i]; }
@@ -400,13 +406,13 @@ __global__ void __launch_bounds__(64) k_expand_const_columns(KArgs a) {
 // the cost (+AL) block, g[j] = gradient.  Same calls and the same order of the constraint terms as expand_knot's table path.
 template <class M, int FIXED_INTEG, int VAR>
 __device__ __forceinline__ void expand_lane_knot(const KArgs& a, int tile, int lane, int k, const double* x, const double* u,
-                                                 double* Mk, double* H, double* g) {
+                                                 double* Mk, double* H, double* g, const double* mp) {
   static_assert(!M::lie, "lane expansion: vector-space models only (identity error-state maps)");
   constexpr int n = M::n, m = M::m, ne = M::ne, nz = n + m, nc = ne + m;
   const DevProblem& P = a.P;
   const bool terminal = (k == P.N - 1);
   if constexpr (has_stage_jac<M>::value && FIXED_INTEG == INTEG_RK4) {
-    if (!terminal) cartpole_rk4_jac(P.mp, x, u, P.dt[k], Mk);  // chain rule over hand-derived stage partials (models.h)
+    if (!terminal) cartpole_rk4_jac(mp, x, u, P.dt[k], Mk);  // chain rule over hand-derived stage partials (models.h)
   } else
   if (!terminal) {  // every column of [A B] in one pass
     MDual<nc> xd[n], ud[m], xn[n];
@@ -414,7 +420,7 @@ __device__ __forceinline__ void expand_lane_knot(const KArgs& a, int tile, int l
     for (int i = 0; i < n; ++i) { xd[i].v = x[i]; xd[i].d[i] = 1.0; }
 #pragma unroll
     for (int i = 0; i < m; ++i) { ud[i].v = u[i]; ud[i].d[ne + i] = 1.0; }
-    model_step<M, MDual<nc>, FIXED_INTEG>(P.mp, P.integrator, k, xd, ud, P.dt[k], xn);
+    model_step<M, MDual<nc>, FIXED_INTEG>(mp, P.integrator, k, xd, ud, P.dt[k], xn);
 #pragma unroll
     for (int i = 0; i < ne; ++i)
 #pragma unroll
@@ -490,7 +496,7 @@ __device__ __forceinline__ void expand_lane_knot(const KArgs& a, int tile, int l
 
 // the expansion as a kernel of its own (phase API, and the solve loop when the fused backward pass is switched off):
 // writes the lane layout as whole 512-byte rows, lane = trajectory.  grid (Bp / 64, N).
-template <class M, int FIXED_INTEG, int VAR>
+template <class M, int FIXED_INTEG, int VAR, bool PM = false>
 __global__ void __launch_bounds__(64) k_expand_lane(KArgs a) {
   constexpr int n = M::n, m = M::m, ne = M::ne, nc = ne + m;
   using L = LaneLay<M>;
@@ -520,7 +526,10 @@ __global__ void __launch_bounds__(64) k_expand_lane(KArgs a) {
     }
   }
   double Mk[ne * nc], H[L::NS], g[nc];
-  expand_lane_knot<M, FIXED_INTEG, VAR>(a, tile, lane, k, x, u, Mk, H, g);
+  double pmr[PM ? 16 : 1];  // PM: the trajectory's own model parameters (here lane = trajectory; padding lanes hold the shared ones)
+  const double* mp = P.mp;
+  if constexpr (PM) { load_plant(P, b, pmr); mp = pmr; }
+  expand_lane_knot<M, FIXED_INTEG, VAR>(a, tile, lane, k, x, u, Mk, H, g, mp);
   if (!live) return;
   if (!terminal) {
     double* Ml = a.Mc + (((size_t)tile * (size_t)(N - 1) + k) * (ne * nc)) * 64 + lane;
@@ -743,7 +752,7 @@ __global__ void __launch_bounds__(64, TO_FUSED_LANE_WAVES) k_expand_backward_lan
 #pragma unroll
         for (int i = 0; i < n; ++i) EL(X0, (N - 1) * n + i) = x[i];
       }
-      expand_lane_knot<M, FIXED_INTEG, VAR>(a, tile, lane, N - 1, x, u, Mk, H, g);
+      expand_lane_knot<M, FIXED_INTEG, VAR>(a, tile, lane, N - 1, x, u, Mk, H, g, a.P.mp);
 #pragma unroll
       for (int i = 0; i < ne; ++i) {
 #pragma unroll
@@ -783,7 +792,7 @@ __global__ void __launch_bounds__(64, TO_FUSED_LANE_WAVES) k_expand_backward_lan
         for (int i = 0; i < m; ++i) EL(U0, k * m + i) = u[i];
       }
       double Me[ne * nc], H[NS], g[nc];
-      expand_lane_knot<M, FIXED_INTEG, VAR>(a, tile, lane, k, x, u, Me, H, g);
+      expand_lane_knot<M, FIXED_INTEG, VAR>(a, tile, lane, k, x, u, Me, H, g, a.P.mp);
       double Mk[ne][nc];
 #pragma unroll
       for (int i = 0; i < ne; ++i)
@@ -1088,7 +1097,7 @@ __global__ void __launch_bounds__(128) k_expand_backward_coop(KArgs a) {
           double Mk[ne * nc], H[LL::NS], gq[nc];
 #pragma unroll
           for (int e = 0; e < ne * nc; ++e) Mk[e] = 0.0;
-          expand_lane_knot<M, FIXED_INTEG, VAR>(a, etile, elane, k, x, u, Mk, H, gq);
+          expand_lane_knot<M, FIXED_INTEG, VAR>(a, etile, elane, k, x, u, Mk, H, gq, a.P.mp);
           double* dst = ring + (size_t)(s & 1) * F::chunk + ((size_t)(kk * G + ge) * R) * EW;
 #pragma unroll
           for (int jj = 0; jj < nc; ++jj) {

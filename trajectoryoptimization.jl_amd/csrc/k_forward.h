@@ -70,7 +70,8 @@ __host__ __device__ inline int gains_lds_doubles(int TW) {  // per buffer, whole
 // partially masked wave issues FP64 ~1.3x slower on gfx950) but store nothing.
 // MODE bit0: simple_stage (stage cost preloaded into registers, uniform dt); bit1: constraints present (AL terms);
 // bit2: RK4 fixed at compile time; bit3: dense costs / non-selector constraints possible (else compiled out);
-// bit4: the register-cached control constraints are unit SOCs (problem_dev.h unit_soc_desc).
+// bit4: the register-cached control constraints are unit SOCs (problem_dev.h unit_soc_desc);
+// bit5: one plant per trajectory — the mp[] copy below comes from DevProblem::pm, indexed by the trajectory b (one-wave general variants only).
 // kbuf: the wave's two LDS buffers for DMA-staged gains (M::lds_gains); krow: this lane's row offset in a buffer.
 template <class M, int MODE>
 __device__ __forceinline__ void forward_candidate(const KArgs& a, int tile, int lane, int b, bool live, double alpha, int wblock, double* kbuf,
@@ -95,8 +96,11 @@ __device__ __forceinline__ void forward_candidate(const KArgs& a, int tile, int 
   const double* mu0 = TILE_PTR(a.mu, P.n_cons);
   // everything wave-uniform the loop needs is fetched ONCE: an in-order wave stalls on every scalar-load round trip
   double mp[16];
+  if constexpr ((MODE & 32) != 0) load_plant(P, b, mp);
+  else {
 #pragma unroll
-  for (int i = 0; i < 16; ++i) mp[i] = in_vgpr(P.mp[i]);
+    for (int i = 0; i < 16; ++i) mp[i] = in_vgpr(P.mp[i]);
+  }
   const int integrator = P.integrator;
   const bool dt_scaling = P.opts.cost_dt_scaling != 0;
   const double max_x = o.max_state_value, max_u = o.max_control_value;

@@ -5,7 +5,7 @@
 namespace to {
 
 // ------------------------------------------------------------------------------------------------ rollout!
-template <class M, int FIXED_INTEG>
+template <class M, int FIXED_INTEG, bool PM = false>  // PM: one plant per trajectory (DevProblem::pm), loaded ahead of the knot loop
 __global__ void __launch_bounds__(64) k_rollout(KArgs a) {  // src/problem.jl:334-340 — open-loop simulate from x0
   constexpr int n = M::n, m = M::m;
   TILE_LANE();
@@ -16,6 +16,9 @@ __global__ void __launch_bounds__(64) k_rollout(KArgs a) {  // src/problem.jl:33
   const double* U = U_SLOT_PTR(a, b, c);
   const double* x0 = TILE_PTR(a.x0, n);
   double x[n], u[m], xn[n];
+  double pmr[PM ? 16 : 1];
+  const double* mp = P.mp;
+  if constexpr (PM) { load_plant(P, b, pmr); mp = pmr; }
 #pragma unroll
   for (int i = 0; i < n; ++i) { x[i] = EL(x0, i); EL(X, i) = x[i]; }
   int lim = 0;  // first knot beyond max_state_value / max_control_value: the state it arrives at first, then the control (Altro's rollout!)
@@ -23,7 +26,7 @@ __global__ void __launch_bounds__(64) k_rollout(KArgs a) {  // src/problem.jl:33
   for (int k = 0; k < P.N - 1; ++k) {
 #pragma unroll
     for (int i = 0; i < m; ++i) u[i] = EL(U, k * m + i);
-    model_step<M, double, FIXED_INTEG>(P.mp, P.integrator, k, x, u, P.dt[k], xn);
+    model_step<M, double, FIXED_INTEG>(mp, P.integrator, k, x, u, P.dt[k], xn);
     double mx = 0.0, mu = 0.0;
 #pragma unroll
     for (int i = 0; i < n; ++i) { x[i] = xn[i]; EL(X, (k + 1) * n + i) = x[i]; const double v = fabs(x[i]); mx = !(v <= mx) ? v : mx; }
@@ -243,7 +246,7 @@ __global__ void __launch_bounds__(64) k_cost_derivs(KArgs a, double* grad, doubl
 }
 
 // RD.jacobian! of the discretised dynamics on the full state: F[n, n+m, N-1, B]
-template <class M>
+template <class M, bool PM = false>
 __global__ void __launch_bounds__(64) k_discrete_jacobian(KArgs a, double* F) {
   constexpr int n = M::n, m = M::m, nz = n + m;
   TILE_LANE();
@@ -258,7 +261,10 @@ __global__ void __launch_bounds__(64) k_discrete_jacobian(KArgs a, double* F) {
   for (int i = 0; i < n; ++i) xd[i] = Dual(EL(X, k * n + i), (i == j) ? 1.0 : 0.0);
 #pragma unroll
   for (int i = 0; i < m; ++i) ud[i] = Dual(EL(U, k * m + i), (n + i == j) ? 1.0 : 0.0);
-  model_step<M, Dual>(P.mp, P.integrator, k, xd, ud, P.dt[k], xn);
+  double pmr[PM ? 16 : 1];
+  const double* mp = P.mp;
+  if constexpr (PM) { load_plant(P, b, pmr); mp = pmr; }
+  model_step<M, Dual>(mp, P.integrator, k, xd, ud, P.dt[k], xn);
   const size_t kb = (size_t)k + (size_t)(N - 1) * b;
 #pragma unroll
   for (int i = 0; i < n; ++i) F[(size_t)i + n * ((size_t)j + nz * kb)] = xn[i].d;

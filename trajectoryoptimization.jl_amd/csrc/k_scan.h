@@ -409,7 +409,7 @@ __global__ void __launch_bounds__(64, 1) k_expand_backward_scan(KArgs a) {
       double Mk[ne * nc], H[LL::NS], g[nc], Hd[nc];
 #pragma unroll
       for (int i = 0; i < ne * nc; ++i) Mk[i] = 0.0;
-      expand_lane_knot<M, FIXED_INTEG, VAR>(a, tile, lane, k, x, u, Mk, H, g);
+      expand_lane_knot<M, FIXED_INTEG, VAR>(a, tile, lane, k, x, u, Mk, H, g, a.P.mp);
 #pragma unroll
       for (int j = 0; j < nc; ++j) { Hd[j] = (terminal && j >= ne) ? 1.0 : H[LL::sym(j, j)]; if (terminal && j >= ne) g[j] = 0.0; }
       double* pk = park + (size_t)kk * PK * 64 + l;

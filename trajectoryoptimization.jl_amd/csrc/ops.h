@@ -271,6 +271,53 @@ void fill_forward2(ModelOps& o) {
   }
 }
 
+// ---- one plant per trajectory (DevProblem::pm): launchers of the flagged instances, instantiated by the ops_plants_*.hip translation units
+template <class M>
+int op_rollout_pm(to_handle* h) {
+  bool done = false;
+  if constexpr (M::pin_rk4) {
+    if (h->a.P.integrator == INTEG_RK4) { hipLaunchKernelGGL((k_rollout<M, INTEG_RK4, true>), grid_b(h), dim3(BLOCK), 0, h->stream, h->a); done = true; }
+  }
+  if (!done) hipLaunchKernelGGL((k_rollout<M, -1, true>), grid_b(h), dim3(BLOCK), 0, h->stream, h->a);
+  HIPCHECK(hipGetLastError());
+  return TO_OK;
+}
+template <class M>
+int op_discrete_jacobian_pm(to_handle* h, double* F) {
+  const DevProblem& P = h->a.P;
+  hipLaunchKernelGGL((k_discrete_jacobian<M, true>), grid_b(h, P.N - 1, P.n + P.m), dim3(BLOCK), 0, h->stream, h->a, F);
+  HIPCHECK(hipGetLastError());
+  return TO_OK;
+}
+// the general variant (7) on the column layout or the full tangent-matrix layout (the handle's expand_variant has bit 2 forced: no compact cost block)
+template <class M, int FI>
+int op_expand_pm_fi(to_handle* h) {
+  const DevProblem& P = h->a.P;
+  constexpr int kc = expand_kc<M, 2>();
+  const dim3 grid((P.B + h->G - 1) / h->G, (P.N + kc - 1) / kc);
+  if (h->a.bwd_lane || h->a.h_compact) return fail(TO_ERR_UNSUPPORTED, "per-trajectory model parameters: expansion layout without a flagged instance");
+  if constexpr (M::mfma_backward) {
+    if (h->a.bwd_mfma) { hipLaunchKernelGGL((k_expand<M, FI, 7, 1, false, true>), grid, dim3(BLOCK), 0, h->stream, h->a); HIPCHECK(hipGetLastError()); return TO_OK; }
+  }
+  if constexpr (!M::mfma_backward || M::coop_backward) {
+    if (!h->a.bwd_mfma) { hipLaunchKernelGGL((k_expand<M, FI, 7, 0, false, true>), grid, dim3(BLOCK), 0, h->stream, h->a); HIPCHECK(hipGetLastError()); return TO_OK; }
+  }
+  return fail(TO_ERR_UNSUPPORTED, "per-trajectory model parameters: expansion not compiled for this model and layout");
+}
+template <class M>
+int op_expand_pm(to_handle* h) {
+  if constexpr (M::pin_rk4) {
+    if (h->a.P.integrator == INTEG_RK4) return op_expand_pm_fi<M, INTEG_RK4>(h);
+  }
+  return op_expand_pm_fi<M, -1>(h);
+}
+// general forward variants GEN (bit 3 set) with the plant loaded per trajectory (k_forward.h MODE bit 5)
+template <class M, int GEN>
+void fill_forward_pm(ModelOps& o) {
+  static_assert((GEN & 8) != 0 && GEN < 32, "per-trajectory model parameters: general forward variants only");
+  if constexpr (M::pin_rk4 || (GEN & 4) == 0) o.forward_pm[GEN] = op_forward<M, (GEN | 32)>;
+}
+
 template <class M>
 void fill_misc(ModelOps& o) {
   fill_traits<M>(o);

@@ -30,6 +30,23 @@ int op_expand_lane(to_handle* h) {
   return op_expand_lane_fi<M, -1>(h);
 }
 
+// one plant per trajectory (DevProblem::pm): the general variant with the parameters loaded per lane (= trajectory)
+template <class M>
+int op_expand_lane_pm(to_handle* h) {
+  if constexpr (M::lane_backward && !M::lie) {
+    const DevProblem& P = h->a.P;
+    const dim3 lgrid(P.Bp / BLOCK, P.N);
+    bool done = false;
+    if constexpr (M::pin_rk4) {
+      if (P.integrator == INTEG_RK4) { hipLaunchKernelGGL((k_expand_lane<M, INTEG_RK4, 7, true>), lgrid, dim3(BLOCK), 0, h->stream, h->a); done = true; }
+    }
+    if (!done) hipLaunchKernelGGL((k_expand_lane<M, -1, 7, true>), lgrid, dim3(BLOCK), 0, h->stream, h->a);
+    HIPCHECK(hipGetLastError());
+    return TO_OK;
+  }
+  return fail(TO_ERR_UNSUPPORTED, "lane expansion not compiled for this model");
+}
+
 // large batches of the small models: expansion fused into the one-lane-per-trajectory backward pass (k_expand.h)
 template <class M, int FI>
 int op_expand_backward_fi(to_handle* h) {

@@ -2,8 +2,7 @@
 #include <algorithm>
 #include <vector>
 
-#include "handle.h"
-#include "k_pn.h"
+#include "ops_pn.h"
 
 namespace to {
 
@@ -59,38 +58,6 @@ int op_pn_prepare(to_handle* h, int want) {
   HIPCHECK(hipMemcpyAsync(h->pn_pak, pak.data(), sizeof(int) * N, hipMemcpyHostToDevice, h->stream));
   HIPCHECK(hipMemcpyAsync(h->pn_koff, koff.data(), sizeof(long long) * (N + 1), hipMemcpyHostToDevice, h->stream));
   HIPCHECK(hipStreamSynchronize(h->stream));  // the host vectors go out of scope
-  return TO_OK;
-}
-
-template <class M>
-int op_pn_launch(to_handle* h, int slot0, int count, hipStream_t stream, const to_solver_opts* opts) {
-  if (count <= 0) return TO_OK;
-  const int N = h->a.P.N;
-  PnArgs q;
-  q.a = h->a;
-  q.a.P.opts = *opts;
-  q.pak = h->pn_pak; q.koff = h->pn_koff; q.list = h->pn_list; q.nbmax = h->pn_nbmax;
-  q.ws = h->pn_ws + (size_t)slot0 * (size_t)h->pn_per;
-  q.base = slot0;
-  q.it_pn = h->a.it_pn; q.cmax_out = h->a.pn_cmax;
-  const size_t lds = sizeof(double) * (size_t)pn_lds_doubles<M>(q.nbmax);
-  constexpr int nc = M::ne + M::m;
-  const int col_blocks = ((N - 1) * nc + 63) / 64, knot_blocks = N;
-  for (int round = 0; round <= opts->n_steps + 1; ++round) {
-    hipLaunchKernelGGL(k_pn_begin<M>, dim3(count), dim3(64), lds, stream, q, round);
-    if (round == opts->n_steps + 1) break;
-    hipLaunchKernelGGL(k_pn_lin_col<M>, dim3(count, col_blocks), dim3(64), 0, stream, q);
-    hipLaunchKernelGGL(k_pn_lin_knot<M>, dim3(count, knot_blocks), dim3(64), 0, stream, q);
-    hipLaunchKernelGGL(k_pn_project<M>, dim3(count), dim3(64), lds, stream, q);
-  }
-  HIPCHECK(hipGetLastError());
-  return TO_OK;
-}
-
-template <class M>
-int op_defect(to_handle* h, double* out) {
-  hipLaunchKernelGGL(k_defect<M>, grid_b(h), dim3(BLOCK), 0, h->stream, h->a, out);
-  HIPCHECK(hipGetLastError());
   return TO_OK;
 }
 

@@ -161,27 +161,42 @@ inline PathPlan plan_paths(const PathTraits& t, const PathShape& s, const PathKn
   }
   return p;
 }
+// `plants` (the trailing argument of the predicates below): the handle carries one set of model parameters per trajectory
+// (DevProblem::pm, to_set_model_params_batch).  Only the general kernel variants have instances that read them, so such a handle is routed
+// the way one with per-trajectory constraint parameters is — its expand_variant has bit 2 forced, which already rules out the scan and the
+// fused cooperative kernel — and, beyond that, never takes the fused lane kernel, the two-wave forward pass, the control-only candidate
+// stores with their re-roll (k_accept_roll), the two-launch line search or the repacked working set.
 // the fused cooperative kernel serves the diagonal cost blocks of the expansion variants 0 / 2; the scan kernel variant 0 only
-inline bool fused_coop_now(const PathPlan& p, int h_diag, int expand_variant) { return p.fused_coop && h_diag && (expand_variant == 0 || expand_variant == 2); }
-inline bool scan_now(const PathPlan& p, int h_diag, int expand_variant) { return p.scan && fused_coop_now(p, h_diag, expand_variant) && expand_variant == 0; }
+inline bool fused_coop_now(const PathPlan& p, int h_diag, int expand_variant, bool plants = false) {
+  return !plants && p.fused_coop && h_diag && (expand_variant == 0 || expand_variant == 2);
+}
+inline bool scan_now(const PathPlan& p, int h_diag, int expand_variant, bool plants = false) {
+  return p.scan && fused_coop_now(p, h_diag, expand_variant, plants) && expand_variant == 0;
+}
+// active-list compaction of a solve: the plan's, except on the lane layout with `plants` — there compaction belongs to the fused lane kernel
+// (the separate lane kernels address the batch by position, as they do with TRAJOPT_FUSED_LANE=0)
+inline int solve_compact(const PathPlan& p, bool plants = false) { return (plants && !p.bwd_mfma) ? 0 : p.compact; }
 inline int roll_min(const PathPlan& p, const PathTraits& t) { return p.roll_min_active >= 0 ? p.roll_min_active : t.write_through ? 32768 : 2048; }
 // repacked working set (trajopt_hip.hip rp_move): iLQR solves of the small models on the fused lane path with compaction
-inline bool working_set_repack(const PathPlan& p, const PathTraits& t) { return p.fused_lane && p.compact && t.write_through && p.rp_min > 0; }
+inline bool working_set_repack(const PathPlan& p, const PathTraits& t, bool plants = false) {
+  return !plants && p.fused_lane && p.compact && t.write_through && p.rp_min > 0;
+}
 enum StepKind { STEP_SPLIT, STEP_FUSED_LANE, STEP_FUSED_COOP, STEP_SCAN };  // expansion + backward pass of one batch step
 struct StepPlan { StepKind kind; int CW, TW; bool two_wave; int store_x; bool two_launch; };  // + forward-wave shape, two-wave workgroups, KArgs::store_x, two-launch search
 // What one batch step launches, from the last active count the host has seen (results do not depend on it) and the batch B it works on.
-inline StepPlan plan_step(const PathPlan& p, const PathTraits& t, int h_diag, int expand_variant, int compact_armed, int last_active, int B) {
+inline StepPlan plan_step(const PathPlan& p, const PathTraits& t, int h_diag, int expand_variant, int compact_armed, int last_active, int B,
+                          bool plants = false) {
   StepPlan s;
-  s.kind = p.fused_lane ? STEP_FUSED_LANE          // expansion in the registers of the lane that runs the recursion
-           : scan_now(p, h_diag, expand_variant) && last_active <= p.scan_max_active ? STEP_SCAN  // the recursion as a scan over the horizon (k_scan.h)
-           : fused_coop_now(p, h_diag, expand_variant) ? STEP_FUSED_COOP  // expansion by a second wave of the workgroup, through an LDS ring
+  s.kind = (p.fused_lane && !plants) ? STEP_FUSED_LANE          // expansion in the registers of the lane that runs the recursion
+           : scan_now(p, h_diag, expand_variant, plants) && last_active <= p.scan_max_active ? STEP_SCAN  // the recursion as a scan over the horizon (k_scan.h)
+           : fused_coop_now(p, h_diag, expand_variant, plants) ? STEP_FUSED_COOP  // expansion by a second wave of the workgroup, through an LDS ring
            : STEP_SPLIT;
   const bool deep = p.cw_deep && last_active <= p.deep_max_active;
   s.CW = deep ? p.cw_deep : p.cw_base; s.TW = deep ? p.tw_deep : p.tw_base;
   // workgroup shape: two waves per candidate group (roller + accountant, k_forward2) shorten the rollout's latency chain by a third, but need twice
   // the wave slots — taken once both waves of every workgroup get a SIMD of their own
   // (C3: 610 vs 812 us per step with the chip full, 480 vs 320 us once the batch has drained)
-  s.two_wave = p.fwd2 == 2 && 2 * wave_blocks(last_active, s.TW) <= (long long)p.simds;
+  s.two_wave = !plants && p.fwd2 == 2 && 2 * wave_blocks(last_active, s.TW) <= (long long)p.simds;
   // ... and what it stores per candidate: with the chip full the pass is bound by its stores, 3/4 of them candidate states that are read once (the
   // accepted one) or never — from roll_min active trajectories on only the controls go out and the accepted candidates are rolled out again
   // (k_accept_roll: bit-identical states, one more latency chain of N-1 steps)
@@ -200,23 +215,23 @@ inline StepPlan plan_step(const PathPlan& p, const PathTraits& t, int h_diag, in
   // the re-roll takes 0.9 ms with every trajectory active and 1.8 ms with a quarter of them); the write-through of the next expansion makes the same
   // scattered stores, but behind 2 000 instructions per knot
   const bool dense = !t.write_through || (double)last_active >= p.roll_min_frac * (double)B;
-  s.store_x = (rmin > 0 && t.accept_roll && !s.two_wave && last_active >= rmin && dense) ? 0 : 1;
+  s.store_x = (!plants && rmin > 0 && t.accept_roll && !s.two_wave && last_active >= rmin && dense) ? 0 : 1;
   // two-launch line search (common.h ls_phase): launch A — one round for everybody; flags -> list; launch B — the rest of the search for the flagged
   // trajectories only; then the accept.  Same candidates, same first accepted step size: bit-identical.
   s.two_launch = !s.store_x && p.ls2_cwa && compact_armed && p.fwd2 != 1;
   return s;
 }
 // to_solver_path: what a handle's solves run, from the predicates plan_step uses
-inline void path_report(const PathPlan& p, const PathTraits& t, int h_diag, int expand_variant, int B, int32_t info[8]) {
+inline void path_report(const PathPlan& p, const PathTraits& t, int h_diag, int expand_variant, int B, int32_t info[8], bool plants = false) {
   info[0] = p.bwd_mfma ? 1 : p.bwd_lane ? 2 : 0;
-  info[1] = (p.fused_lane || fused_coop_now(p, h_diag, expand_variant)) ? 1 : 0;
-  info[2] = p.compact;
+  info[1] = ((p.fused_lane && !plants) || fused_coop_now(p, h_diag, expand_variant, plants)) ? 1 : 0;
+  info[2] = solve_compact(p, plants);
   info[3] = p.cw_base;
-  info[4] = (p.fwd2 && t.forward2) ? 2 : 1;  // (two-wave workgroups are used while the active trajectories leave room for them)
-  info[5] = scan_now(p, h_diag, expand_variant) ? 1 : 0;
-  info[6] = (t.accept_roll && p.roll_min_active != 0) ? 1 : 0;  // full-chip batch steps store candidate controls only (k_accept_roll)
+  info[4] = (!plants && p.fwd2 && t.forward2) ? 2 : 1;  // (two-wave workgroups are used while the active trajectories leave room for them)
+  info[5] = scan_now(p, h_diag, expand_variant, plants) ? 1 : 0;
+  info[6] = (!plants && t.accept_roll && p.roll_min_active != 0) ? 1 : 0;  // full-chip batch steps store candidate controls only (k_accept_roll)
   info[7] = p.repack_block0 != 0 ? 1 : 0;                        // repacked last line-search round
-  if (working_set_repack(p, t) && B >= p.rp_min) info[7] |= 2;   // repacked working set (iLQR solves)
+  if (working_set_repack(p, t, plants) && B >= p.rp_min) info[7] |= 2;   // repacked working set (iLQR solves)
 }
 // Forward-pass kernel variant (k_forward.h MODE bits): bit0 simple stage cost, bit1 constraints, bit2 compile-time RK4 (models that
 // pin it), bit3 dense costs / generic constraints / per-trajectory terms, bit4 unit-SOC; `mask` holds the compiled ones.  -1: none fits.

@@ -60,7 +60,19 @@ struct DevProblem {
   // (con_shift).  A LinearConstraint A z = b + db is the shared one seen from z - A^+ db (the host forms the minimum-norm A^+ db).  NULL (the default): every trajectory shares the descriptors.  Read by the GENERAL kernel variants only.
   const double* cp;
   int n_cp;
+  // Per-trajectory model parameters (to_set_model_params_batch: one plant per trajectory): tiled array, L = 16; entry i of trajectory b
+  // sits at pm[((b >> 6) * 16 + i) * 64 + (b & 63)].  NULL (the default): every trajectory is planned on mp.  Read by the flagged (PM)
+  // kernel instances only — the others keep mp wave-uniform in SGPRs and never look at this pointer.
+  const double* pm;
 };
+
+// The 16 model parameters of trajectory b into registers (the flagged kernel instances, once, ahead of their knot loops): indexed by the
+// TRAJECTORY, never by the hardware lane — under active-list compaction and in the column lane maps the two differ.
+__device__ __forceinline__ void load_plant(const DevProblem& P, int b, double* mp) {
+  const double* pp = P.pm + ((size_t)(b >> 6) * 16) * 64 + (b & 63);
+#pragma unroll
+  for (int i = 0; i < 16; ++i) mp[i] = pp[(size_t)i * 64];
+}
 
 // z = [x; u] as constraint K sees it for this lane's trajectory (cp0: the lane's pointer to entry 0 of DevProblem::cp; blocks of nz = n + m)
 template <int nz>

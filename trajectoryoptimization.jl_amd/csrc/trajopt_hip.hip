@@ -121,6 +121,8 @@ const ModelOps* model_ops(int key) {
     fill_ops_hybrid(g_ops); fill_ops_small_forward2(g_ops); fill_ops_small_scan(g_ops); fill_ops_pn(g_ops); fill_ops_vector(g_ops); fill_ops_infeasible_a(g_ops); fill_ops_infeasible_b(g_ops);
     fill_ops_policy(g_ops);
     fill_ops_policy_mc(g_ops);
+    fill_ops_plants_small(g_ops); fill_ops_plants_lane(g_ops); fill_ops_plants_forward(g_ops);
+    fill_ops_plants_quad(g_ops); fill_ops_plants_quad_forward(g_ops); fill_ops_plants_pn(g_ops);
   });
   return (key >= 0 && key < N_MODEL_KEYS) ? &g_ops[key] : nullptr;
 }
@@ -245,6 +247,7 @@ int upload_tables(to_handle* h) {
     for (const auto& c : h->costs) dense = dense || c.kind == TO_COST_QUADRATIC || c.kind == TO_COST_ERROR_QUADRATIC;
     for (const auto& c : h->cons) generic = generic || !c.selector;
     for (const auto& c : h->cons) generic = generic || c.cp_off >= 0;  // per-trajectory parameters are read by the general variants only
+    generic = generic || P.pm != nullptr;  // ... and per-trajectory model parameters by the flagged instances of the general variants only
     P.expand_variant = (dense ? 1 : 0) | (h->cons.empty() ? 0 : 2) | (generic ? 4 : 0);
     // unit-SOC forward-pass variants (problem_dev.h unit_soc_desc): at least one control-block constraint, and all of them unit
     bool any_ctrl = false, all_unit = true;
@@ -277,9 +280,17 @@ int launch_set_active(to_handle* h, int v, int clear_bpfail = 1) {
   HIPCHECK(hipGetLastError());
   return TO_OK;
 }
-int launch_rollout(to_handle* h) { return h->ops->rollout(h); }
+// (DevProblem::pm set — one plant per trajectory — : the flagged instances of the kernels that read model parameters, here and below)
+int launch_rollout(to_handle* h) { return h->a.P.pm ? h->ops->rollout_pm(h) : h->ops->rollout(h); }
+int launch_defect(to_handle* h, double* out) { return h->a.P.pm ? h->ops->defect_pm(h, out) : h->ops->defect(h, out); }
+int launch_pn(to_handle* h, int slot0, int count, hipStream_t stream, const to_solver_opts* opts) {
+  return h->a.P.pm ? h->ops->pn_launch_pm(h, slot0, count, stream, opts) : h->ops->pn_launch(h, slot0, count, stream, opts);
+}
 int launch_cost(to_handle* h, int with_al, double* out, double* Jk) { return h->ops->cost(h, with_al, out, Jk); }
-int launch_expand(to_handle* h) { return h->ops->expand(h); }
+int launch_expand(to_handle* h) {
+  if (h->a.P.pm) return h->a.bwd_lane ? h->ops->expand_lane_pm(h) : h->ops->expand_pm(h);
+  return h->ops->expand(h);
+}
 int launch_backward(to_handle* h) { return h->ops->backward(h); }
 int launch_accept(to_handle* h) {  // materialise accepted candidate slots on slot 0, then forget them
   if (!h->a.store_x) return h->ops->accept_roll(h);  // their states were not stored: rolled out again from the stored controls (clears acc itself)
@@ -292,6 +303,15 @@ int launch_accept(to_handle* h) {  // materialise accepted candidate slots on sl
 // per-trajectory state machine (k_forward.h), in the kernel variant path_plan.h forward_mode picks
 int launch_forward(to_handle* h, bool accept = true, bool two_wave = false) {
   const DevProblem& P = h->a.P;  // (the general variants also with per-trajectory linear cost terms / constraint parameters: only they read them)
+  if (P.pm) {  // one plant per trajectory: the general variants that load it per trajectory, as one-wave workgroups (stage cost read per knot)
+    uint32_t mask = 0;
+    for (int i = 0; i < 32; ++i) if (h->ops->forward_pm[i]) mask |= 1u << i;
+    const int pmode = forward_mode(false, P.n_cons > 0, P.integrator == INTEG_RK4, true, false, mask);
+    if (pmode < 0) return fail(TO_ERR_UNSUPPORTED, "forward-pass variant with per-trajectory model parameters not compiled for this model");
+    TRY(h->ops->forward_pm[pmode](h));
+    if (accept) TRY(launch_accept(h));
+    return TO_OK;
+  }
   const int mode = forward_mode(P.simple_stage, P.n_cons > 0, P.integrator == INTEG_RK4, (P.expand_variant & 5) || P.gl || P.cp, P.unit_soc, h->traits.forward);
   if (mode < 0) return fail(TO_ERR_UNSUPPORTED, "forward-pass variant not compiled for this model");
   if ((two_wave || h->plan.fwd2 == 1) && h->ops->forward2[mode]) TRY(h->ops->forward2[mode](h));
@@ -347,7 +367,7 @@ int fill_stats(to_handle* h, to_solve_stats* st, bool with_defect) {
     else std::memset(st->c_max, 0, sizeof(double) * B);
     if (with_defect) {
       std::vector<double> df(B);
-      TRY(h->ops->defect(h, h->d_tmp));
+      TRY(launch_defect(h, h->d_tmp));
       TRY(download_scalar(h, df.data(), h->d_tmp));
       for (int b = 0; b < B; ++b) if (df[b] > st->c_max[b] || df[b] != df[b]) st->c_max[b] = df[b];
     }
@@ -511,7 +531,7 @@ int pn_run(to_handle* h, const std::vector<int>& list, const to_solver_opts& opt
   for (int base = 0; base < count; base += h->pn_cap) {
     const int cnt = std::min(h->pn_cap, count - base);
     HIPCHECK(hipMemcpyAsync(h->pn_list, h->pn_list_host + base, sizeof(int) * cnt, hipMemcpyHostToDevice, h->stream));
-    TRY(h->ops->pn_launch(h, 0, cnt, h->stream, &opts));
+    TRY(launch_pn(h, 0, cnt, h->stream, &opts));
   }
   HIPCHECK(hipEventRecord(e1, h->stream));
   HIPCHECK(hipEventSynchronize(e1));
@@ -586,7 +606,7 @@ int early_polish_launch(to_handle* h) {
   HIPCHECK(hipStreamWaitEvent(h->pn_stream, h->pn_ev[0], 0));
   if (s0 == 0) HIPCHECK(hipEventRecord(h->pn_ev[2], h->pn_stream));
   HIPCHECK(hipMemcpyAsync(h->pn_list + s0, h->pn_list_host + s0, sizeof(int) * cnt, hipMemcpyHostToDevice, h->pn_stream));
-  TRY(h->ops->pn_launch(h, s0, cnt, h->pn_stream, &h->pn_opts));
+  TRY(launch_pn(h, s0, cnt, h->pn_stream, &h->pn_opts));
   HIPCHECK(hipEventRecord(h->pn_ev[1], h->pn_stream));
   h->pn_early_slots += cnt;
   return TO_OK;
@@ -667,7 +687,7 @@ int solve_impl(to_handle* h, to_solve_stats* st, int al_mode) {
   a.al_mode = al_mode;
   a.control = 1;
   h->rp_arr.clear();  // the table of carried arrays is rebuilt per solve (per-trajectory cost terms may have appeared)
-  a.compact = h->plan.compact;
+  a.compact = solve_compact(h->plan, P.pm != nullptr);
   const int max_steps = (al_mode ? P.opts.iterations_total : P.opts.iterations) + 1;
   if (h->counter_len < max_steps) {
     int* c = nullptr;
@@ -713,7 +733,7 @@ int solve_impl(to_handle* h, to_solve_stats* st, int al_mode) {
       if (h->profile) HIPCHECK(hipEventRecord(h->ev[4 * step + 0], h->stream));
       // what this step launches (path_plan.h), from the last active count the host has seen (results do not depend on it)
       const PathPlan& pl = h->plan;
-      const StepPlan sp = plan_step(pl, h->traits, a.h_diag, P.expand_variant, a.compact, last_active, P.B);
+      const StepPlan sp = plan_step(pl, h->traits, a.h_diag, P.expand_variant, a.compact, last_active, P.B, P.pm != nullptr);
       if (sp.kind == STEP_SPLIT) TRY(launch_expand(h));
       if (h->profile) HIPCHECK(hipEventRecord(h->ev[4 * step + 1], h->stream));
       switch (sp.kind) {
@@ -764,7 +784,7 @@ int solve_impl(to_handle* h, to_solve_stats* st, int al_mode) {
   int early_thr = (al_mode && h->pn_early > 0) ? P.B / early_div : -1, early_left = h->pn_early;
   bool snapshot_pending = false;
   // repacked working set (above): iLQR solves of the small models on the fused lane path with compaction
-  bool repack = !al_mode && a.compact && working_set_repack(h->plan, h->traits);
+  bool repack = !al_mode && a.compact && working_set_repack(h->plan, h->traits, P.pm != nullptr);
   if (max_steps > 0) TRY(enqueue_chunk());
   while (!done && waited < nchunks) {
     if (repack && last_active >= 1 && (double)last_active <= h->plan.rp_at * (double)a.P.B && a.P.B >= h->plan.rp_min) {
@@ -1111,7 +1131,7 @@ void* to_stream(to_handle* h) { return h ? (void*)h->stream : nullptr; }
 
 int to_solver_path(const to_handle* h, int32_t* info) {
   CHECK_H(h); CHECK_P(info);
-  path_report(h->plan, h->traits, h->a.h_diag, h->a.P.expand_variant, h->a.P.B, info);
+  path_report(h->plan, h->traits, h->a.h_diag, h->a.P.expand_variant, h->a.P.B, info, h->a.P.pm != nullptr);
   return TO_OK;
 }
 int to_knot_dims(const to_handle* h, int32_t* nx, int32_t* nu) {
@@ -1326,6 +1346,70 @@ int to_clear_constraint_params_batch(to_handle* h) {
   return upload_tables(h);
 }
 
+// One set of model parameters per TRAJECTORY (DevProblem::pm): params[16, B], 16 fastest.  Every column is checked like
+// to_policy_opts::plant_params (finite; the entries that select dimensions or the attitude representation equal the problem's).  The solves
+// then run the flagged instances of the general kernel variants (path_plan.h `plants`); X, U, duals and gains are left as they are.
+static const char* model_key_name(int key) {
+  static const char* names[N_MODEL_KEYS] = {"double integrator (D = 1)", "double integrator (D = 2)", "double integrator (D = 3)", "Cartpole", "Quadrotor",
+                                            "Quadrotor{MRP}", "Quadrotor{RodriguesParam}", "hybrid double integrator", "model vector",
+                                            "InfeasibleModel (double integrator, D = 1)", "InfeasibleModel (double integrator, D = 2)", "InfeasibleModel (Cartpole)"};
+  return (key >= 0 && key < N_MODEL_KEYS) ? names[key] : "unknown model";
+}
+static int model_params_supported(const to_handle* h, const char* who) {
+  const ModelOps& o = *h->ops;
+  if (h->model_key > 4 || !o.rollout_pm || !o.discrete_jacobian_pm || !o.expand_pm || !o.defect_pm || !o.pn_launch_pm || !o.forward_pm[8] ||
+      (h->a.bwd_lane && !o.expand_lane_pm) || !o.policy_rollout_mc || !(o.policy_noise_mask & 4))
+    return fail(TO_ERR_UNSUPPORTED, std::string(who) + ": per-trajectory model parameters are not available for the " + model_key_name(h->model_key) +
+                                        " (double integrator, Cartpole and quaternion Quadrotor only)");
+  return TO_OK;
+}
+int to_set_model_params_batch(to_handle* h, const double* params) {
+  CHECK_H(h); CHECK_IDLE(h); CHECK_P(params); TRY(use_device(h));
+  TRY(model_params_supported(h, "to_set_model_params_batch"));
+  DevProblem& P = h->a.P;
+  const int B = P.B, key = h->model_key;
+  for (int b = 0; b < B; ++b) {
+    const double* pp = params + (size_t)16 * b;
+    for (int i = 0; i < 16; ++i)
+      if (!std::isfinite(pp[i]))
+        return fail(TO_ERR_ARGUMENT, "to_set_model_params_batch: entry " + std::to_string(i) + " of trajectory " + std::to_string(b) + " is not finite");
+    const bool ok = key <= 2 ? pp[1] == P.mp[1] : key == 4 ? pp[10] == P.mp[10] : true;  // double integrator: D; Quadrotor: rotation
+    if (!ok) return fail(TO_ERR_ARGUMENT, "to_set_model_params_batch: the parameters of trajectory " + std::to_string(b) +
+                                              " change the model's dimensions or attitude representation");
+  }
+  const size_t tiles = (size_t)P.Bp / 64 + 1;  // (+ one spare tile, like the nominal states)
+  if (!h->d_pm) TRY(dev_alloc(h, &h->d_pm, tiles * 16 * 64));
+  // tiled on the host; lanes behind the batch carry the shared parameters (idle lanes compute along on valid data)
+  std::vector<double> tiled(tiles * 16 * 64);
+  for (size_t t = 0; t < tiles; ++t)
+    for (int i = 0; i < 16; ++i)
+      for (int l = 0; l < 64; ++l) {
+        const size_t b = t * 64 + l;
+        tiled[(t * 16 + i) * 64 + l] = b < (size_t)B ? params[16 * b + i] : P.mp[i];
+      }
+  HIPCHECK(hipMemcpyAsync(h->d_pm, tiled.data(), tiled.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  HIPCHECK(hipStreamSynchronize(h->stream));
+  h->pm_host.assign(params, params + (size_t)16 * B);
+  P.pm = h->d_pm;
+  TRY(upload_tables(h));  // (expand_variant bit 2, and with it the compact cost block, follow pm)
+  return check_guards(h, "to_set_model_params_batch");
+}
+int to_get_model_params_batch(to_handle* h, double* params) {
+  CHECK_H(h); CHECK_IDLE(h); CHECK_P(params);
+  TRY(model_params_supported(h, "to_get_model_params_batch"));
+  const DevProblem& P = h->a.P;
+  if (P.pm) std::memcpy(params, h->pm_host.data(), sizeof(double) * 16 * P.B);
+  else for (int b = 0; b < P.B; ++b) std::memcpy(params + (size_t)16 * b, P.mp, sizeof(double) * 16);
+  return TO_OK;
+}
+int to_clear_model_params_batch(to_handle* h) {
+  CHECK_H(h); CHECK_IDLE(h); TRY(use_device(h));
+  TRY(model_params_supported(h, "to_clear_model_params_batch"));
+  h->a.P.pm = nullptr;
+  h->pm_host.clear();
+  return upload_tables(h);
+}
+
 int to_rollout(to_handle* h) { CHECK_H(h); CHECK_IDLE(h); TRY(use_device(h)); TRY(launch_rollout(h)); HIPCHECK(hipStreamSynchronize(h->stream)); return check_guards(h, "to_rollout"); }
 int to_cost(to_handle* h, double* J) {
   CHECK_H(h); CHECK_IDLE(h); CHECK_P(J); TRY(use_device(h));
@@ -1363,7 +1447,7 @@ int to_expand(to_handle* h) {
 static int phase_backward(to_handle* h) {
   TRY(launch_set_active(h, 1));
   const DevProblem& P = h->a.P;
-  if (h->plan.scan == 2 && scan_now(h->plan, h->a.h_diag, P.expand_variant)) {
+  if (h->plan.scan == 2 && scan_now(h->plan, h->a.h_diag, P.expand_variant, P.pm != nullptr)) {
     // TRAJOPT_SCAN=2 (tests): the phase API runs the solve loop's scan kernel so that its gains can be read back and compared
     // (it expands on its own: to_expand's arrays are not used)
     TRY(h->ops->expand_backward_scan(h));
@@ -1432,9 +1516,20 @@ static int policy_rollout_impl(to_handle* h, int32_t S, const double* x0s, const
       nz |= 4;
     }
     pa.seed = noise->seed; pa.traj_offset = noise->traj_offset; pa.sample_offset = noise->sample_offset;
-    if (nz && (!h->ops->policy_rollout_mc || (nz & ~h->ops->policy_noise_mask)))
-      return fail(TO_ERR_UNSUPPORTED, "to_policy_rollout_mc: not compiled for this model");
   }
+  // A handle planned on one plant per trajectory (to_set_model_params_batch) simulates each trajectory on ITS plant when the caller names none:
+  // the host fills the per-sample plants array and the one-plant-per-sample instance runs (an explicit plant, shared or per sample, overrides)
+  const double* plants_src = (noise && noise->plant_params) ? noise->plant_params : nullptr;
+  std::vector<double> own_plants;
+  if (P.pm && !o.plant_params && !plants_src) {
+    own_plants.resize((size_t)16 * S * B);
+    for (int b = 0; b < B; ++b)
+      for (int s = 0; s < S; ++s) std::memcpy(&own_plants[((size_t)b * S + s) * 16], &h->pm_host[(size_t)16 * b], sizeof(double) * 16);
+    plants_src = own_plants.data();
+    nz |= 4;
+  }
+  if (nz && (!h->ops->policy_rollout_mc || (nz & ~h->ops->policy_noise_mask)))
+    return fail(TO_ERR_UNSUPPORTED, "to_policy_rollout_mc: not compiled for this model");
   auto launch = [&](const PolicyArgs& a, int w) { return nz ? h->ops->policy_rollout_mc(h, a, w, nz) : h->ops->policy_rollout(h, a, w); };
   // lane map: packed while a wave holds at least two trajectories, one trajectory per wave beyond (TRAJOPT_POLICY_MAP=packed forces the
   // per-lane body up to S = 64: the A/B of tools/policy_rollout_probe.py)
@@ -1479,7 +1574,7 @@ static int policy_rollout_impl(to_handle* h, int32_t S, const double* x0s, const
       h->pol_plants_cap = SB;
     }
     pa.plants = h->pol_plants;
-    HIPCHECK(hipMemcpyAsync(h->pol_plants, noise->plant_params, SB * 16 * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHECK(hipMemcpyAsync(h->pol_plants, plants_src, SB * 16 * sizeof(double), hipMemcpyHostToDevice, h->stream));
   }
   if (!out->X && !out->U) {
     TRY(launch(pa, waves));
@@ -1618,7 +1713,7 @@ int to_solve_wait_below(to_handle* h, int32_t active_max) {
 int to_dynamics_defect(to_handle* h, double* defect) {
   CHECK_H(h); CHECK_IDLE(h); CHECK_P(defect);
   TRY(use_device(h));
-  TRY(h->ops->defect(h, h->d_tmp));
+  TRY(launch_defect(h, h->d_tmp));
   return download_scalar(h, defect, h->d_tmp);
 }
 
@@ -1761,7 +1856,7 @@ int to_discrete_jacobian(to_handle* h, double* F) {
   const DevProblem& P = h->a.P;
   const size_t cnt = (size_t)P.n * (P.n + P.m) * (P.N - 1) * P.B;
   TRY(ensure_stage(h, cnt * sizeof(double)));
-  TRY(h->ops->discrete_jacobian(h, h->stage));
+  TRY(h->a.P.pm ? h->ops->discrete_jacobian_pm(h, h->stage) : h->ops->discrete_jacobian(h, h->stage));
   HIPCHECK(hipMemcpyAsync(F, h->stage, cnt * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIPCHECK(hipStreamSynchronize(h->stream));
   return TO_OK;
