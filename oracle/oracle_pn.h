@@ -256,14 +256,16 @@ void pn_reg_solve(PnSys& s, const std::vector<double>& b, std::vector<double>& x
   }
 }
 
-struct PnResult { bool ran = false, failed = false; double viol = 0.0; };
+/* how a projection ended (the polish trace, oracle_pn_trace: bookkeeping for the tests, no part of the arithmetic) */
+enum { PN_EXIT_CONVERGED = 0, PN_EXIT_RATE = 1, PN_EXIT_LINESEARCH = 2, PN_EXIT_REFINEMENTS = 3, PN_EXIT_FACTOR = 4 };
+struct PnResult { bool ran = false, failed = false; double viol = 0.0; int refinements = 0, trials = 0, reason = PN_EXIT_REFINEMENTS; };
 
 /* Altro _projection_solve! on the working copy (X, U); the active set is the one pn_residual(refresh) left in s */
 PnResult pn_projection(const Problem& P, const Traj& t, std::vector<double>& X, std::vector<double>& U, PnSys& s, double viol0) {
   const int N = P.N, n = P.n, m = P.m, ne = P.ne, nc = ne + m;
   PnResult res; res.ran = true; res.viol = viol0;
   pn_linearise(P, t, X.data(), U.data(), s);
-  if (!pn_factor(s, P.opts.rho_chol)) { res.failed = true; return res; }
+  if (!pn_factor(s, P.opts.rho_chol)) { res.failed = true; res.reason = PN_EXIT_FACTOR; return res; }
   std::vector<double> dl, dZ(s.nv), Xb(X.size()), Ub(U.size()), dn;
   double viol_prev = viol0;
   for (int count = 0; count < PN_REFINEMENTS; ++count) {
@@ -272,8 +274,10 @@ PnResult pn_projection(const Problem& P, const Traj& t, std::vector<double>& X, 
     for (int i = 0; i < s.M; ++i) { const PnRow& r = s.rows[i]; for (int c = 0; c < r.len; ++c) dZ[r.v0 + c] += r.coef[c] * dl[i]; }
     for (int c = 0; c < s.nv; ++c) dZ[c] = -(s.W[c] * dZ[c]);
     double alpha = 1.0, v = 0.0; bool accepted = false;
+    res.refinements = count + 1; res.trials = 0;
     for (int ls = 0; ls < PN_LS_TRIALS; ++ls) {
       double step[MAXN];
+      res.trials = ls + 1;
       for (int k = 0; k < N; ++k) {
         for (int i = 0; i < ne; ++i) step[i] = alpha * dZ[(size_t)k * nc + i];
         state_add(P.M, &X[(size_t)k * n], step, &Xb[(size_t)k * n]);
@@ -291,13 +295,13 @@ PnResult pn_projection(const Problem& P, const Traj& t, std::vector<double>& X, 
       alpha *= 0.5;
     }
     if (std::getenv("ORACLE_PN_VERBOSE")) std::fprintf(stderr, "  pn refine %d: viol %.3e -> %.3e alpha %.3g accepted %d rows %d\n", count, viol_prev, v, alpha, (int)accepted, s.M);
-    if (!accepted) break;
+    if (!accepted) { res.reason = PN_EXIT_LINESEARCH; break; }
     X = Xb; U = Ub; s.d = dn;
     const double before = viol_prev;
     viol_prev = v;
-    if (v < P.opts.constraint_tolerance) break;
-    if (before < 1.0) { if (std::log10(v) / std::log10(before) < P.opts.r_threshold) break; }
-    else if (!(v < 0.5 * before)) break;
+    if (v < P.opts.constraint_tolerance) { res.reason = PN_EXIT_CONVERGED; break; }
+    if (before < 1.0) { if (std::log10(v) / std::log10(before) < P.opts.r_threshold) { res.reason = PN_EXIT_RATE; break; } }
+    else if (!(v < 0.5 * before)) { res.reason = PN_EXIT_RATE; break; }
   }
   res.viol = viol_prev;
   return res;
@@ -308,6 +312,7 @@ void pn_solve(const Problem& P, Traj& t) {
   PnSys s;
   std::vector<double> X = t.X, U = t.U;
   t.iterations_pn = 0;
+  t.pn_trace.clear();
   bool failed = false;
   for (int k = 0; k < P.N && !failed; ++k) if (pn_candidate_count(P, k) > PN_MAX_ROWS) failed = true;
   for (int step = 0; !failed; ++step) {
@@ -316,6 +321,7 @@ void pn_solve(const Problem& P, Traj& t) {
     if (std::getenv("ORACLE_PN_VERBOSE")) std::fprintf(stderr, "pn step %d: viol %.3e rows %d\n", step, viol, s.M);
     const PnResult r = pn_projection(P, t, X, U, s, viol);
     t.iterations_pn++;
+    t.pn_trace.push_back(r.refinements); t.pn_trace.push_back(r.trials); t.pn_trace.push_back(r.reason);
     if (r.failed) failed = true;
   }
   t.X = X; t.U = U;

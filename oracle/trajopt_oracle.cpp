@@ -82,6 +82,7 @@ struct Traj {
   /* phase API: the last oracle_backward ran into bp_reg_max (gains of an abandoned attempt).  Cleared by the next oracle_expand and
    * at the start of every solve, where the device clears its bpfail (k_set_active from to_expand / to_backward, the solves' initialisation kernel). */
   bool bp_failed = false;
+  std::vector<int> pn_trace;                  /* per projection of the last polish: refinements run, trials of the last line search, exit reason (oracle_pn.h) */
 };
 
 }  // namespace
@@ -1184,6 +1185,14 @@ int oracle_altro_solve(oracle_handle* h, to_solve_stats* st) {
   double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   fill_stats(h, st, ms, true);
   return TO_OK;
+}
+/* The polish trace of trajectory b: three integers per projection (refinements, trials of the last line search, PN_EXIT_* reason).
+ * Returns the number of integers the trace holds; at most cap are written. */
+int oracle_pn_trace(oracle_handle* h, int32_t b, int32_t* out, int32_t cap) {
+  if (!h || b < 0 || b >= h->P.B) return -1;
+  const std::vector<int>& tr = h->T[b].pn_trace;
+  for (int i = 0; i < (int)tr.size() && i < cap; ++i) out[i] = tr[i];
+  return (int)tr.size();
 }
 int oracle_dynamics_defect(oracle_handle* h, double* out) {
   CHECK_H(h); CHECK_P(out);

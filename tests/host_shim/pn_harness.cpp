@@ -52,6 +52,11 @@ static int run(const DevProblem& P, KArgs& a, std::vector<DevCon>& cons) {
   return TO_OK;
 }
 
+// The limits that choose the kernel's code paths by block stride (tests/pn_cases.py places its ladder of strides around them)
+extern "C" void pn_host_limits(int* nbr, int* pf, int* nb_limit, int* max_rows) {
+  *nbr = PN_NBR; *pf = PN_PF; *nb_limit = PN_NB_LIMIT; *max_rows = PN_MAX_ROWS;
+}
+
 extern "C" const char* pn_host_last_error() { return g_err.c_str(); }
 
 extern "C" int pn_host_solve(const to_problem_desc* desc, const to_solver_opts* opts, const double* x0, double* X, double* U,

@@ -63,5 +63,18 @@ def load_oracle():
     return _lib
 
 
+PN_EXITS = ("converged", "rate", "linesearch", "refinements", "factor")
+
+
+def pn_trace(prob, b):
+    """The oracle's trace of trajectory b's last polish: one (refinements run, trials of the last line search, exit reason) per projection."""
+    f = prob._lib.dll.oracle_pn_trace
+    f.argtypes, f.restype = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_int32], C.c_int
+    buf = (C.c_int32 * 96)()
+    n = f(prob._h, int(b), buf, 96)
+    assert 0 <= n <= 96 and n % 3 == 0, n
+    return [(buf[i], buf[i + 1], PN_EXITS[buf[i + 2]]) for i in range(0, n, 3)]
+
+
 def set_threads(prob, threads):
     prob._lib.call("set_threads", prob._h, int(threads))

@@ -41,6 +41,9 @@ PN_CASES = {
     "quickstart_circle_soc_bound_goal": (lambda lib: _quickstart(lib, 5), 1e-3),
     "quadrotor_goal_soc": (lambda lib: configs.quadrotor_problem(batch=24, N=61, tf=3.0, constrained=True, goal_inds=configs.C5_GOAL_INDS, lib=lib), 0.0),
     "quadrotor_goal_soc_perturbed": (lambda lib: configs.quadrotor_problem(batch=9, N=41, tf=3.0, constrained=True, goal_inds=configs.C5_GOAL_INDS, lib=lib), 3e-4),
+    # C5' small: Goal(9) + QuatVecEq(3) at the terminal knot, stride NB = 24 (the generic Cholesky and the unstaged solve sweeps)
+    "quadrotor_quatvec_goal_NB24": (lambda lib: configs.quadrotor_problem(batch=5, N=41, tf=3.0, constrained=True, goal_inds=configs.C5_GOAL_INDS,
+                                                                          quatvec_goal=True, lib=lib), 3e-4),
 }
 
 

@@ -75,6 +75,9 @@ CASES = {
     "quickstart_circle_soc_bound_goal": (lambda o: _quickstart(o, 2), 1e-3),
     "quadrotor_goal_soc": (lambda o: configs.quadrotor_problem(batch=3, N=61, tf=3.0, constrained=True, goal_inds=configs.C5_GOAL_INDS, lib=o), 0.0),
     "quadrotor_goal_soc_perturbed": (lambda o: configs.quadrotor_problem(batch=2, N=41, tf=3.0, constrained=True, goal_inds=configs.C5_GOAL_INDS, lib=o), 3e-4),
+    # C5' small: Goal(9) + QuatVecEq(3) at the terminal knot, stride NB = 24 (the generic Cholesky and the unstaged solve sweeps)
+    "quadrotor_quatvec_goal_NB24": (lambda o: configs.quadrotor_problem(batch=5, N=41, tf=3.0, constrained=True, goal_inds=configs.C5_GOAL_INDS,
+                                                                        quatvec_goal=True, lib=o), 3e-4),
 }
 
 
@@ -114,3 +117,33 @@ def test_index_helpers_of_the_factorisation(pn_host):
     pn_host.pn_host_index_selftest.restype = C.c_int
     assert pn_host.pn_host_index_selftest() == 0
 
+
+
+# ---- the ladder of block strides and the exits of tests/pn_cases.py (vetted on the oracle by tests/test_pn_cases_oracle.py): a logic error
+# in the generic-path code fails here; what only the GPU can get wrong (lane mapping, staging, v_readlane, barriers) fails in
+# tests/test_gpu_pn_blocks.py alone
+import pn_cases as P
+
+
+@pytest.mark.parametrize("name", list(P.CASES))
+def test_pn_cases_kernel_source_on_host_matches_oracle(name, oracle):
+    case = P.CASES[name]
+    prob = case.build(oracle)
+    Xh, Uh, sth, iph, cmh = host_polish(P.host_library(), prob)
+    ref = case.polish(oracle)
+    P.assert_case_matches(case, dict(status=sth, iterations_pn=iph, c_max=cmh, X=Xh, U=Uh), ref, "host")
+    if name in P.LADDER:
+        assert np.all(sth == T.capi.SOLVE_SUCCEEDED) and cmh.max() <= 1e-6 and np.all(iph >= 1)
+
+
+def test_host_build_refuses_a_stride_beyond_the_limit(oracle):
+    L = P.limits()
+    case = P.quadrotor_rung(L["nb_limit"] + 1, 4, waypoint=True)
+    prob = case.build(oracle)
+    X, U = np.ascontiguousarray(T.states(prob)), np.ascontiguousarray(T.controls(prob))
+    x0 = np.zeros((prob.B, prob.n)); prob._call("get_initial_state", prob._pd(x0))
+    st, ip, cm = np.zeros(prob.B, np.int32), np.zeros(prob.B, np.int32), np.zeros(prob.B)
+    pd = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+    pi = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+    lib = P.host_library()
+    assert lib.pn_host_solve(C.byref(prob._desc), None, pd(x0), pd(X), pd(U), pi(st), pi(ip), pd(cm)) == T.capi.TO_ERR_UNSUPPORTED

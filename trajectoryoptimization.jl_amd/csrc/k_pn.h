@@ -34,6 +34,7 @@ namespace to {
 
 constexpr int PN_MAX_ROWS = 64;      // candidate constraint rows of one knot (one bit each in the active mask)
 constexpr int PN_NB_LIMIT = 44;      // largest block: ne + active rows of a knot (LDS: 2 NB^2 + ... doubles)
+constexpr int PN_NBR = 21;           // largest block stride whose Cholesky factor and inverse are formed in registers (pn_chol_inv_regs)
 constexpr int PN_REFINEMENTS = 10;   // Altro _projection_solve!: max_refinements
 constexpr int PN_LS_TRIALS = 10;     // Altro _projection_linesearch!
 constexpr int PN_REG_SOLVE_ITERS = 25;
@@ -423,7 +424,6 @@ PN_FN int pn_tri_row(int e) {
 // REGISTERS: lane i owns row i of L, then column i of L^-1; what the other lanes need of a row travels by v_readlane (the row
 // index is the loop counter: uniform).  The generic path below does the same arithmetic in the same order (column after column,
 // the terms of every entry in ascending order) through ~45 LDS phases per block — a third of a projection's time on C5.
-constexpr int PN_NBR = 21;
 PN_FN double pn_bcast(double v, int src) {
   return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), src), __builtin_amdgcn_readlane(__double2loint(v), src));
 }
