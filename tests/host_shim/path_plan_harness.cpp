@@ -28,28 +28,30 @@ static PathKnobs knobs(const char* env) {  // "NAME=value NAME=value" (names wit
 
 // ---- the trait sets of models.h, with the optional launchers the ops_*.hip translation units fill -----------------------------
 struct Model { const char* name; int ne, m; PathTraits t; };
-static PathTraits traits(bool wt, bool mfma, bool coop, bool lane, int ls, bool eb, bool ebc, bool ebs, bool ar, bool elk, bool ec, uint32_t f, uint32_t f2) {
+static PathTraits traits(bool wt, bool mfma, bool coop, bool lane, int ls, bool eb, bool ebc, bool ebs, bool ar, bool elk, bool ec, uint32_t f, uint32_t f2, uint32_t fp) {
   PathTraits t;
   t.write_through = wt; t.mfma_backward = mfma; t.coop_backward = coop; t.lane_backward = lane; t.ls_first_round = ls;
   t.expand_backward = eb; t.expand_backward_coop = ebc; t.expand_backward_scan = ebs; t.accept_roll = ar; t.expand_lane_k = elk; t.expand_const = ec;
-  t.forward = f; t.forward2 = f2;
+  t.forward = f; t.forward2 = f2; t.forward_plants = fp;
   return t;
 }
 constexpr uint32_t F_SMALL = 0xFFFFu;  // variants 0..15 (models that pin RK4)
 constexpr uint32_t F_QUAD = 0x0F0Fu | (3u << 18) | (3u << 26);  // 0-3, 8-11, 18-19, 26-27
 constexpr uint32_t F_ATT = (1u << 8) | (1u << 10);
+// one plant per trajectory: the general variants (bit 3) of the models to_set_model_params_batch accepts; 12 / 14 where RK4 is pinned
+constexpr uint32_t FP_SMALL = (1u << 8) | (1u << 10) | (1u << 12) | (1u << 14), FP_QUAD = (1u << 8) | (1u << 10);
 static const Model MODELS[] = {
-    {"double integrator 1", 2, 1, traits(true, false, true, true, 4, true, true, true, true, true, false, F_SMALL, F_SMALL)},
-    {"double integrator 2", 4, 2, traits(true, false, true, true, 4, true, true, true, true, true, false, F_SMALL, F_SMALL)},
-    {"double integrator 3", 6, 3, traits(true, false, true, false, 4, false, false, false, true, false, false, F_SMALL, F_SMALL)},
-    {"cartpole", 4, 1, traits(true, true, true, true, 4, true, true, true, true, true, false, F_SMALL, F_SMALL)},
-    {"quadrotor", 12, 4, traits(false, true, false, false, 16, false, false, false, true, false, true, F_QUAD, F_QUAD)},
-    {"quadrotor mrp/rp", 12, 4, traits(false, true, false, false, 16, false, false, false, true, false, true, F_ATT, F_ATT)},
-    {"hybrid", 4, 2, traits(true, false, true, true, 4, true, true, true, true, true, false, F_SMALL, F_SMALL)},
-    {"model vector", 6, 3, traits(true, false, true, false, 4, false, false, false, true, false, false, F_SMALL, F_SMALL)},
-    {"infeasible di 1", 2, 3, traits(true, false, true, false, 4, false, false, false, true, false, false, F_SMALL, F_SMALL)},
-    {"infeasible di 2", 4, 6, traits(true, false, true, false, 4, false, false, false, true, false, false, F_SMALL, F_SMALL)},
-    {"infeasible cartpole", 4, 5, traits(true, false, true, false, 4, false, false, false, true, false, false, F_SMALL, F_SMALL)},
+    {"double integrator 1", 2, 1, traits(true, false, true, true, 4, true, true, true, true, true, false, F_SMALL, F_SMALL, FP_SMALL)},
+    {"double integrator 2", 4, 2, traits(true, false, true, true, 4, true, true, true, true, true, false, F_SMALL, F_SMALL, FP_SMALL)},
+    {"double integrator 3", 6, 3, traits(true, false, true, false, 4, false, false, false, true, false, false, F_SMALL, F_SMALL, FP_SMALL)},
+    {"cartpole", 4, 1, traits(true, true, true, true, 4, true, true, true, true, true, false, F_SMALL, F_SMALL, FP_SMALL)},
+    {"quadrotor", 12, 4, traits(false, true, false, false, 16, false, false, false, true, false, true, F_QUAD, F_QUAD, FP_QUAD)},
+    {"quadrotor mrp/rp", 12, 4, traits(false, true, false, false, 16, false, false, false, true, false, true, F_ATT, F_ATT, 0u)},
+    {"hybrid", 4, 2, traits(true, false, true, true, 4, true, true, true, true, true, false, F_SMALL, F_SMALL, 0u)},
+    {"model vector", 6, 3, traits(true, false, true, false, 4, false, false, false, true, false, false, F_SMALL, F_SMALL, 0u)},
+    {"infeasible di 1", 2, 3, traits(true, false, true, false, 4, false, false, false, true, false, false, F_SMALL, F_SMALL, 0u)},
+    {"infeasible di 2", 4, 6, traits(true, false, true, false, 4, false, false, false, true, false, false, F_SMALL, F_SMALL, 0u)},
+    {"infeasible cartpole", 4, 5, traits(true, false, true, false, 4, false, false, false, true, false, false, F_SMALL, F_SMALL, 0u)},
 };
 enum { DI1, DI2, DI3, CART, QUAD, QATT, HYB, VEC, INF1, INF2, INFC, N_MODELS };
 
@@ -355,6 +357,19 @@ static void forward_modes() {
         CHECK(has(mode), "forward_mode(req %d, mask %08x) = %d: not compiled", req, mask, mode);
         CHECK(mode == (has(cand[0]) ? cand[0] : cand[1]), "forward_mode(req %d, mask %08x) = %d", req, mask, mode);
         CHECK(((mode & 2) != 0) == cons, "forward_mode(req %d, mask %08x) = %d: constraint bit changed", req, mask, mode);
+      } else ++none;
+    }
+  // the request launch_forward makes with one plant per trajectory (general variant, stage cost read per knot) over every model's mask of
+  // flagged variants: a compiled general variant with the constraint bit as asked, -1 exactly for the models without flagged instances
+  for (const Model& M : MODELS)
+    for (int req = 0; req < 4; ++req) {
+      const bool cons = req & 1, rk4 = req & 2;
+      const uint32_t mask = M.t.forward_plants;
+      const int mode = forward_mode(false, cons, rk4, true, false, mask);
+      CHECK((mode >= 0) == (mask != 0), "%s: plants forward_mode(cons %d, rk4 %d, mask %08x) = %d", M.name, (int)cons, (int)rk4, mask, mode);
+      if (mode >= 0) {
+        ++found;
+        CHECK(((mask >> mode) & 1u) && (mode & 8) && !(mode & 1) && ((mode & 2) != 0) == cons, "%s: plants forward_mode(cons %d, rk4 %d, mask %08x) = %d", M.name, (int)cons, (int)rk4, mask, mode);
       } else ++none;
     }
   printf("forward_found %lld forward_none %lld\n", found, none);

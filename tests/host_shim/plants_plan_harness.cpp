@@ -61,19 +61,19 @@ static PathKnobs knobs(const char* env) {  // "NAME=value NAME=value" (names wit
 }
 
 struct Model { const char* name; int ne, m; PathTraits t; };
-static PathTraits traits(bool wt, bool mfma, bool coop, bool lane, int ls, bool eb, bool ebc, bool ebs, bool ar, bool elk, bool ec, uint32_t f, uint32_t f2) {
+static PathTraits traits(bool wt, bool mfma, bool coop, bool lane, int ls, bool eb, bool ebc, bool ebs, bool ar, bool elk, bool ec, uint32_t f, uint32_t f2, uint32_t fp) {
   PathTraits t;
   t.write_through = wt; t.mfma_backward = mfma; t.coop_backward = coop; t.lane_backward = lane; t.ls_first_round = ls;
   t.expand_backward = eb; t.expand_backward_coop = ebc; t.expand_backward_scan = ebs; t.accept_roll = ar; t.expand_lane_k = elk; t.expand_const = ec;
-  t.forward = f; t.forward2 = f2;
+  t.forward = f; t.forward2 = f2; t.forward_plants = fp;
   return t;
 }
 // the models to_set_model_params_batch accepts, with the traits their launch tables report (models.h, ops_*.hip)
 static const Model MODELS[] = {
-    {"double integrator 2", 4, 2, traits(true, false, true, true, 4, true, true, true, true, true, false, 0xFFFFu, 0xFFFFu)},
-    {"double integrator 3", 6, 3, traits(true, false, true, false, 4, false, false, false, true, false, false, 0xFFFFu, 0xFFFFu)},
-    {"cartpole", 4, 1, traits(true, true, true, true, 4, true, true, true, true, true, false, 0xFFFFu, 0xFFFFu)},
-    {"quadrotor", 12, 4, traits(false, true, false, false, 16, false, false, false, true, false, true, 0x0F0Fu | (3u << 18) | (3u << 26), 0x0F0Fu | (3u << 18) | (3u << 26))},
+    {"double integrator 2", 4, 2, traits(true, false, true, true, 4, true, true, true, true, true, false, 0xFFFFu, 0xFFFFu, 0x5500u)},
+    {"double integrator 3", 6, 3, traits(true, false, true, false, 4, false, false, false, true, false, false, 0xFFFFu, 0xFFFFu, 0x5500u)},
+    {"cartpole", 4, 1, traits(true, true, true, true, 4, true, true, true, true, true, false, 0xFFFFu, 0xFFFFu, 0x5500u)},
+    {"quadrotor", 12, 4, traits(false, true, false, false, 16, false, false, false, true, false, true, 0x0F0Fu | (3u << 18) | (3u << 26), 0x0F0Fu | (3u << 18) | (3u << 26), 0x0500u)},
 };
 
 static bool same_step(const StepPlan& a, const StepPlan& b) { return a.kind == b.kind && a.CW == b.CW && a.TW == b.TW && a.two_wave == b.two_wave && a.store_x == b.store_x && a.two_launch == b.two_launch; }

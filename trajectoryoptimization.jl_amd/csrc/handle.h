@@ -30,6 +30,22 @@ int fail(int code, const std::string& msg);  // records the message for to_last_
 
 constexpr int BLOCK = 64;  // one wave per workgroup: a small batch is spread over as many CUs as possible
 
+// THE launch sequence of every kernel of the library.  enqueue() puts a kernel on a stream; launched() checks hipGetLastError() and returns
+// TO_OK / TO_ERR_HIP; launch() is one after the other.  A launcher of several kernels enqueues all but the last: one check per launcher.
+template <class... P, class... A>
+inline void enqueue(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t stream, const A&... args) {
+  hipLaunchKernelGGL(kernel, grid, block, lds, stream, args...);
+}
+inline int launched() {
+  HIPCHECK(hipGetLastError());
+  return TO_OK;
+}
+template <class... P, class... A>
+inline int launch(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t stream, const A&... args) {
+  enqueue(kernel, grid, block, lds, stream, args...);
+  return launched();
+}
+
 struct ModelOps;
 
 }  // namespace to
@@ -156,80 +172,59 @@ struct ModelOps {
   int gains_lds_pieces = 0;    // 16-byte pieces of one gains row (LDS sizing of the forward pass)
   int crow[64];                // compact_row(g, c) of the tangent-matrix layout
   int nep = 0, rs = 0;         // Tm<M>::NEP, Tm<M>::RS
-  int (*rollout)(to_handle*) = nullptr;
+  // Entries indexed [plants]: [1] is the flagged instance that loads one plant per trajectory (DevProblem::pm set, to_set_model_params_batch;
+  // ops_plants_*.hip), null where a model has none.  A handle with pm set runs the general variants only (path_plan.h `plants`), so there is
+  // one expansion per layout, the general forward variants (index = the mode, bit 3 set) and no fused / scan / packed / two-wave instance.
+  int (*rollout[2])(to_handle*) = {};
   int (*cost)(to_handle*, int with_al, double* out, double* Jk) = nullptr;
   int (*violation)(to_handle*, double* out) = nullptr;
   int (*dual_update)(to_handle*) = nullptr;
   int (*outer)(to_handle*) = nullptr;
   int (*cost_derivs)(to_handle*, double* grad, double* hess) = nullptr;
-  int (*discrete_jacobian)(to_handle*, double* F) = nullptr;
+  int (*discrete_jacobian[2])(to_handle*, double* F) = {};
   int (*constraint_eval)(to_handle*, int ci, double* vals, double* jac) = nullptr;
   int (*constraint_hessian)(to_handle*, int ci, const double* lambda, double* H) = nullptr;
-  int (*expand)(to_handle*) = nullptr;
+  int (*expand[2])(to_handle*) = {};             // [0] picks layout, variant and kernel itself (ops.h op_expand); [1]: column and tangent-matrix layouts, general variant
   int (*expand_const)(to_handle*) = nullptr;     // packed expansion: the constant columns of [A B], written once per handle (k_expand_const_columns)
   int (*backward)(to_handle*) = nullptr;
-  int (*expand_lane_k)(to_handle*) = nullptr;    // lane-layout expansion, one lane per (trajectory, knot) (ops_lane.h; null: column-per-lane kernel)
+  int (*expand_lane_k[2])(to_handle*) = {};      // lane-layout expansion, one lane per (trajectory, knot) (ops_lane.h; [0] null: column-per-lane kernel; [1]: general variant)
   int (*expand_backward)(to_handle*) = nullptr;  // fused lane expansion + Riccati (small models; null elsewhere)
   int (*expand_backward_scan)(to_handle*) = nullptr;  // fused expansion + scan Riccati, one wave per trajectory (k_scan.h)
   int (*expand_backward_coop)(to_handle*) = nullptr;  // fused expansion + cooperative Riccati (small models with <= 8 directions)
   int (*pn_prepare)(to_handle*, int want) = nullptr;  // projected-Newton polish (k_pn.h): tables + workspace slots ...
-  int (*pn_launch)(to_handle*, int slot0, int count, hipStream_t stream, const to_solver_opts* opts) = nullptr;  // ... and its launches
-  int (*defect)(to_handle*, double* out) = nullptr;             // max dynamics / initial-condition defect of the nominal trajectory
+  int (*pn_launch[2])(to_handle*, int slot0, int count, hipStream_t stream, const to_solver_opts* opts) = {};  // ... and its launches
+  int (*defect[2])(to_handle*, double* out) = {};               // max dynamics / initial-condition defect of the nominal trajectory
   int (*infeasible_controls)(to_handle*) = nullptr;             // InfeasibleModel only: slack controls from the current states (k_misc.h)
-  int (*policy_rollout)(to_handle*, const PolicyArgs& pa, int waves) = nullptr;  // closed-loop policy rollout of `waves` waves from pa.g0 (k_policy.h)
-  // ... its stochastic instances (ops_policy_mc.hip): nz = the kernel's NZ, 1 .. 7; noise_mask = the bits of nz this model has instances for
+  // closed-loop policy rollout of `waves` waves from pa.g0 (k_policy.h): nz = the kernel's NZ, 0 (ops_policy.hip) or one of the stochastic
+  // instances 1 .. 7 (ops_policy_mc.hip); noise_mask = the bits of nz this model has instances for
+  int (*policy_rollout)(to_handle*, const PolicyArgs& pa, int waves) = nullptr;
   int (*policy_rollout_mc)(to_handle*, const PolicyArgs& pa, int waves, int nz) = nullptr;
   int policy_noise_mask = 0;
   int (*accept_roll)(to_handle*) = nullptr;  // accept by re-rolling the stored controls (k_forward.h; models without write-through)
-  int (*forward[32])(to_handle*) = {};  // by kernel variant (k_forward.h MODE bits); variants a model never uses stay null
+  int (*forward[2][32])(to_handle*) = {};  // by kernel variant (k_forward.h MODE bits); variants a model never uses stay null
   int (*forward2[32])(to_handle*) = {};  // the same variants as two-wave workgroups (k_forward2; models with LDS-staged gains)
-  // One plant per trajectory (DevProblem::pm set, to_set_model_params_batch): the flagged instances of the kernels that read model
-  // parameters (ops_plants_*.hip).  A handle with pm set runs the general variants only (path_plan.h `plants`), so there is one
-  // expansion per layout, the general forward variants (index = the mode, bit 3 set) and no fused / scan / packed / two-wave instance.
-  int (*rollout_pm)(to_handle*) = nullptr;
-  int (*discrete_jacobian_pm)(to_handle*, double* F) = nullptr;
-  int (*expand_pm)(to_handle*) = nullptr;        // column and tangent-matrix layouts (k_expand, general variant)
-  int (*expand_lane_pm)(to_handle*) = nullptr;   // lane layout (k_expand_lane, general variant)
-  int (*forward_pm[32])(to_handle*) = {};
-  int (*pn_launch_pm)(to_handle*, int slot0, int count, hipStream_t stream, const to_solver_opts* opts) = nullptr;
-  int (*defect_pm)(to_handle*, double* out) = nullptr;
+  // every kernel that reads model parameters has its flagged instance (lane: on the lane layout), the per-sample plant of the policy rollout included
+  bool plants(bool lane) const {
+    return rollout[1] && discrete_jacobian[1] && expand[1] && defect[1] && pn_launch[1] && forward[1][8] && (!lane || expand_lane_k[1]) && policy_rollout_mc &&
+           (policy_noise_mask & 4);
+  }
 };
 
 // each ops_*.hip fills the entries it instantiates; table indexed by model key (0..2 double integrator D=1..3, 3 Cartpole,
 // 4 Quadrotor, 5 Quadrotor{MRP}, 6 Quadrotor{RodriguesParam}, 7 hybrid double integrator, 8 general model vector)
 constexpr int N_MODEL_KEYS = 12;  // ... 9, 10 InfeasibleModel over the 1-D / 2-D double integrator, 11 over the Cartpole
-void fill_ops_small(ModelOps* table);
-void fill_ops_small_forward(ModelOps* table);
-void fill_ops_small_lane(ModelOps* table);
-void fill_ops_quad_misc(ModelOps* table);
-void fill_ops_quad_expand(ModelOps* table);
-void fill_ops_quad_backward(ModelOps* table);
-void fill_ops_quad_forward_a(ModelOps* table);
-void fill_ops_quad_forward_b(ModelOps* table);
-void fill_ops_quad_forward_c(ModelOps* table);
-void fill_ops_quad_forward2_a(ModelOps* table);
-void fill_ops_quad_forward2_b(ModelOps* table);
-void fill_ops_quad_forward2_c(ModelOps* table);
-void fill_ops_quadatt_misc(ModelOps* table);
-void fill_ops_quadmrp_expand(ModelOps* table);
-void fill_ops_quadrp_expand(ModelOps* table);
-void fill_ops_quadmrp_forward(ModelOps* table);
-void fill_ops_quadrp_forward(ModelOps* table);
-void fill_ops_hybrid(ModelOps* table);
-void fill_ops_small_forward2(ModelOps* table);
-void fill_ops_small_scan(ModelOps* table);
-void fill_ops_pn(ModelOps* table);
-void fill_ops_vector(ModelOps* table);
-void fill_ops_infeasible_a(ModelOps* table);
-void fill_ops_infeasible_b(ModelOps* table);
-void fill_ops_policy(ModelOps* table);
-void fill_ops_policy_mc(ModelOps* table);
-void fill_ops_plants_small(ModelOps* table);
-void fill_ops_plants_lane(ModelOps* table);
-void fill_ops_plants_forward(ModelOps* table);
-void fill_ops_plants_quad(ModelOps* table);
-void fill_ops_plants_quad_forward(ModelOps* table);
-void fill_ops_plants_pn(ModelOps* table);
+// THE list of the ops_*.hip translation units: fill_ops_<unit> is declared and called (fill_model_ops) from here, so a unit cannot be one without the other
+#define TO_OPS_UNITS(X)                                                                                                                          \
+  X(small) X(small_forward) X(small_lane) X(quad_misc) X(quad_expand) X(quad_backward) X(quad_forward_a) X(quad_forward_b) X(quad_forward_c)      \
+  X(quad_forward2_a) X(quad_forward2_b) X(quad_forward2_c) X(quadatt_misc) X(quadmrp_expand) X(quadrp_expand) X(quadmrp_forward) X(quadrp_forward) \
+  X(hybrid) X(small_forward2) X(small_scan) X(pn) X(vector) X(infeasible_a) X(infeasible_b) X(policy) X(policy_mc)                                \
+  X(plants_small) X(plants_lane) X(plants_forward) X(plants_quad) X(plants_quad_forward) X(plants_pn)
+#define TO_OPS_DECLARE(unit) void fill_ops_##unit(ModelOps* table);
+#define TO_OPS_CALL(unit) fill_ops_##unit(table);
+TO_OPS_UNITS(TO_OPS_DECLARE)
+inline void fill_model_ops(ModelOps* table) { TO_OPS_UNITS(TO_OPS_CALL) }
+#undef TO_OPS_DECLARE
+#undef TO_OPS_CALL
 
 // handle-owned device memory (red zones around it in guard mode); g_free accepts what g_malloc returned
 int g_malloc(to_handle* h, void** p, size_t bytes, const char* name);

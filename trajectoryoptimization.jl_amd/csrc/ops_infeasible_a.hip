@@ -5,15 +5,9 @@
 
 namespace to {
 template <class M>
-int op_infeasible_controls(to_handle* h) {
-  hipLaunchKernelGGL(k_infeasible_controls<M>, grid_b(h, h->a.P.N - 1), dim3(BLOCK), 0, h->stream, h->a);
-  HIPCHECK(hipGetLastError());
-  return TO_OK;
-}
-template <class M>
 static void fill_one(ModelOps& o) {
   fill_misc<M>(o);
-  o.expand = op_expand<M>;
+  o.expand[0] = op_expand<M>;
   o.backward = op_backward<M>;
   o.accept_roll = op_accept_roll<M>;
   o.infeasible_controls = op_infeasible_controls<M>;

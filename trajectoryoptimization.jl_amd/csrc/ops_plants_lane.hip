@@ -5,7 +5,7 @@
 namespace to {
 template <class M>
 static void fill_one(ModelOps& o) {
-  if constexpr (M::lane_backward && !M::lie) o.expand_lane_pm = op_expand_lane_pm<M>;
+  if constexpr (M::lane_backward && !M::lie) o.expand_lane_k[1] = op_expand_lane<M, true>;
 }
 void fill_ops_plants_lane(ModelOps* t) {
   fill_one<DoubleIntegratorModel<1>>(t[0]);

@@ -4,7 +4,7 @@
 
 namespace to {
 template <class M>
-static void fill_one(ModelOps& o) { o.pn_launch_pm = op_pn_launch<M, true>; o.defect_pm = op_defect<M, true>; }
+static void fill_one(ModelOps& o) { o.pn_launch[1] = op_pn_launch<M, true>; o.defect[1] = op_defect<M, true>; }
 
 void fill_ops_plants_pn(ModelOps* t) {
   fill_one<DoubleIntegratorModel<1>>(t[0]);

@@ -4,8 +4,8 @@
 
 namespace to {
 void fill_ops_plants_quad(ModelOps* t) {
-  t[4].rollout_pm = op_rollout_pm<QuadrotorModel>;
-  t[4].discrete_jacobian_pm = op_discrete_jacobian_pm<QuadrotorModel>;
-  t[4].expand_pm = op_expand_pm<QuadrotorModel>;
+  t[4].rollout[1] = op_rollout<QuadrotorModel, true>;
+  t[4].discrete_jacobian[1] = op_discrete_jacobian<QuadrotorModel, true>;
+  t[4].expand[1] = op_expand_pm<QuadrotorModel>;
 }
 }  // namespace to

@@ -5,9 +5,9 @@
 namespace to {
 template <class M>
 static void fill_one(ModelOps& o) {
-  o.rollout_pm = op_rollout_pm<M>;
-  o.discrete_jacobian_pm = op_discrete_jacobian_pm<M>;
-  o.expand_pm = op_expand_pm<M>;
+  o.rollout[1] = op_rollout<M, true>;
+  o.discrete_jacobian[1] = op_discrete_jacobian<M, true>;
+  o.expand[1] = op_expand_pm<M>;
 }
 void fill_ops_plants_small(ModelOps* t) {
   fill_one<DoubleIntegratorModel<1>>(t[0]);

@@ -62,7 +62,7 @@ int op_pn_prepare(to_handle* h, int want) {
 }
 
 template <class M>
-static void fill_one(ModelOps& o) { o.pn_prepare = op_pn_prepare<M>; o.pn_launch = op_pn_launch<M>; o.defect = op_defect<M>; }
+static void fill_one(ModelOps& o) { o.pn_prepare = op_pn_prepare<M>; o.pn_launch[0] = op_pn_launch<M>; o.defect[0] = op_defect<M>; }
 
 void fill_ops_pn(ModelOps* t) {
   fill_one<DoubleIntegratorModel<1>>(t[0]);

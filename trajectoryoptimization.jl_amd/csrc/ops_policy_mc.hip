@@ -6,35 +6,17 @@
 
 namespace to {
 
-template <class M, int NZ>
-int launch_policy_mc(to_handle* h, const PolicyArgs& pa, int waves) {
-  const bool uniform = pa.TPW == 0;
-  const size_t lds = M::lds_gains ? sizeof(double) * 2 * gains_lds_doubles<M>(uniform ? 1 : pa.TPW) : 0;  // two gains buffers
-  bool rk4 = false;
-  if constexpr (M::pin_rk4) rk4 = h->a.P.integrator == INTEG_RK4;
-  if constexpr (M::pin_rk4) {
-    if (rk4 && uniform) hipLaunchKernelGGL((k_policy_rollout<M, true, INTEG_RK4, NZ>), dim3(waves), dim3(BLOCK), lds, h->stream, h->a, pa);
-    else if (rk4) hipLaunchKernelGGL((k_policy_rollout<M, false, INTEG_RK4, NZ>), dim3(waves), dim3(BLOCK), lds, h->stream, h->a, pa);
-  }
-  if (!rk4) {
-    if (uniform) hipLaunchKernelGGL((k_policy_rollout<M, true, -1, NZ>), dim3(waves), dim3(BLOCK), lds, h->stream, h->a, pa);
-    else hipLaunchKernelGGL((k_policy_rollout<M, false, -1, NZ>), dim3(waves), dim3(BLOCK), lds, h->stream, h->a, pa);
-  }
-  HIPCHECK(hipGetLastError());
-  return TO_OK;
-}
-
 template <class M, bool NOISE>
 int op_policy_rollout_mc(to_handle* h, const PolicyArgs& pa, int waves, int nz) {
-  if (nz == 4) return launch_policy_mc<M, 4>(h, pa, waves);
+  if (nz == 4) return op_policy_rollout<M, 4>(h, pa, waves);
   if constexpr (NOISE) {
     switch (nz) {
-      case 1: return launch_policy_mc<M, 1>(h, pa, waves);
-      case 2: return launch_policy_mc<M, 2>(h, pa, waves);
-      case 3: return launch_policy_mc<M, 3>(h, pa, waves);
-      case 5: return launch_policy_mc<M, 5>(h, pa, waves);
-      case 6: return launch_policy_mc<M, 6>(h, pa, waves);
-      case 7: return launch_policy_mc<M, 7>(h, pa, waves);
+      case 1: return op_policy_rollout<M, 1>(h, pa, waves);
+      case 2: return op_policy_rollout<M, 2>(h, pa, waves);
+      case 3: return op_policy_rollout<M, 3>(h, pa, waves);
+      case 5: return op_policy_rollout<M, 5>(h, pa, waves);
+      case 6: return op_policy_rollout<M, 6>(h, pa, waves);
+      case 7: return op_policy_rollout<M, 7>(h, pa, waves);
     }
   }
   return fail(TO_ERR_UNSUPPORTED, "policy rollout: no kernel instance for this combination of noise and plants on this model");

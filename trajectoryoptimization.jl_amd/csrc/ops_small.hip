@@ -5,7 +5,7 @@ namespace to {
 template <class M>
 static void fill_one(ModelOps& o) {
   fill_misc<M>(o);
-  o.expand = op_expand<M>;
+  o.expand[0] = op_expand<M>;
   o.backward = op_backward<M>;
   if constexpr (!M::lie && Coop<M>::R <= 8) o.expand_backward_coop = op_expand_backward_coop<M>;
 }

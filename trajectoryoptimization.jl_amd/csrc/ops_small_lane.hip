@@ -7,7 +7,7 @@ namespace to {
 template <class M>
 static void fill_one(ModelOps& o) {
   if constexpr (M::lane_backward && !M::lie) {
-    o.expand_lane_k = op_expand_lane<M>;
+    o.expand_lane_k[0] = op_expand_lane<M>;
     o.expand_backward = op_expand_backward<M>;
   }
 }

@@ -7,7 +7,7 @@ namespace to {
 void fill_ops_vector(ModelOps* t) {
   using M = ModelVectorModel;
   fill_misc<M>(t[8]);
-  t[8].expand = op_expand<M>;
+  t[8].expand[0] = op_expand<M>;
   t[8].backward = op_backward<M>;
   fill_forward<M, 0, 16>(t[8]);
   t[8].accept_roll = op_accept_roll<M>;

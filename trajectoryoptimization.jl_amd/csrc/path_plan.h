@@ -15,7 +15,8 @@ struct PathTraits {
   bool write_through = false, mfma_backward = false, coop_backward = true, lane_backward = false;
   int ls_first_round = 16;
   bool expand_backward = false, expand_backward_coop = false, expand_backward_scan = false, accept_roll = false, expand_lane_k = false, expand_const = false;
-  uint32_t forward = 0, forward2 = 0;  // bit i: forward[i] / forward2[i] is compiled
+  uint32_t forward = 0, forward2 = 0;  // bit i: forward[0][i] / forward2[i] is compiled
+  uint32_t forward_plants = 0;         // bit i: forward[1][i], the variant that loads one plant per trajectory, is compiled
 };
 struct PathShape {
   int B = 1, Bp = 64, N = 2, ne = 1, m = 1, n_cons = 0, iterations_linesearch = 20;

@@ -53,10 +53,10 @@ int g_malloc(to_handle* h, void** p, size_t bytes, const char* name) {
   void* base = nullptr;
   HIPCHECK(hipMalloc(&base, payload + 2 * GUARD_BYTES));
   char* q = (char*)base + GUARD_BYTES;
-  hipLaunchKernelGGL(k_guard_fill, dim3(GUARD_BYTES / 8 / 64), dim3(64), 0, h->stream, (unsigned long long*)base);
-  hipLaunchKernelGGL(k_guard_fill, dim3(GUARD_BYTES / 8 / 64), dim3(64), 0, h->stream, (unsigned long long*)(q + payload));
+  enqueue(k_guard_fill, dim3(GUARD_BYTES / 8 / 64), dim3(64), 0, h->stream, (unsigned long long*)base);
+  enqueue(k_guard_fill, dim3(GUARD_BYTES / 8 / 64), dim3(64), 0, h->stream, (unsigned long long*)(q + payload));
   if (payload > bytes) HIPCHECK(hipMemsetAsync(q + bytes, 0, payload - bytes, h->stream));
-  HIPCHECK(hipGetLastError());
+  TRY(launched());
   h->guards.push_back({base, q, payload, name ? name : ""});
   h->guard_dirty = true;
   *p = q;
@@ -89,8 +89,7 @@ int check_guards(to_handle* h, const char* where) {
   }
   int bad = 0x7fffffff;
   HIPCHECK(hipMemcpyAsync(h->guard_bad, &bad, sizeof(int), hipMemcpyHostToDevice, h->stream));
-  hipLaunchKernelGGL(k_guard_check, dim3((unsigned)h->guards.size()), dim3(64), 0, h->stream, (const GuardZones*)h->guard_tab, h->guard_bad);
-  HIPCHECK(hipGetLastError());
+  TRY(launch(k_guard_check, dim3((unsigned)h->guards.size()), dim3(64), 0, h->stream, (const GuardZones*)h->guard_tab, h->guard_bad));
   HIPCHECK(hipMemcpyAsync(&bad, h->guard_bad, sizeof(int), hipMemcpyDeviceToHost, h->stream));
   HIPCHECK(hipStreamSynchronize(h->stream));
   if (bad != 0x7fffffff) {
@@ -111,19 +110,7 @@ namespace {
 ModelOps g_ops[N_MODEL_KEYS];
 std::once_flag g_ops_once;
 const ModelOps* model_ops(int key) {
-  std::call_once(g_ops_once, [] {
-    fill_ops_small(g_ops); fill_ops_small_forward(g_ops); fill_ops_small_lane(g_ops);
-    fill_ops_quad_misc(g_ops); fill_ops_quad_expand(g_ops); fill_ops_quad_backward(g_ops);
-    fill_ops_quad_forward_a(g_ops); fill_ops_quad_forward_b(g_ops); fill_ops_quad_forward_c(g_ops);
-    fill_ops_quad_forward2_a(g_ops); fill_ops_quad_forward2_b(g_ops); fill_ops_quad_forward2_c(g_ops);
-    fill_ops_quadatt_misc(g_ops); fill_ops_quadmrp_expand(g_ops); fill_ops_quadrp_expand(g_ops);
-    fill_ops_quadmrp_forward(g_ops); fill_ops_quadrp_forward(g_ops);
-    fill_ops_hybrid(g_ops); fill_ops_small_forward2(g_ops); fill_ops_small_scan(g_ops); fill_ops_pn(g_ops); fill_ops_vector(g_ops); fill_ops_infeasible_a(g_ops); fill_ops_infeasible_b(g_ops);
-    fill_ops_policy(g_ops);
-    fill_ops_policy_mc(g_ops);
-    fill_ops_plants_small(g_ops); fill_ops_plants_lane(g_ops); fill_ops_plants_forward(g_ops);
-    fill_ops_plants_quad(g_ops); fill_ops_plants_quad_forward(g_ops); fill_ops_plants_pn(g_ops);
-  });
+  std::call_once(g_ops_once, [] { fill_model_ops(g_ops); });
   return (key >= 0 && key < N_MODEL_KEYS) ? &g_ops[key] : nullptr;
 }
 
@@ -162,8 +149,7 @@ int upload_vec(to_handle* h, const double* host, double* d, int cnt, int L = -1,
   const size_t total = (size_t)cnt * h->a.P.B;
   TRY(ensure_stage(h, total * sizeof(double)));
   HIPCHECK(hipMemcpyAsync(h->stage, host, total * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  hipLaunchKernelGGL(k_to_device, grid_b(h, cnt), dim3(BLOCK), 0, h->stream, h->stage, d, L, e0, cnt, h->a.P.B);
-  HIPCHECK(hipGetLastError());
+  TRY(launch(k_to_device, grid_b(h, cnt), dim3(BLOCK), 0, h->stream, h->stage, d, L, e0, cnt, h->a.P.B));
   HIPCHECK(hipStreamSynchronize(h->stream));
   return TO_OK;
 }
@@ -171,8 +157,7 @@ int download_vec(to_handle* h, double* host, const double* d, int cnt, int L = -
   if (L < 0) L = cnt;
   const size_t total = (size_t)cnt * h->a.P.B;
   TRY(ensure_stage(h, total * sizeof(double)));
-  hipLaunchKernelGGL(k_to_host, grid_b(h, cnt), dim3(BLOCK), 0, h->stream, d, h->stage, L, e0, cnt, h->a.P.B);
-  HIPCHECK(hipGetLastError());
+  TRY(launch(k_to_host, grid_b(h, cnt), dim3(BLOCK), 0, h->stream, d, h->stage, L, e0, cnt, h->a.P.B));
   HIPCHECK(hipMemcpyAsync(host, h->stage, total * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIPCHECK(hipStreamSynchronize(h->stream));
   return TO_OK;
@@ -182,8 +167,7 @@ int download_nominal(to_handle* h, double* host, const double* slot0, int cnt, v
   const size_t total = (size_t)cnt * h->a.P.B;
   double* dst = (double*)dev_dst;
   if (!dst) { TRY(ensure_stage(h, total * sizeof(double))); dst = h->stage; }
-  hipLaunchKernelGGL(k_to_host, grid_b(h, cnt), dim3(BLOCK), 0, h->stream, slot0, dst, cnt, 0, cnt, h->a.P.B);
-  HIPCHECK(hipGetLastError());
+  TRY(launch(k_to_host, grid_b(h, cnt), dim3(BLOCK), 0, h->stream, slot0, dst, cnt, 0, cnt, h->a.P.B));
   if (host) HIPCHECK(hipMemcpyAsync(host, dst, total * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIPCHECK(hipStreamSynchronize(h->stream));
   return TO_OK;
@@ -229,8 +213,12 @@ bool diagonal_cost_blocks(const to_handle* h) {
 // what the host logic needs to know of a model's launch table (path_plan.h)
 PathTraits path_traits(const ModelOps& o) {
   PathTraits t{o.write_through, o.mfma_backward, o.coop_backward, o.lane_backward, o.ls_first_round, o.expand_backward != nullptr, o.expand_backward_coop != nullptr,
-               o.expand_backward_scan != nullptr, o.accept_roll != nullptr, o.expand_lane_k != nullptr, o.expand_const != nullptr, 0u, 0u};
-  for (int i = 0; i < 32; ++i) { if (o.forward[i]) t.forward |= 1u << i; if (o.forward2[i]) t.forward2 |= 1u << i; }
+               o.expand_backward_scan != nullptr, o.accept_roll != nullptr, o.expand_lane_k[0] != nullptr, o.expand_const != nullptr, 0u, 0u, 0u};
+  for (int i = 0; i < 32; ++i) {
+    if (o.forward[0][i]) t.forward |= 1u << i;
+    if (o.forward[1][i]) t.forward_plants |= 1u << i;
+    if (o.forward2[i]) t.forward2 |= 1u << i;
+  }
   return t;
 }
 
@@ -276,46 +264,44 @@ int upload_tables(to_handle* h) {
 }
 
 int launch_set_active(to_handle* h, int v, int clear_bpfail = 1) {
-  hipLaunchKernelGGL(k_set_active, grid_b(h), dim3(BLOCK), 0, h->stream, h->a, v, clear_bpfail);
-  HIPCHECK(hipGetLastError());
-  return TO_OK;
+  return launch(k_set_active, grid_b(h), dim3(BLOCK), 0, h->stream, h->a, v, clear_bpfail);
 }
-// (DevProblem::pm set — one plant per trajectory — : the flagged instances of the kernels that read model parameters, here and below)
-int launch_rollout(to_handle* h) { return h->a.P.pm ? h->ops->rollout_pm(h) : h->ops->rollout(h); }
-int launch_defect(to_handle* h, double* out) { return h->a.P.pm ? h->ops->defect_pm(h, out) : h->ops->defect(h, out); }
+// THE plants choice: DevProblem::pm set — one plant per trajectory — selects entry [1] of the kernels that read model parameters (handle.h ModelOps)
+inline int plants(const to_handle* h) { return h->a.P.pm != nullptr; }
+int launch_rollout(to_handle* h) { return h->ops->rollout[plants(h)](h); }
+int launch_defect(to_handle* h, double* out) { return h->ops->defect[plants(h)](h, out); }
 int launch_pn(to_handle* h, int slot0, int count, hipStream_t stream, const to_solver_opts* opts) {
-  return h->a.P.pm ? h->ops->pn_launch_pm(h, slot0, count, stream, opts) : h->ops->pn_launch(h, slot0, count, stream, opts);
+  return h->ops->pn_launch[plants(h)](h, slot0, count, stream, opts);
 }
+int launch_discrete_jacobian(to_handle* h, double* F) { return h->ops->discrete_jacobian[plants(h)](h, F); }
 int launch_cost(to_handle* h, int with_al, double* out, double* Jk) { return h->ops->cost(h, with_al, out, Jk); }
 int launch_expand(to_handle* h) {
-  if (h->a.P.pm) return h->a.bwd_lane ? h->ops->expand_lane_pm(h) : h->ops->expand_pm(h);
-  return h->ops->expand(h);
+  // with plants the lane layout takes the lane instance and the other layouts the general column / tangent-matrix one (no expand_lane knob);
+  // without, op_expand decides
+  if (plants(h) && h->a.bwd_lane) return h->ops->expand_lane_k[1](h);
+  return h->ops->expand[plants(h)](h);
 }
 int launch_backward(to_handle* h) { return h->ops->backward(h); }
 int launch_accept(to_handle* h) {  // materialise accepted candidate slots on slot 0, then forget them
   if (!h->a.store_x) return h->ops->accept_roll(h);  // their states were not stored: rolled out again from the stored controls (clears acc itself)
-  hipLaunchKernelGGL(k_accept, grid_b(h, 1, h->accept_chunks), dim3(BLOCK), 0, h->stream, h->a);
-  hipLaunchKernelGGL(k_clear_acc, grid_b(h), dim3(BLOCK), 0, h->stream, h->a);
-  HIPCHECK(hipGetLastError());
-  return TO_OK;
+  enqueue(k_accept, grid_b(h, 1, h->accept_chunks), dim3(BLOCK), 0, h->stream, h->a);
+  return launch(k_clear_acc, grid_b(h), dim3(BLOCK), 0, h->stream, h->a);
 }
 // forward pass: ONE launch runs the whole line search (CW step sizes per round, concurrently, inside each wave) and the
 // per-trajectory state machine (k_forward.h), in the kernel variant path_plan.h forward_mode picks
 int launch_forward(to_handle* h, bool accept = true, bool two_wave = false) {
   const DevProblem& P = h->a.P;  // (the general variants also with per-trajectory linear cost terms / constraint parameters: only they read them)
   if (P.pm) {  // one plant per trajectory: the general variants that load it per trajectory, as one-wave workgroups (stage cost read per knot)
-    uint32_t mask = 0;
-    for (int i = 0; i < 32; ++i) if (h->ops->forward_pm[i]) mask |= 1u << i;
-    const int pmode = forward_mode(false, P.n_cons > 0, P.integrator == INTEG_RK4, true, false, mask);
+    const int pmode = forward_mode(false, P.n_cons > 0, P.integrator == INTEG_RK4, true, false, h->traits.forward_plants);
     if (pmode < 0) return fail(TO_ERR_UNSUPPORTED, "forward-pass variant with per-trajectory model parameters not compiled for this model");
-    TRY(h->ops->forward_pm[pmode](h));
+    TRY(h->ops->forward[1][pmode](h));
     if (accept) TRY(launch_accept(h));
     return TO_OK;
   }
   const int mode = forward_mode(P.simple_stage, P.n_cons > 0, P.integrator == INTEG_RK4, (P.expand_variant & 5) || P.gl || P.cp, P.unit_soc, h->traits.forward);
   if (mode < 0) return fail(TO_ERR_UNSUPPORTED, "forward-pass variant not compiled for this model");
   if ((two_wave || h->plan.fwd2 == 1) && h->ops->forward2[mode]) TRY(h->ops->forward2[mode](h));
-  else TRY(h->ops->forward[mode](h));
+  else TRY(h->ops->forward[0][mode](h));
   if (accept) TRY(launch_accept(h));  // inside a solve the next expansion writes the accepted step through instead
   return TO_OK;
 }
@@ -324,13 +310,13 @@ int launch_outer(to_handle* h) { return h->ops->outer(h); }
 int launch_compact(to_handle* h) {
   const KArgs& a = h->a;
   int per, nb;
-  if (a.P.Bp <= COMPACT_ONE_LAUNCH) hipLaunchKernelGGL(k_compact, dim3(1), dim3(1024), 0, h->stream, a);
+  if (a.P.Bp <= COMPACT_ONE_LAUNCH) enqueue(k_compact, dim3(1), dim3(1024), 0, h->stream, a);
   else if (!compact_grid(a.P.Bp, &per, &nb)) return fail(TO_ERR_UNSUPPORTED, "batch too large for the compaction kernels (16 777 216 trajectories)");
   else {
-    hipLaunchKernelGGL(k_compact_count, dim3(nb), dim3(1024), 0, h->stream, a, per);
-    hipLaunchKernelGGL(k_compact_write, dim3(nb), dim3(1024), 0, h->stream, a, per);
+    enqueue(k_compact_count, dim3(nb), dim3(1024), 0, h->stream, a, per);
+    enqueue(k_compact_write, dim3(nb), dim3(1024), 0, h->stream, a, per);
   }
-  HIPCHECK(hipGetLastError());
+  TRY(launched());
   return TO_OK;
 }
 // ... and, in the two-launch line search, of the trajectories whose `pending` flag launch A left set (-> plist / pcount)
@@ -338,10 +324,8 @@ int launch_flag_list(to_handle* h) {
   const KArgs& a = h->a;
   int per, nb;
   if (!compact_grid(a.P.Bp, &per, &nb)) return fail(TO_ERR_UNSUPPORTED, "batch too large for the compaction kernels (16 777 216 trajectories)");
-  hipLaunchKernelGGL(k_flags_count, dim3(nb), dim3(1024), 0, h->stream, a.pending, a.P.Bp, per, a.ccount);
-  hipLaunchKernelGGL(k_flags_write, dim3(nb), dim3(1024), 0, h->stream, a.pending, a.P.Bp, per, a.ccount, a.plist, a.pcount);
-  HIPCHECK(hipGetLastError());
-  return TO_OK;
+  enqueue(k_flags_count, dim3(nb), dim3(1024), 0, h->stream, a.pending, a.P.Bp, per, a.ccount);
+  return launch(k_flags_write, dim3(nb), dim3(1024), 0, h->stream, a.pending, a.P.Bp, per, a.ccount, a.plist, a.pcount);
 }
 int launch_violation(to_handle* h, double* out) { return h->ops->violation(h, out); }
 
@@ -373,8 +357,7 @@ int fill_stats(to_handle* h, to_solve_stats* st, bool with_defect) {
     }
   }
   if (st->penalty_max) {
-    hipLaunchKernelGGL(k_penalty_max, grid_b(h), dim3(BLOCK), 0, h->stream, a, h->d_tmp);
-    HIPCHECK(hipGetLastError());
+    TRY(launch(k_penalty_max, grid_b(h), dim3(BLOCK), 0, h->stream, a, h->d_tmp));
     TRY(download_scalar(h, st->penalty_max, h->d_tmp));
   }
   st->total_iterations = tot;
@@ -454,15 +437,13 @@ int rp_move(to_handle* h, int count) {
   };
   dbg_sync("memsets");
   if (lvl > 0)  // what has finished in the set we leave goes home first (level 0 IS home)
-    hipLaunchKernelGGL(k_repack_home, dim3((a.P.B + 63) / 64, hm.n), dim3(64), 0, h->stream, hm, a.active, a.P.B, omap_old, 0);
+    enqueue(k_repack_home, dim3((a.P.B + 63) / 64, hm.n), dim3(64), 0, h->stream, hm, a.active, a.P.B, omap_old, 0);
   dbg_sync("k_repack_home");
-  hipLaunchKernelGGL(k_repack_move, dim3((count + 63) / 64, mv.n), dim3(64), 0, h->stream, mv, list, count, omap_old, h->rp_map[w]);
-  HIPCHECK(hipGetLastError());
+  TRY(launch(k_repack_move, dim3((count + 63) / 64, mv.n), dim3(64), 0, h->stream, mv, list, count, omap_old, h->rp_map[w]));
   dbg_sync("k_repack_move");
   for (int i = 0; i < mv.n; ++i) rp_field(h, h->rp_arr[i].off) = h->rp_work[w][i];
   a.P.B = count; a.P.Bp = Bp_new;
-  hipLaunchKernelGGL(k_repack_list, dim3((count + 255) / 256), dim3(256), 0, h->stream, a.alist + (size_t)next * a.P.Bp, a.acount + next, count);
-  HIPCHECK(hipGetLastError());
+  TRY(launch(k_repack_list, dim3((count + 255) / 256), dim3(256), 0, h->stream, a.alist + (size_t)next * a.P.Bp, a.acount + next, count));
   h->rp_level = lvl + 1;
   return TO_OK;
 }
@@ -476,8 +457,8 @@ int rp_finish(to_handle* h, bool copy) {
     RpArgs hm;
     hm.n = (int)h->rp_arr.size();
     for (int i = 0; i < hm.n; ++i) { hm.kind[i] = h->rp_arr[i].kind; hm.L[i] = h->rp_arr[i].L; hm.src[i] = rp_field(h, h->rp_arr[i].off); hm.dst[i] = h->rp_home[i]; }
-    hipLaunchKernelGGL(k_repack_home, dim3((a.P.B + 63) / 64, hm.n), dim3(64), 0, h->stream, hm, a.active, a.P.B, h->rp_map[w], 1);
-    if (hipGetLastError() != hipSuccess) rc = fail(TO_ERR_HIP, "k_repack_home launch failed");
+    if (launch(k_repack_home, dim3((a.P.B + 63) / 64, hm.n), dim3(64), 0, h->stream, hm, a.active, a.P.B, h->rp_map[w], 1) != TO_OK)
+      rc = fail(TO_ERR_HIP, "k_repack_home launch failed");
   }
   for (size_t i = 0; i < h->rp_arr.size(); ++i) rp_field(h, h->rp_arr[i].off) = h->rp_home[i];
   a.P.B = h->rp_B; a.P.Bp = h->rp_Bp;
@@ -522,7 +503,7 @@ int solve(to_handle* h, to_solve_stats* st, int al_mode) {
 // device time is added to h->last_ms.  The list goes through the workspace in chunks of h->pn_cap trajectories.
 int pn_run(to_handle* h, const std::vector<int>& list, const to_solver_opts& opts) {
   if (list.empty()) return TO_OK;
-  if (!h->ops->pn_launch) return fail(TO_ERR_UNSUPPORTED, "projected Newton not compiled for this model");
+  if (!h->ops->pn_launch[0]) return fail(TO_ERR_UNSUPPORTED, "projected Newton not compiled for this model");
   const int count = (int)list.size();
   TRY(h->ops->pn_prepare(h, count));
   hipEvent_t e0 = h->sev[0], e1 = h->sev[1];
@@ -637,7 +618,7 @@ int altro_solve(to_handle* h, to_solve_stats* st) {
   int early = 1;
   if (const char* env = std::getenv("TRAJOPT_PN_EARLY")) early = std::max(0, std::min(8, std::atoi(env)));
   h->pn_early = 0; h->pn_early_slots = 0;
-  if (early > 0 && h->ops->pn_launch && !h->ops->write_through) {  // (write-through models keep accepted steps in candidate slots until the solve ends)
+  if (early > 0 && h->ops->pn_launch[0] && !h->ops->write_through) {  // (write-through models keep accepted steps in candidate slots until the solve ends)
     // (a problem the polish cannot take — too many rows on a knot, no memory for the workspace — still gets its AL stage)
     if (h->ops->pn_prepare(h, B) == TO_OK && h->pn_cap >= B) {  // every trajectory has a workspace slot of its own
       TRY(early_polish_setup(h));
@@ -703,8 +684,7 @@ int solve_impl(to_handle* h, to_solve_stats* st, int al_mode) {
   const hipEvent_t e0 = h->sev[0], e1 = h->sev[1];
   HIPCHECK(hipEventRecord(e0, h->stream));
   HIPCHECK(hipMemsetAsync(a.it_pn, 0, sizeof(int) * P.Bp, h->stream));
-  hipLaunchKernelGGL(k_solve_init, grid_b(h), dim3(BLOCK), 0, h->stream, a, al_mode);
-  HIPCHECK(hipGetLastError());
+  TRY(launch(k_solve_init, grid_b(h), dim3(BLOCK), 0, h->stream, a, al_mode));
   TRY(launch_rollout(h));
   TRY(launch_cost(h, 1, a.J, nullptr));
   if (a.compact) {  // the initial rollout may have ended trajectories (TO_STATE_LIMIT / TO_CONTROL_LIMIT): the list of step 0 without them
@@ -762,7 +742,7 @@ int solve_impl(to_handle* h, to_solve_stats* st, int al_mode) {
       if (h->profile) HIPCHECK(hipEventRecord(h->ev[4 * step + 3], h->stream));
       if (h->guard) {
         if (step == 0) if (const char* env = std::getenv("TRAJOPT_GUARD_SELFTEST")) if (std::atoi(env))  // one double behind the nominal states
-          hipLaunchKernelGGL(k_guard_poke, dim3(1), dim3(1), 0, h->stream, a.Xs, (long long)P.N * P.n * (P.Bp + 64) + 3);
+          enqueue(k_guard_poke, dim3(1), dim3(1), 0, h->stream, a.Xs, (long long)P.N * P.n * (P.Bp + 64) + 3);
         TRY(check_guards(h, ("batch step " + std::to_string(step) + " of a solve").c_str()));
       }
       if (dbg_sync) {  // TRAJOPT_SYNC_DEBUG=1: localise a device fault to a batch step
@@ -987,7 +967,7 @@ int to_create(const to_problem_desc* desc, const to_solver_opts* opts, int devic
   h->R = coop_lanes(ne, m);
   h->G = 64 / h->R;
   h->ops = model_ops(key);
-  if (!h->ops || !h->ops->rollout || !h->ops->expand || !h->ops->backward) { delete h; return fail(TO_ERR_UNSUPPORTED, "model kernels not linked"); }
+  if (!h->ops || !h->ops->rollout[0] || !h->ops->expand[0] || !h->ops->backward) { delete h; return fail(TO_ERR_UNSUPPORTED, "model kernels not linked"); }
   h->traits = path_traits(*h->ops);
   h->costs.assign(desc->costs, desc->costs + desc->n_costs);
   h->cons = cons; h->dt = dt; h->cost_index = cost_index; h->step_table = step_table;
@@ -1203,8 +1183,7 @@ int to_set_controls_uniform(to_handle* h, const double* u) {
   const DevProblem& P = h->a.P;
   TRY(ensure_stage(h, sizeof(double) * P.m));
   HIPCHECK(hipMemcpyAsync(h->stage, u, sizeof(double) * P.m, hipMemcpyHostToDevice, h->stream));
-  hipLaunchKernelGGL(k_fill_uniform, grid_b(h, P.m * (P.N - 1)), dim3(BLOCK), 0, h->stream, h->a.Us, h->stage, P.m, P.m * (P.N - 1), P.B);
-  HIPCHECK(hipGetLastError());
+  TRY(launch(k_fill_uniform, grid_b(h, P.m * (P.N - 1)), dim3(BLOCK), 0, h->stream, h->a.Us, h->stage, P.m, P.m * (P.N - 1), P.B));
   HIPCHECK(hipStreamSynchronize(h->stream));
   return TO_OK;
 }
@@ -1356,9 +1335,7 @@ static const char* model_key_name(int key) {
   return (key >= 0 && key < N_MODEL_KEYS) ? names[key] : "unknown model";
 }
 static int model_params_supported(const to_handle* h, const char* who) {
-  const ModelOps& o = *h->ops;
-  if (h->model_key > 4 || !o.rollout_pm || !o.discrete_jacobian_pm || !o.expand_pm || !o.defect_pm || !o.pn_launch_pm || !o.forward_pm[8] ||
-      (h->a.bwd_lane && !o.expand_lane_pm) || !o.policy_rollout_mc || !(o.policy_noise_mask & 4))
+  if (h->model_key > 4 || !h->ops->plants(h->a.bwd_lane != 0))
     return fail(TO_ERR_UNSUPPORTED, std::string(who) + ": per-trajectory model parameters are not available for the " + model_key_name(h->model_key) +
                                         " (double integrator, Cartpole and quaternion Quadrotor only)");
   return TO_OK;
@@ -1429,8 +1406,7 @@ int to_stage_costs(to_handle* h, double* Jk) {
   TRY(ensure_stage(h, 2 * cnt * sizeof(double)));
   double* dJk = h->stage + cnt;
   TRY(launch_cost(h, 0, nullptr, dJk));
-  hipLaunchKernelGGL(k_to_host, grid_b(h, P.N), dim3(BLOCK), 0, h->stream, dJk, h->stage, P.N, 0, P.N, P.B);
-  HIPCHECK(hipGetLastError());
+  TRY(launch(k_to_host, grid_b(h, P.N), dim3(BLOCK), 0, h->stream, dJk, h->stage, P.N, 0, P.N, P.B));
   HIPCHECK(hipMemcpyAsync(Jk, h->stage, sizeof(double) * P.N * P.B, hipMemcpyDeviceToHost, h->stream));
   HIPCHECK(hipStreamSynchronize(h->stream));
   return TO_OK;
@@ -1608,9 +1584,9 @@ static int policy_rollout_impl(to_handle* h, int32_t S, const double* x0s, const
       double* hx = h->stage;
       double* hu = h->stage + (size_t)cnt * Lx;
       const unsigned gx = (unsigned)((cnt + 63) / 64);
-      if (out->X) hipLaunchKernelGGL(k_policy_to_host, dim3(gx, (unsigned)std::min<size_t>(Lx, 65535)), dim3(BLOCK), 0, h->stream, h->pol_xw, hx, (int)Lx, S, pa.TPW, pa.WPT, pa.g0, c0, cnt);
-      if (out->U) hipLaunchKernelGGL(k_policy_to_host, dim3(gx, (unsigned)std::min<size_t>(Lu, 65535)), dim3(BLOCK), 0, h->stream, h->pol_uw, hu, (int)Lu, S, pa.TPW, pa.WPT, pa.g0, c0, cnt);
-      HIPCHECK(hipGetLastError());
+      if (out->X) enqueue(k_policy_to_host, dim3(gx, (unsigned)std::min<size_t>(Lx, 65535)), dim3(BLOCK), 0, h->stream, h->pol_xw, hx, (int)Lx, S, pa.TPW, pa.WPT, pa.g0, c0, cnt);
+      if (out->U) enqueue(k_policy_to_host, dim3(gx, (unsigned)std::min<size_t>(Lu, 65535)), dim3(BLOCK), 0, h->stream, h->pol_uw, hu, (int)Lu, S, pa.TPW, pa.WPT, pa.g0, c0, cnt);
+      TRY(launched());
       if (out->X) HIPCHECK(hipMemcpyAsync(out->X + (size_t)c0 * Lx, hx, (size_t)cnt * Lx * sizeof(double), hipMemcpyDeviceToHost, h->stream));
       if (out->U) HIPCHECK(hipMemcpyAsync(out->U + (size_t)c0 * Lu, hu, (size_t)cnt * Lu * sizeof(double), hipMemcpyDeviceToHost, h->stream));
       HIPCHECK(hipStreamSynchronize(h->stream));  // the staging pair is re-used by the next chunk
@@ -1642,8 +1618,7 @@ int to_policy_noise_draws(int device, uint64_t seed, uint32_t traj, uint32_t sam
     ~DevBuf() { if (p) hipFree(p); }
   } bz;
   HIPCHECK(hipMalloc(&bz.p, (size_t)2 * pairs * sizeof(double)));
-  hipLaunchKernelGGL(k_policy_noise_draws, dim3(1), dim3(64), 0, 0, (unsigned long long)seed, traj, sample, k, kind, (int)pairs, (double*)bz.p);
-  HIPCHECK(hipGetLastError());
+  TRY(launch(k_policy_noise_draws, dim3(1), dim3(64), 0, 0, (unsigned long long)seed, traj, sample, k, kind, (int)pairs, (double*)bz.p));
   HIPCHECK(hipMemcpy(z, bz.p, (size_t)2 * pairs * sizeof(double), hipMemcpyDeviceToHost));
   return TO_OK;
 }
@@ -1730,23 +1705,23 @@ static int download_block(to_handle* h, double* host, int which, int row0, int R
   if (h->a.bwd_lane) {
     const int nc = P.ne + P.m;
     if (which == BLK_M)
-      hipLaunchKernelGGL(k_lane_to_host, grid_b(h, K * Rr * Cc), dim3(BLOCK), 0, h->stream, h->a.Mc, out, P.ne * nc, 0, nc, row0, Rr, col0, Cc, K, P.B);
+      enqueue(k_lane_to_host, grid_b(h, K * Rr * Cc), dim3(BLOCK), 0, h->stream, h->a.Mc, out, P.ne * nc, 0, nc, row0, Rr, col0, Cc, K, P.B);
     else
-      hipLaunchKernelGGL(k_lane_to_host, grid_b(h, K * Rr * Cc), dim3(BLOCK), 0, h->stream, h->a.Hc, out, nc * (nc + 1) / 2, 1, nc, row0, Rr, col0, Cc, K, P.B);
+      enqueue(k_lane_to_host, grid_b(h, K * Rr * Cc), dim3(BLOCK), 0, h->stream, h->a.Hc, out, nc * (nc + 1) / 2, 1, nc, row0, Rr, col0, Cc, K, P.B);
   } else if (h->a.bwd_mfma) {
     const int nep = h->ops->nep, rs = h->ops->rs;
     auto tix = [&](int i) { return i < P.ne ? i : nep + (i - P.ne); };  // tangent index (control directions start at NEP)
     const bool compact = which == BLK_H && h->a.h_compact;
-    hipLaunchKernelGGL(k_tm_to_host, grid_b(h, K * Rr * Cc), dim3(BLOCK), 0, h->stream, which == BLK_M ? h->a.Mt : h->a.Ht, out,
+    enqueue(k_tm_to_host, grid_b(h, K * Rr * Cc), dim3(BLOCK), 0, h->stream, which == BLK_M ? h->a.Mt : h->a.Ht, out,
                        which == BLK_M ? rs : rs + 1, tix(row0), Rr, tix(col0), Cc, K, P.B, compact ? h->d_crow : nullptr);
   } else {
     const int nc = P.ne + P.m;
     const int diag = (which == BLK_H && h->a.h_diag) ? 1 : 0;
-    hipLaunchKernelGGL(k_col_to_host, grid_b(h, K * Rr * Cc), dim3(BLOCK), 0, h->stream, which == BLK_M ? h->a.Mc : h->a.Hc, out,
+    enqueue(k_col_to_host, grid_b(h, K * Rr * Cc), dim3(BLOCK), 0, h->stream, which == BLK_M ? h->a.Mc : h->a.Hc, out,
                        which == BLK_M ? (P.N - 1) * P.ne : (diag ? P.N : P.N * nc), which == BLK_M ? P.ne : nc, row0, Rr, col0, Cc, K, P.B,
                        h->R, h->G, diag);
   }
-  HIPCHECK(hipGetLastError());
+  TRY(launched());
   if (dev_out) return TO_OK;
   HIPCHECK(hipMemcpyAsync(host, h->stage, cnt * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIPCHECK(hipStreamSynchronize(h->stream));
@@ -1760,14 +1735,14 @@ static int download_gradient(to_handle* h, double* host, int col0, int Cc, doubl
   double* const out = dev_out ? dev_out : h->stage;
   if (h->a.bwd_lane) {
     const int nc = P.ne + P.m;
-    hipLaunchKernelGGL(k_lane_to_host, grid_b(h, P.N * Cc), dim3(BLOCK), 0, h->stream, h->a.gc, out, nc, 0, nc, 0, 1, col0, Cc, P.N, P.B);
+    enqueue(k_lane_to_host, grid_b(h, P.N * Cc), dim3(BLOCK), 0, h->stream, h->a.gc, out, nc, 0, nc, 0, 1, col0, Cc, P.N, P.B);
   } else if (h->a.bwd_mfma) {
     const int tcol = col0 < P.ne ? col0 : h->ops->nep + (col0 - P.ne);
-    hipLaunchKernelGGL(k_tmvec_to_host, grid_b(h, P.N * Cc), dim3(BLOCK), 0, h->stream, h->a.gt, out, tcol, Cc, P.N, P.B);
+    enqueue(k_tmvec_to_host, grid_b(h, P.N * Cc), dim3(BLOCK), 0, h->stream, h->a.gt, out, tcol, Cc, P.N, P.B);
   } else {
-    hipLaunchKernelGGL(k_col_to_host, grid_b(h, P.N * Cc), dim3(BLOCK), 0, h->stream, h->a.gc, out, P.N, 1, 0, 1, col0, Cc, P.N, P.B, h->R, h->G, 0);
+    enqueue(k_col_to_host, grid_b(h, P.N * Cc), dim3(BLOCK), 0, h->stream, h->a.gc, out, P.N, 1, 0, 1, col0, Cc, P.N, P.B, h->R, h->G, 0);
   }
-  HIPCHECK(hipGetLastError());
+  TRY(launched());
   if (dev_out) return TO_OK;
   HIPCHECK(hipMemcpyAsync(host, h->stage, cnt * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIPCHECK(hipStreamSynchronize(h->stream));
@@ -1797,8 +1772,7 @@ int to_get_gains(to_handle* h, double* K, double* d, double* dV, double* rho) {
     const size_t nK = (size_t)P.m * P.ne * (P.N - 1) * P.B, nd = (size_t)P.m * (P.N - 1) * P.B;
     TRY(ensure_stage(h, (nK + nd) * sizeof(double)));
     double *dK = h->stage, *dd = h->stage + nK;
-    hipLaunchKernelGGL(k_gains_to_host, grid_b(h, (P.N - 1) * P.m * (P.ne + 1)), dim3(BLOCK), 0, h->stream, h->a.Kt, dK, dd, P.m, P.ne, P.N - 1, P.B);
-    HIPCHECK(hipGetLastError());
+    TRY(launch(k_gains_to_host, grid_b(h, (P.N - 1) * P.m * (P.ne + 1)), dim3(BLOCK), 0, h->stream, h->a.Kt, dK, dd, P.m, P.ne, P.N - 1, P.B));
     if (K) HIPCHECK(hipMemcpyAsync(K, dK, nK * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     if (d) HIPCHECK(hipMemcpyAsync(d, dd, nd * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHECK(hipStreamSynchronize(h->stream));
@@ -1831,9 +1805,8 @@ int to_get_cost_to_go(to_handle* h, double* S, double* s) {
   TRY(download_block(h, nullptr, BLK_H, P.ne, P.m, 0, P.ne, dux));
   TRY(download_gradient(h, nullptr, 0, P.ne, dx));
   TRY(download_gradient(h, nullptr, P.ne, P.m, du));
-  hipLaunchKernelGGL(k_gains_to_host, grid_b(h, (P.N - 1) * P.m * (P.ne + 1)), dim3(BLOCK), 0, h->stream, h->a.Kt, dK, dd, P.m, P.ne, P.N - 1, P.B);
-  hipLaunchKernelGGL(k_cost_to_go, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, h->stream, dA, dB, dxx, duu, dux, dx, du, dK, dd, dS, ds, P.ne, P.m, P.N, P.B);
-  HIPCHECK(hipGetLastError());
+  enqueue(k_gains_to_host, grid_b(h, (P.N - 1) * P.m * (P.ne + 1)), dim3(BLOCK), 0, h->stream, h->a.Kt, dK, dd, P.m, P.ne, P.N - 1, P.B);
+  TRY(launch(k_cost_to_go, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, h->stream, dA, dB, dxx, duu, dux, dx, du, dK, dd, dS, ds, P.ne, P.m, P.N, P.B));
   if (S) HIPCHECK(hipMemcpyAsync(S, dS, nxx * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   if (s) HIPCHECK(hipMemcpyAsync(s, ds, nx * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIPCHECK(hipStreamSynchronize(h->stream));
@@ -1856,7 +1829,7 @@ int to_discrete_jacobian(to_handle* h, double* F) {
   const DevProblem& P = h->a.P;
   const size_t cnt = (size_t)P.n * (P.n + P.m) * (P.N - 1) * P.B;
   TRY(ensure_stage(h, cnt * sizeof(double)));
-  TRY(h->a.P.pm ? h->ops->discrete_jacobian_pm(h, h->stage) : h->ops->discrete_jacobian(h, h->stage));
+  TRY(launch_discrete_jacobian(h, h->stage));
   HIPCHECK(hipMemcpyAsync(F, h->stage, cnt * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIPCHECK(hipStreamSynchronize(h->stream));
   return TO_OK;
@@ -2043,14 +2016,12 @@ int to_allgather(to_handle* h, void* dX_all, void* dU_all) {
   const size_t px = (size_t)P.n * P.N, pu = (size_t)P.m * (P.N - 1);
   if (dX_all) {  // own shard written in place, then one in-place gather on the handle's stream
     double* mine = (double*)dX_all + px * (size_t)h->comm_offset;
-    hipLaunchKernelGGL(k_to_host, grid_b(h, P.n * P.N), dim3(BLOCK), 0, h->stream, h->a.Xs, mine, P.n * P.N, 0, P.n * P.N, P.B);
-    HIPCHECK(hipGetLastError());
+    TRY(launch(k_to_host, grid_b(h, P.n * P.N), dim3(BLOCK), 0, h->stream, h->a.Xs, mine, P.n * P.N, 0, P.n * P.N, P.B));
     TRY(gather_blocks(h, dX_all, px, kNcclDouble, sizeof(double)));
   }
   if (dU_all) {
     double* mine = (double*)dU_all + pu * (size_t)h->comm_offset;
-    hipLaunchKernelGGL(k_to_host, grid_b(h, P.m * (P.N - 1)), dim3(BLOCK), 0, h->stream, h->a.Us, mine, P.m * (P.N - 1), 0, P.m * (P.N - 1), P.B);
-    HIPCHECK(hipGetLastError());
+    TRY(launch(k_to_host, grid_b(h, P.m * (P.N - 1)), dim3(BLOCK), 0, h->stream, h->a.Us, mine, P.m * (P.N - 1), 0, P.m * (P.N - 1), P.B));
     TRY(gather_blocks(h, dU_all, pu, kNcclDouble, sizeof(double)));
   }
   HIPCHECK(hipStreamSynchronize(h->stream));
@@ -2110,10 +2081,10 @@ static int cone_op(int device, int which, int32_t cone, int32_t dim, int64_t cou
   HIPCHECK(hipMemcpy(dx, x, nx * sizeof(double), hipMemcpyHostToDevice));
   if (which == 2) { HIPCHECK(hipMalloc(&bb.p, nx * sizeof(double))); db = (double*)bb.p; HIPCHECK(hipMemcpy(db, b, nx * sizeof(double), hipMemcpyHostToDevice)); }
   const unsigned blocks = (unsigned)((count + 255) / 256);
-  if (which == 0) hipLaunchKernelGGL(k_cone_projection, dim3(blocks), dim3(256), 0, 0, cone, dim, (long long)count, dx, dout, dst);
-  else if (which == 1) hipLaunchKernelGGL(k_cone_jacobian, dim3(blocks), dim3(256), 0, 0, cone, dim, (long long)count, dx, dout, dst);
-  else hipLaunchKernelGGL(k_cone_hessian, dim3(blocks), dim3(256), 0, 0, cone, dim, (long long)count, dx, db, dout, dst);
-  HIPCHECK(hipGetLastError());
+  if (which == 0) enqueue(k_cone_projection, dim3(blocks), dim3(256), 0, 0, cone, dim, (long long)count, dx, dout, dst);
+  else if (which == 1) enqueue(k_cone_jacobian, dim3(blocks), dim3(256), 0, 0, cone, dim, (long long)count, dx, dout, dst);
+  else enqueue(k_cone_hessian, dim3(blocks), dim3(256), 0, 0, cone, dim, (long long)count, dx, db, dout, dst);
+  TRY(launched());
   HIPCHECK(hipMemcpy(out, dout, no * sizeof(double), hipMemcpyDeviceToHost));
   std::vector<int> st(count);
   HIPCHECK(hipMemcpy(st.data(), dst, count * sizeof(int), hipMemcpyDeviceToHost));
