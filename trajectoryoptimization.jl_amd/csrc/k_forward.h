@@ -573,6 +573,42 @@ struct Fwd2Ring {
   static constexpr int NV = n + 2 * m, PAIRS = (NV + 1) / 2, SLOT = PAIRS * 128;  // doubles per slot: 64 lanes x PAIRS 16-byte pieces
 };
 
+// One knot of the roller for the models whose gains row travels in registers (!M::lds_gains): x̄_k in x, the knot's nominal and gains
+// row in cur; publishes (x_k, u_k, d_k) in the ring slot and steps to xn.  The expressions are forward_candidate's, one by one.
+template <class M, int MODE>
+__device__ __forceinline__ void fwd2_roll_knot(const FwdKnot<M, true>& cur, const double* x, double alpha, const double* mp, int integrator, int k,
+                                               double h, double2* slot, double* xn) {
+  constexpr int n = M::n, m = M::m, ne = M::ne;
+  using R = Fwd2Ring<M>;
+  double vals[2 * R::PAIRS];  // [x_k | u_k | d_k | pad]
+#pragma unroll
+  for (int i = 0; i < n; ++i) vals[i] = x[i];
+  double dx[ne], ub[m];
+  state_diff<M>(x, cur.x, dx);
+#pragma unroll
+  for (int j = 0; j < m; ++j) {
+    const double dj = cur.kd[j * (ne + 1) + ne];
+    double du = dj * alpha;
+#pragma unroll
+    for (int i = 0; i < ne; ++i) du += cur.kd[j * (ne + 1) + i] * dx[i];
+    ub[j] = cur.u[j] + du;
+    vals[n + j] = ub[j];
+    vals[n + m + j] = dj;
+  }
+  if (2 * R::PAIRS > R::NV) vals[2 * R::PAIRS - 1] = 0.0;
+#pragma unroll
+  for (int pr = 0; pr < R::PAIRS; ++pr) slot[pr * 64] = make_double2(vals[2 * pr], vals[2 * pr + 1]);
+  model_step<M, double, (MODE & 4) ? INTEG_RK4 : -1>(mp, integrator, k, x, ub, h, xn);
+  FWD2_BARRIER();
+}
+template <class M>
+__device__ __forceinline__ void fwd2_roll_terminal(const double* x, double2* slot) {
+  constexpr int n = M::n;
+#pragma unroll
+  for (int pr = 0; pr < (n + 1) / 2; ++pr) slot[pr * 64] = make_double2(x[2 * pr], (2 * pr + 1 < n) ? x[2 * pr + 1] : 0.0);
+  FWD2_BARRIER();
+}
+
 template <class M, int MODE>
 __device__ __forceinline__ void fwd2_roll(const KArgs& a, int tile, int lane, int b, double alpha, double* kbuf, int kbuf_len, int krow,
                                           int TW, int hw, double* ring) {
@@ -594,71 +630,94 @@ __device__ __forceinline__ void fwd2_roll(const KArgs& a, int tile, int lane, in
   double xb[n];
 #pragma unroll
   for (int i = 0; i < n; ++i) xb[i] = EL(px0, i);
-  if constexpr (KLDS) stage_gains<M>(a.Kt, b, TW, 0, N, kbuf, hw);
-  FwdKnot<M, !KLDS> nxt;
-  nxt.load(Xc, Uc, pK);
-  const double *pXn = Xc + n * 64, *pUn = Uc + m * 64, *pKn = pK + RSK;
-  for (int k = 0; k < N - 1; ++k) {
-    if constexpr (KLDS) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const FwdKnot<M, !KLDS> cur = nxt;
-    const double* kcur = kbuf + (size_t)(k & 1) * kbuf_len + krow;
-    if constexpr (!KLDS) {  // gains row in registers: plain loads, the compiler waits for exactly what it uses — issue them first
-      if (k + 1 < N - 1) nxt.load(pXn, pUn, pKn);
-      pXn += n * 64; pUn += m * 64; pKn += RSK;
-    }
-    double vals[2 * R::PAIRS];  // [x_k | u_k | d_k | pad]
-#pragma unroll
-    for (int i = 0; i < n; ++i) vals[i] = xb[i];
-    double dx[ne], ub[m], xn[n];
-    state_diff<M>(xb, cur.x, dx);
-    {
-      // the roller has registers to spare (the accountant holds the cost / AL state): the whole gains block of the knot is
-      // requested in one go — one LDS round trip per knot instead of one per row (C3 forward phase 604.8 -> 599.5 us per step)
-      double kr[m][ne + 1];
-#pragma unroll
-      for (int j = 0; j < m; ++j)
-#pragma unroll
-        for (int i = 0; i <= ne; ++i) kr[j][i] = KLDS ? kcur[j * (ne + 1) + i] : cur.kd[KLDS ? 0 : j * (ne + 1) + i];
-      if constexpr (KLDS) __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int j = 0; j < m; ++j) {
-        const double dj = kr[j][ne];
-        double du = dj * alpha;
-#pragma unroll
-        for (int i = 0; i < ne; ++i) du += kr[j][i] * dx[i];
-        ub[j] = cur.u[j] + du;
-        vals[n + j] = ub[j];
-        vals[n + m + j] = dj;
+  if constexpr (!KLDS) {
+    // Gains row in registers: the knot loop is unrolled by two and the knot data and the state ping-pong between two sets of registers
+    // (ka, xb: even knots; kb, xo: odd knots), so no value is copied from "next" to "current" at the turn of a knot, the ring slot
+    // k & 1 is a constant of each half, and the three nominal pointers advance once per two knots.  The loads of knot k + 1 still go
+    // out before knot k is computed — a whole knot ahead, plain loads, the compiler waits for exactly what it uses.
+    FwdKnot<M, true> ka, kb;
+    ka.load(Xc, Uc, pK);
+    // (the uniform time step in a VGPR: as an SGPR its scalar load is first waited for INSIDE the loop, with lgkmcnt(0), which there
+    // also waits for the ring writes issued a few instructions earlier)
+    const double hs = in_vgpr(h0);
+    double2* const slot0 = (double2*)ring + hw;
+    double2* const slot1 = (double2*)(ring + R::SLOT) + hw;
+    const double *pXk = Xc, *pUk = Uc, *pKk = pK;  // knot k of the nominal
+    double xo[n];
+    int k = 0;
+    for (; k + 2 <= N - 1; k += 2) {
+      kb.load(pXk + n * 64, pUk + m * 64, pKk + RSK);  // knot k + 1 <= N - 2
+      fwd2_roll_knot<M, MODE>(ka, xb, alpha, mp, integrator, k, SIMPLE ? hs : P.dt[k], slot0, xo);
+      {
+        // knot k + 2, unconditionally: past the last stage knot the loads re-read knot k + 1 (never used).  Behind a branch they
+        // made the compiler wait for EVERYTHING in flight (vmcnt(0)) where the odd knot first touches kb — the path around the
+        // branch has nothing else outstanding — and that exposed these loads' round trip in every pass.
+        const size_t adv = (k + 2 < N - 1) ? 2 : 1;
+        ka.load(pXk + adv * (n * 64), pUk + adv * (m * 64), pKk + adv * RSK);
       }
+      fwd2_roll_knot<M, MODE>(kb, xo, alpha, mp, integrator, k + 1, SIMPLE ? hs : P.dt[k + 1], slot1, xb);
+      pXk += 2 * n * 64; pUk += 2 * m * 64; pKk += 2 * RSK;
     }
-    if (2 * R::PAIRS > R::NV) vals[2 * R::PAIRS - 1] = 0.0;
-    double2* slot = (double2*)(ring + (size_t)(k & 1) * R::SLOT) + hw;
+    if (k < N - 1) {  // N - 1 odd: the last stage knot is an even one, the terminal state lands in slot (N - 1) & 1 = 1
+      fwd2_roll_knot<M, MODE>(ka, xb, alpha, mp, integrator, k, SIMPLE ? hs : P.dt[k], slot0, xo);
+      fwd2_roll_terminal<M>(xo, slot1);
+    } else fwd2_roll_terminal<M>(xb, slot0);
+  } else {
+    stage_gains<M>(a.Kt, b, TW, 0, N, kbuf, hw);
+    FwdKnot<M, false> nxt;
+    nxt.load(Xc, Uc, pK);
+    const double *pXn = Xc + n * 64, *pUn = Uc + m * 64, *pKn = pK + RSK;
+    for (int k = 0; k < N - 1; ++k) {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      const FwdKnot<M, false> cur = nxt;
+      const double* kcur = kbuf + (size_t)(k & 1) * kbuf_len + krow;
+      double vals[2 * R::PAIRS];  // [x_k | u_k | d_k | pad]
 #pragma unroll
-    for (int pr = 0; pr < R::PAIRS; ++pr) slot[pr * 64] = make_double2(vals[2 * pr], vals[2 * pr + 1]);
-    // LDS-staged gains: the next knot's DMA / loads go out only NOW.  hipcc orders every LDS write of a wave behind its
-    // outstanding LDS-DMAs (it cannot tell the ring from the gains buffers) and a vmcnt wait drains the nominal loads with
-    // them — issued at the top of the knot, as in k_forward, the ring writes above stalled for a full memory round trip per
-    // knot.  They land during the RK stages.
-    if constexpr (KLDS) {
+      for (int i = 0; i < n; ++i) vals[i] = xb[i];
+      double dx[ne], ub[m], xn[n];
+      state_diff<M>(xb, cur.x, dx);
+      {
+        // the roller has registers to spare (the accountant holds the cost / AL state): the whole gains block of the knot is
+        // requested in one go — one LDS round trip per knot instead of one per row (C3 forward phase 604.8 -> 599.5 us per step)
+        double kr[m][ne + 1];
+#pragma unroll
+        for (int j = 0; j < m; ++j)
+#pragma unroll
+          for (int i = 0; i <= ne; ++i) kr[j][i] = kcur[j * (ne + 1) + i];
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int j = 0; j < m; ++j) {
+          const double dj = kr[j][ne];
+          double du = dj * alpha;
+#pragma unroll
+          for (int i = 0; i < ne; ++i) du += kr[j][i] * dx[i];
+          ub[j] = cur.u[j] + du;
+          vals[n + j] = ub[j];
+          vals[n + m + j] = dj;
+        }
+      }
+      if (2 * R::PAIRS > R::NV) vals[2 * R::PAIRS - 1] = 0.0;
+      double2* slot = (double2*)(ring + (size_t)(k & 1) * R::SLOT) + hw;
+#pragma unroll
+      for (int pr = 0; pr < R::PAIRS; ++pr) slot[pr * 64] = make_double2(vals[2 * pr], vals[2 * pr + 1]);
+      // LDS-staged gains: the next knot's DMA / loads go out only NOW.  hipcc orders every LDS write of a wave behind its
+      // outstanding LDS-DMAs (it cannot tell the ring from the gains buffers) and a vmcnt wait drains the nominal loads with
+      // them — issued at the top of the knot, as in k_forward, the ring writes above stalled for a full memory round trip per
+      // knot.  They land during the RK stages.
       if (k + 1 < N - 1) {
         stage_gains<M>(a.Kt, b, TW, k + 1, N, kbuf + (size_t)((k + 1) & 1) * kbuf_len, hw);
         nxt.load(pXn, pUn, pKn);
       }
       pXn += n * 64; pUn += m * 64; pKn += RSK;
+      const double h = SIMPLE ? h0 : P.dt[k];
+      model_step<M, double, (MODE & 4) ? INTEG_RK4 : -1>(mp, integrator, k, xb, ub, h, xn);
+#pragma unroll
+      for (int i = 0; i < n; ++i) xb[i] = xn[i];
+      FWD2_BARRIER();
     }
-    const double h = SIMPLE ? h0 : P.dt[k];
-    model_step<M, double, (MODE & 4) ? INTEG_RK4 : -1>(mp, integrator, k, xb, ub, h, xn);
-#pragma unroll
-    for (int i = 0; i < n; ++i) xb[i] = xn[i];
-    FWD2_BARRIER();
+    fwd2_roll_terminal<M>(xb, (double2*)(ring + (size_t)((N - 1) & 1) * R::SLOT) + hw);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   }
-  {  // terminal state
-    double2* slot = (double2*)(ring + (size_t)((N - 1) & 1) * R::SLOT) + hw;
-#pragma unroll
-    for (int pr = 0; pr < (n + 1) / 2; ++pr) slot[pr * 64] = make_double2(xb[2 * pr], (2 * pr + 1 < n) ? xb[2 * pr + 1] : 0.0);
-    FWD2_BARRIER();
-  }
-  if constexpr (KLDS) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
 template <class M, int MODE>
