@@ -67,7 +67,10 @@ extern "C" {
  * Departure from that rule, once: to_set_model_params_batch / to_get_model_params_batch / to_clear_model_params_batch (one plant per
  * trajectory on the planning side) were added WITHOUT raising TO_ABI_MINOR, which stays 1.  A host detects them by symbol lookup —
  * dlsym() in C, Libdl.dlsym(lib, sym; throw_error = false) in Julia, an optional binding in the Python mirror — and treats a library
- * without them as one that plans every trajectory on to_problem_desc::model_params. */
+ * without them as one that plans every trajectory on to_problem_desc::model_params.  The same holds for to_set_constraint_limits_batch /
+ * to_get_constraint_limits_batch / to_clear_constraint_limits_batch (the bounds of a BoundConstraint, the value of a second-order-cone
+ * NormConstraint, one set per trajectory): added with TO_ABI_VERSION and TO_ABI_MINOR unchanged, found by symbol lookup; a library
+ * without them shares every limit among the trajectories of a handle. */
 #define TO_ABI_VERSION 7
 #define TO_ABI_MINOR 1
 
@@ -416,6 +419,26 @@ int to_clear_constraint_params_batch(to_handle* h);
 int to_set_model_params_batch(to_handle* h, const double* params /* [16*B] */);
 int to_get_model_params_batch(to_handle* h, double* params /* [16*B] */);
 int to_clear_model_params_batch(to_handle* h);
+/* One set of constraint LIMITS per TRAJECTORY: a fleet whose members have different actuators — the Cartpole's |u| <= 3, the thrust budget
+ * |u| <= 6 of a Quadrotor — on one handle.  con_id names
+ *   a TO_CON_BOUND constraint (BoundConstraint, src/constraints.jl:660-765): limits[q, B] (q fastest) with q = p, the values of the
+ *     constraint's FINITE rows in its own row order [x_max..., u_max..., x_min..., u_min...] — the order of to_evaluate_constraints and of
+ *     src/constraints.jl:738-741.  Which entries are finite is the descriptor's for every trajectory (p cannot change per trajectory);
+ *   a TO_CON_NORM constraint with TO_CONE_SECOND_ORDER (NormConstraint(..., SecondOrderCone(), ...), src/constraints.jl:442-517): q = 1,
+ *     the value a_b of the cone's last row.
+ * Refused: a value that is not finite, or an upper row below the lower row of the same coordinate in any trajectory ("Upper bounds must be
+ * greater than or equal to lower bounds", src/constraints.jl:712) — TO_ERR_ARGUMENT; a_b < 0 — TO_ERR_ASSERTION (src/constraints.jl:451);
+ * every other kind, the quadratic form of NormConstraint included — TO_ERR_UNSUPPORTED (for a GoalConstraint's target and a
+ * LinearConstraint's right-hand side see to_set_constraint_params_batch).  Everything that evaluates the constraint — AL terms and their
+ * expansion, violation, dual update, the projected-Newton polish, to_evaluate_constraints, the violation to_policy_rollout reports — then
+ * evaluates row r of trajectory b as sgn_r (z - limit_b[r]), the expression a single-trajectory problem built with that limit evaluates; the
+ * solves run the general kernel variants while any constraint carries limits (as with to_set_constraint_params_batch).  The setter leaves
+ * X, U, duals and gains as they are.  to_get_... returns what was set, or the descriptor's values repeated B times.  to_set_constraint on
+ * the constraint returns it to shared limits; to_clear_... returns the whole handle to the descriptors — a solve after it is bit-identical
+ * to the same solve on a fresh handle.  Not announced by TO_ABI_MINOR: look the symbols up (ABI history above). */
+int to_set_constraint_limits_batch(to_handle* h, int32_t con_id, const double* limits /* [q*B], q fastest */);
+int to_get_constraint_limits_batch(to_handle* h, int32_t con_id, double* limits /* [q*B] */);
+int to_clear_constraint_limits_batch(to_handle* h);
 
 /* ---- the hot path, phase by phase ----------------------------------------------------------- */
 int to_rollout(to_handle* h);                                   /* rollout!  src/problem.jl:330-340 */

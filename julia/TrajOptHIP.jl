@@ -768,6 +768,32 @@ function clear_model_params_batch!(p::BatchProblem)
     check(ccall((:to_clear_model_params_batch, lib), Cint, (Ptr{Cvoid},), p.handle))
     nothing
 end
+"""
+    set_constraint_limits_batch!(p, con_id, limits)       # limits :: (q, B)
+One set of limits per trajectory for constraint `con_id` (1-based position in the ConstraintList; `to_set_constraint_limits_batch`): the
+values of a `BoundConstraint`'s finite rows in row order `[x_max..., u_max..., x_min..., u_min...]` (`q = p`), or the value `a_b` of a
+`NormConstraint(..., SecondOrderCone(), ...)` (`q = 1`).  `get_constraint_limits_batch(p, con_id, q)` returns what is set (the descriptor's
+values repeated if nothing is), `clear_constraint_limits_batch!(p)` returns every constraint to its descriptor.  Added without raising
+`TO_ABI_MINOR`: a library that lacks them is detected by symbol lookup (`has_constraint_limits_batch()`).
+"""
+has_constraint_limits_batch() = Libdl.dlsym(Libdl.dlopen(lib), :to_set_constraint_limits_batch; throw_error = false) !== nothing
+function set_constraint_limits_batch!(p::BatchProblem, con_id::Integer, limits::Matrix{Float64})
+    has_constraint_limits_batch() || error("libtrajopt_hip.so does not export to_set_constraint_limits_batch")
+    size(limits, 2) == p.B || throw(DimensionMismatch("limits must be (q, B)"))
+    check(ccall((:to_set_constraint_limits_batch, lib), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}), p.handle, Int32(con_id - 1), limits))
+    nothing
+end
+function get_constraint_limits_batch(p::BatchProblem, con_id::Integer, q::Integer)
+    has_constraint_limits_batch() || error("libtrajopt_hip.so does not export to_get_constraint_limits_batch")
+    limits = zeros(q, p.B)
+    check(ccall((:to_get_constraint_limits_batch, lib), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}), p.handle, Int32(con_id - 1), limits))
+    limits
+end
+function clear_constraint_limits_batch!(p::BatchProblem)
+    has_constraint_limits_batch() || error("libtrajopt_hip.so does not export to_clear_constraint_limits_batch")
+    check(ccall((:to_clear_constraint_limits_batch, lib), Cint, (Ptr{Cvoid},), p.handle))
+    nothing
+end
 function clear_goal_state_batch!(p::BatchProblem)
     check(ccall((:to_clear_cost_linear_batch, lib), Cint, (Ptr{Cvoid},), p.handle))
     check(ccall((:to_clear_constraint_params_batch, lib), Cint, (Ptr{Cvoid},), p.handle))
@@ -921,7 +947,7 @@ function profile(p::BatchProblem)
     (kernel_ms = ms, launches = launches)
 end
 
-export LinearMap, MassDoubleIntegrator, BatchProblem, set_model_params_batch!, model_params_batch, clear_model_params_batch!, has_model_params_batch, policy_rollout, PolicyOpts, PolicyResult, policy_rollout_mc, policy_noise_draws, PolicyNoise, abi_minor, SolverOpts, solver_options, default_options, solve_ilqr!, solve_al!, solve_pn!, solve_altro!, solve_async!, wait_solve!, dynamics_defect, expand!, backwardpass!, forwardpass!,
+export LinearMap, MassDoubleIntegrator, BatchProblem, set_model_params_batch!, model_params_batch, clear_model_params_batch!, has_model_params_batch, set_constraint_limits_batch!, get_constraint_limits_batch, clear_constraint_limits_batch!, has_constraint_limits_batch, policy_rollout, PolicyOpts, PolicyResult, policy_rollout_mc, policy_noise_draws, PolicyNoise, abi_minor, SolverOpts, solver_options, default_options, solve_ilqr!, solve_al!, solve_pn!, solve_altro!, solve_async!, wait_solve!, dynamics_defect, expand!, backwardpass!, forwardpass!,
     stage_costs, al_cost, dynamics_jacobians, cost_expansion, gains, cost_gradient_hessian, discrete_jacobian, duals, set_duals!,
     reset_duals!, dual_update!, comm_unique_id, comm_init_rank!, allgather!, allgather_stats, comm_shards, comm_destroy!, solver_path, knot_dims, device_count, build_id
 

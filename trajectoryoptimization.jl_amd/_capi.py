@@ -253,10 +253,15 @@ HIP_ONLY = {
     "set_model_params_batch": [_H, _PD],
     "get_model_params_batch": [_H, _PD],
     "clear_model_params_batch": [_H],
+    # one set of bounds / one cone value per trajectory (OPTIONAL_HIP below)
+    "set_constraint_limits_batch": [_H, C.c_int32, _PD],
+    "get_constraint_limits_batch": [_H, C.c_int32, _PD],
+    "clear_constraint_limits_batch": [_H],
 }
 # Entry points added without raising TO_ABI_MINOR (include/trajopt_hip.h, ABI history): detected by symbol lookup.  A library that does
 # not export them still loads; the names are then absent from Library._fn and the wrappers in api.py raise UnsupportedError.
-OPTIONAL_HIP = ("set_model_params_batch", "get_model_params_batch", "clear_model_params_batch")
+OPTIONAL_HIP = ("set_model_params_batch", "get_model_params_batch", "clear_model_params_batch",
+                "set_constraint_limits_batch", "get_constraint_limits_batch", "clear_constraint_limits_batch")
 
 
 class Library:

@@ -33,7 +33,8 @@ from ._capi import (ArgumentError, DimensionMismatch, ConstraintDesc, CostDesc, 
                     SolverOpts, SolveStats, UnsupportedError)
 
 __all__ = [
-    "clear_goal_state_batch", "set_constraint_params_batch", "InfeasibleModel", "InfeasibleConstraint", "InfeasibleProblem", "infeasible_controls",
+    "clear_goal_state_batch", "set_constraint_params_batch", "set_constraint_limits_batch", "get_constraint_limits_batch",
+    "clear_constraint_limits_batch", "set_bounds_batch", "InfeasibleModel", "InfeasibleConstraint", "InfeasibleProblem", "infeasible_controls",
     "DoubleIntegrator", "Cartpole", "Quadrotor", "DiscreteMap", "LinearMap", "ModelVector", "HybridDoubleIntegrator", "pad_cost", "dims", "RK4", "RK3", "Euler",
     "DiagonalCost", "QuadraticCost", "LQRCost", "DiagonalQuatCost", "ErrorQuadratic", "QuatLQRCost",
     "Objective", "LQRObjective", "TrackingObjective",
@@ -1617,6 +1618,84 @@ def set_constraint_params_batch(prob, con_id, params):
     if par.shape != (prob.B, con.p):
         raise DimensionMismatch(f"params must be [B, p] = {(prob.B, con.p)}; got {par.shape}")
     prob._call("set_constraint_params_batch", int(con_id), prob._pd(par))
+
+
+def _need_constraint_limits_batch(prob):
+    if "set_constraint_limits_batch" not in prob._lib._fn:
+        raise UnsupportedError("per-trajectory constraint limits need a HIP library that exports to_set_constraint_limits_batch "
+                               "(the CPU oracle shares every limit among the trajectories of a problem)")
+
+
+def _limits_q(prob, con_id):
+    """Values per trajectory of constraint ``con_id``'s limits: p for a BoundConstraint, 1 for a second-order-cone NormConstraint; None for
+    every other kind (the library refuses those by name)."""
+    con = prob.constraints.constraints[con_id]
+    if con.kind == capi.CON_BOUND:
+        return con.p
+    if con.kind == capi.CON_NORM and isinstance(con.sense(), SecondOrderCone):
+        return 1
+    return None
+
+
+def set_constraint_limits_batch(prob, con_id, limits):
+    """One set of limits per TRAJECTORY for constraint ``con_id`` (0-based position in the ConstraintList; to_set_constraint_limits_batch).
+    A BoundConstraint (StateBound / ControlBound / IndexedConstraint-wrapped ones included): ``limits`` [B, p], the values of its finite rows
+    in row order [x_max..., u_max..., x_min..., u_min...] (``set_bounds_batch`` takes them by name).  A NormConstraint with
+    SecondOrderCone(): ``limits`` [B, 1] (or [B]), the value a_b.  X, U, duals and gains stay as they are."""
+    _need_constraint_limits_batch(prob)
+    q = _limits_q(prob, con_id)
+    lim = np.asarray(limits, dtype=np.float64)
+    if q == 1 and lim.ndim == 1:
+        lim = lim[:, None]
+    if q is not None and lim.shape != (prob.B, q):
+        raise DimensionMismatch(f"limits must be [B, q] = {(prob.B, q)}; got {lim.shape}")
+    if q is None:  # the library names the two supported kinds
+        lim = np.zeros((prob.B, 1))
+    prob._call("set_constraint_limits_batch", int(con_id), prob._pd(np.ascontiguousarray(lim)))
+
+
+def get_constraint_limits_batch(prob, con_id):
+    """[B, q]: the limits every trajectory's constraint ``con_id`` is evaluated with (to_get_constraint_limits_batch; the descriptor's,
+    repeated, if none are set)."""
+    _need_constraint_limits_batch(prob)
+    q = _limits_q(prob, con_id)
+    lim = np.empty((prob.B, q if q is not None else 1))
+    prob._call("get_constraint_limits_batch", int(con_id), prob._pd(lim))
+    return lim
+
+
+def clear_constraint_limits_batch(prob):
+    """Every constraint back to the limits of its descriptor (to_clear_constraint_limits_batch)."""
+    _need_constraint_limits_batch(prob)
+    prob._call("clear_constraint_limits_batch")
+
+
+def set_bounds_batch(prob, con_id, x_max=None, x_min=None, u_max=None, u_min=None):
+    """Bounds per TRAJECTORY for the BoundConstraint ``con_id`` by name: ``x_max`` / ``x_min`` [B, n], ``u_max`` / ``u_min`` [B, m]; a bound
+    left out keeps the constraint's own values for every trajectory.  Which entries are finite must be the constraint's for every
+    trajectory — the number of rows p cannot change per trajectory — else ArgumentError."""
+    _need_constraint_limits_batch(prob)
+    con = prob.constraints.constraints[con_id]
+    if con.kind != capi.CON_BOUND:
+        raise ArgumentError(f"set_bounds_batch: constraint {con_id} is a {type(con).__name__}, not a BoundConstraint")
+    n, m, B = prob.n, prob.m, prob.B
+    par = np.asarray(con._fill()[1], dtype=np.float64)  # the lowered descriptor: [z_max; z_min] over the problem's [x; u]
+    zmax, zmin = np.tile(par[: n + m], (B, 1)), np.tile(par[n + m:], (B, 1))
+    for name, val, dst, lo, k in (("x_max", x_max, zmax, 0, n), ("u_max", u_max, zmax, n, m), ("x_min", x_min, zmin, 0, n), ("u_min", u_min, zmin, n, m)):
+        if val is None:
+            continue
+        val = np.asarray(val, dtype=np.float64)
+        if val.shape != (B, k):
+            raise DimensionMismatch(f"{name} must be {(B, k)}; got {val.shape}")
+        dst[:, lo:lo + k] = val
+    for name, z, ref in (("upper", zmax, par[: n + m]), ("lower", zmin, par[n + m:])):
+        bad = np.isfinite(z) != np.isfinite(ref)[None, :]
+        if bad.any():
+            b, j = np.argwhere(bad)[0]
+            raise ArgumentError(f"set_bounds_batch: the {name} bound of entry {int(j) + 1} of [x; u] is {'finite' if np.isfinite(z[b, j]) else 'infinite'} for "
+                                f"trajectory {int(b)} and {'finite' if np.isfinite(ref[j]) else 'infinite'} in the constraint: p cannot change per trajectory")
+    rows = np.concatenate([zmax[:, np.isfinite(par[: n + m])], zmin[:, np.isfinite(par[n + m:])]], axis=1)
+    set_constraint_limits_batch(prob, con_id, rows)
 
 
 def clear_goal_state_batch(prob):

@@ -130,9 +130,11 @@ __device__ __forceinline__ double* slot_ptr(double* nominal, double* cand, const
 // lam0 / mu0: this lane's pointers to dual row 0 / penalty 0 (tiled arrays).
 // GEN = false: no dense QuadraticCost and no non-selector constraint in the tables (those branches are compiled out)
 // gl0: this lane's pointer into DevProblem::gl (per-trajectory linear cost terms; nullptr: none)
+// cp0 / cl0: this lane's pointers into DevProblem::cp / cl (per-trajectory constraint parameters / limits; general variants only)
 template <class M, bool GEN = true>
 __device__ __forceinline__ double knot_cost(const DevProblem& P, int k, const double* x, const double* u, const double* lam0,
-                                            const double* mu0, bool with_al, const double* gl0 = nullptr, const double* cp0 = nullptr) {
+                                            const double* mu0, bool with_al, const double* gl0 = nullptr, const double* cp0 = nullptr,
+                                            const double* cl0 = nullptr) {
   constexpr int n = M::n, m = M::m, nz = n + m;
   const int cidx = P.cost_index[k];
   double Jk = cost_eval<n, m, GEN>(P.costs[cidx], x, u);
@@ -156,7 +158,7 @@ __device__ __forceinline__ double knot_cost(const DevProblem& P, int k, const do
 #pragma unroll
         for (int i = 0; i < nz; ++i) zc[i] = z[i];
         con_shift<nz>(P, K, cp0, zc);
-        Ja += al_term<n, m, GEN>(K, zc, lam, (size_t)64, EL(mu0, ci));
+        Ja += al_term<n, m, GEN>(K, zc, lam, (size_t)64, EL(mu0, ci), cl0);
       } else
       Ja += al_term<n, m, GEN>(K, z, lam, (size_t)64, EL(mu0, ci));
     }
@@ -170,7 +172,8 @@ __device__ __forceinline__ double knot_cost(const DevProblem& P, int k, const do
 // descriptor-table path.  Terms are summed in constraint order, like knot_al.
 template <class M, bool GEN, class CS>
 __device__ __forceinline__ double knot_al_cached(const DevProblem& P, int k, const double* x, const double* u, const double* lam0,
-                                                 const double* mu0, int ncs, const CS& c0, const CS& c1, const double* cp0 = nullptr) {
+                                                 const double* mu0, int ncs, const CS& c0, const CS& c1, const double* cp0 = nullptr,
+                                                 const double* cl0 = nullptr) {
   constexpr int n = M::n, m = M::m, nz = n + m;
   double Ja = 0.0;
   for (int ci = 0; ci < P.n_cons; ++ci) {
@@ -184,7 +187,10 @@ __device__ __forceinline__ double knot_al_cached(const DevProblem& P, int k, con
 #pragma unroll
     for (int i = 0; i < m; ++i) z[n + i] = u[i];
     const double* lam = lam0 + (size_t)(K.dual_off + (long long)(k - K.k1) * K.p) * 64;
-    if constexpr (GEN) con_shift<nz>(P, K, cp0, z);  // (z is rebuilt for every table constraint)
+    if constexpr (GEN) {
+      con_shift<nz>(P, K, cp0, z);  // (z is rebuilt for every table constraint)
+      Ja += al_term<n, m, GEN>(K, z, lam, (size_t)64, EL(mu0, ci), cl0);
+    } else
     Ja += al_term<n, m, GEN>(K, z, lam, (size_t)64, EL(mu0, ci));
   }
   return Ja;
@@ -209,7 +215,8 @@ __device__ __forceinline__ double knot_al(const DevProblem& P, int k, const doub
 }
 
 template <class M>
-__device__ __forceinline__ double knot_violation(const DevProblem& P, int k, const double* x, const double* u, const double* cp0 = nullptr) {
+__device__ __forceinline__ double knot_violation(const DevProblem& P, int k, const double* x, const double* u, const double* cp0 = nullptr,
+                                                 const double* cl0 = nullptr) {
   constexpr int n = M::n, m = M::m, nz = n + m;
   double z[nz];
 #pragma unroll
@@ -224,7 +231,7 @@ __device__ __forceinline__ double knot_violation(const DevProblem& P, int k, con
 #pragma unroll
     for (int i = 0; i < nz; ++i) zc[i] = z[i];
     con_shift<nz>(P, K, cp0, zc);
-    const double v = con_violation<nz>(K, zc);
+    const double v = con_violation<nz>(K, zc, cl0);
     if (!(v <= vmax)) vmax = v;
   }
   return vmax;
@@ -242,6 +249,7 @@ __device__ __forceinline__ void trajectory_pass(const KArgs& a, int tile, int la
   double* lam0 = TILE_PTR(a.lam, P.n_duals);
   double* mu0 = TILE_PTR(a.mu, P.n_cons);
   const double* cp0 = TILE_PTR(P.cp, P.n_cp);
+  const double* cl0 = TILE_PTR(P.cl, P.n_cl);
   double J = 0.0, cmax = 0.0;
   for (int k = 0; k < N; ++k) {
     double x[n], u[m];
@@ -263,11 +271,11 @@ __device__ __forceinline__ void trajectory_pass(const KArgs& a, int tile, int la
 #pragma unroll
         for (int i = 0; i < nz; ++i) zc[i] = z[i];
         con_shift<nz>(P, K, cp0, zc);
-        con_dual_update<nz>(K, zc, lam, (size_t)64, EL(mu0, ci), P.opts.dual_max);
+        con_dual_update<nz>(K, zc, lam, (size_t)64, EL(mu0, ci), P.opts.dual_max, cl0);
       }
     }
-    if (cmax_out && P.n_cons > 0) { const double v = knot_violation<M>(P, k, x, u, cp0); if (!(v <= cmax)) cmax = v; }
-    if (J_out) J += knot_cost<M>(P, k, x, u, lam0, mu0, with_al, TILE_PTR(P.gl, P.n_costs * nz), cp0);
+    if (cmax_out && P.n_cons > 0) { const double v = knot_violation<M>(P, k, x, u, cp0, cl0); if (!(v <= cmax)) cmax = v; }
+    if (J_out) J += knot_cost<M>(P, k, x, u, lam0, mu0, with_al, TILE_PTR(P.gl, P.n_costs * nz), cp0, cl0);
   }
   if (J_out) *J_out = J;
   if (cmax_out) *cmax_out = cmax;

@@ -123,6 +123,7 @@ inline int validate_constraint(int n, int m, int N, const to_constraint_desc& d,
   std::memset(&ci, 0, sizeof(ci));
   ci.d = d;
   ci.cp_off = -1;  // shared parameters (to_set_constraint_params_batch flags a constraint later)
+  ci.cl_off = -1;  // shared limits (to_set_constraint_limits_batch)
   if (d.k_first < 1 || d.k_last > N || d.k_first > d.k_last)
     return fail(TO_ERR_ASSERTION, "Invalid inds, inds[end] must be less than number of knotpoints");  // src/constraint_list.jl:112
   if (d.n_inds < 0 || d.n_inds > TO_MAX_CON_INDS || d.n_params < 0 || d.n_params > TO_MAX_CON_PARAMS)
@@ -213,6 +214,48 @@ inline int validate_constraint(int n, int m, int N, const to_constraint_desc& d,
   ci.p = p; ci.k1 = d.k_first - 1; ci.k2 = d.k_last - 1;
   *out = ci;
   return TO_OK;
+}
+
+// Per-trajectory limits of a selector constraint (to_set_constraint_limits_batch).  constraint_limits_q: the number of values per
+// trajectory — p for a BoundConstraint (one per finite row, in row order), 1 for a second-order-cone NormConstraint (the value of its last
+// row) — or the refusal for every other kind.  lower_constraint_limits: limits[q, B] -> the values of soff[r] for every row, rows[p, B]
+// (what DevProblem::cl holds), with the checks the reference's constructors make on a single constraint, for every trajectory.
+inline int constraint_limits_q(const DevCon& ci, int* q) {
+  if (ci.d.kind == TO_CON_BOUND) { *q = ci.p; return TO_OK; }
+  if (ci.d.kind == TO_CON_NORM && ci.d.sense == TO_CONE_SECOND_ORDER) { *q = 1; return TO_OK; }
+  return fail(TO_ERR_UNSUPPORTED, "per-trajectory constraint limits: BoundConstraint (its bounds) and NormConstraint with SecondOrderCone (its value) only");
+}
+inline int lower_constraint_limits(const DevCon& ci, int B, const double* limits, std::vector<double>* rows) {
+  int q = 0;
+  if (int r = constraint_limits_q(ci, &q)) return r;
+  const int p = ci.p;
+  for (int b = 0; b < B; ++b)
+    for (int i = 0; i < q; ++i)
+      if (!std::isfinite(limits[i + (size_t)q * b]))
+        return fail(TO_ERR_ARGUMENT, "to_set_constraint_limits_batch: value " + std::to_string(i) + " of trajectory " + std::to_string(b) + " is not finite");
+  rows->assign((size_t)p * B, 0.0);
+  if (ci.d.kind == TO_CON_BOUND) {
+    for (int b = 0; b < B; ++b) {
+      const double* lb = limits + (size_t)p * b;
+      for (int r = 0; r < p; ++r) {
+        if (ci.ssgn[r] > 0.0)  // an upper row: against the lower row of the same coordinate, if there is one
+          for (int s = 0; s < p; ++s)
+            if (ci.ssgn[s] < 0.0 && ci.sidx[s] == ci.sidx[r] && !(lb[r] >= lb[s]))
+              return fail(TO_ERR_ARGUMENT, "Upper bounds must be greater than or equal to lower bounds (trajectory " + std::to_string(b) + ")");  // src/constraints.jl:712
+        (*rows)[r + (size_t)p * b] = lb[r];
+      }
+    }
+  } else {
+    for (int b = 0; b < B; ++b) {
+      if (!(limits[b] >= 0)) return fail(TO_ERR_ASSERTION, "Value must be greater than or equal to zero (trajectory " + std::to_string(b) + ")");  // src/constraints.jl:451
+      (*rows)[(p - 1) + (size_t)p * b] = limits[b];  // (rows r < p - 1 select a coordinate: offset 0)
+    }
+  }
+  return TO_OK;
+}
+// the descriptor's own limits in the layout of the setter's argument (what the getter reports for a constraint on shared limits)
+inline void shared_constraint_limits(const DevCon& ci, int q, double* out) {
+  for (int i = 0; i < q; ++i) out[i] = ci.soff[q == 1 && ci.d.kind == TO_CON_NORM ? ci.p - 1 : i];
 }
 
 // rot: attitude representation of the model's state (to_rotation), -1 for vector-space models

@@ -81,6 +81,9 @@ struct to_handle_s {
   double* d_pm = nullptr;   // per-trajectory model parameters (DevProblem::pm), tiled, L = 16, one spare tile; allocated on first use
   std::vector<double> pm_host;  // [16, B] host copy of what to_set_model_params_batch was given (empty: shared parameters)
   double* d_cp = nullptr;   // per-trajectory constraint parameters (DevProblem::cp), tiled, L = (n + m) * number of constraints; allocated on first use
+  double* d_cl = nullptr;   // per-trajectory constraint limits (DevProblem::cl), tiled, L = n_cl = summed p of the constraints, one spare tile; allocated on first use
+  std::vector<int> cl_base;                 // [n_cons] first row of constraint i's block in d_cl
+  std::vector<std::vector<double>> cl_host; // [n_cons] limits[q, B] as to_set_constraint_limits_batch was given them (empty: shared limits)
   double* d_tmp = nullptr;  // [Bp] scratch for reductions / outputs
   double* d_tmp2 = nullptr;
   // multi-GPU: RCCL communicator of the batch shards (to_comm_*; librccl is dlopen'ed on first use)

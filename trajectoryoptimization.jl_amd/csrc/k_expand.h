@@ -137,7 +137,8 @@ __device__ __forceinline__ void expand_knot(const KArgs& a, int gtile, int lane,
 #pragma unroll
           for (int i = 0; i < nz; ++i) zc[i] = z[i];
           con_shift<nz>(P, K, P.cp + ((size_t)tile * (size_t)P.n_cp) * 64 + lane64, zc);
-          al_grad_hvp<n, m, true>(K, zc, lam, (size_t)64, EL(mu0, ci), v, gr, y, P.opts.al_full_newton != 0);
+          al_grad_hvp<n, m, true>(K, zc, lam, (size_t)64, EL(mu0, ci), v, gr, y, P.opts.al_full_newton != 0,
+                                  P.cl + ((size_t)tile * (size_t)P.n_cl) * 64 + lane64);  // ... and limits (DevProblem::cl)
         } else
         al_grad_hvp<n, m, (VAR & 4) != 0>(K, z, lam, (size_t)64, EL(mu0, ci), v, gr, y, P.opts.al_full_newton != 0);
       }
@@ -322,7 +323,8 @@ __global__ void __launch_bounds__(64, TO_EXPAND_WAVES) k_expand(KArgs a) {
   if constexpr ((VAR & 2) != 0) {
     for (int ci = 0; ci < P.n_cons; ++ci) {
       ConC& K = P.cons[ci];
-      if (K.fast == 2 && K.p <= m + 1 && ce1.ci < 0) { if (ce0.ci < 0) ce0.load(K, ci); else ce1.load(K, ci); }
+      // (a constraint with per-trajectory limits stays out of the registers, whose soff is wave-uniform: it takes the table path)
+      if (K.fast == 2 && K.p <= m + 1 && ce1.ci < 0 && !((VAR & 4) != 0 && K.cl_off >= 0)) { if (ce0.ci < 0) ce0.load(K, ci); else ce1.load(K, ci); }
       else if (K.k1 <= k0 + KC - 1 && K.k2 >= k0) table_cons = true;
     }
   }
@@ -479,7 +481,8 @@ __device__ __forceinline__ void expand_lane_knot(const KArgs& a, int tile, int l
 #pragma unroll
           for (int i = 0; i < nz; ++i) zc[i] = z[i];
           con_shift<nz>(P, K, P.cp + ((size_t)tile * (size_t)P.n_cp) * 64 + lane, zc);
-          al_grad_hvp<n, m, true>(K, zc, lam, (size_t)64, EL(mu0, ci), v, gr, y, P.opts.al_full_newton != 0);
+          al_grad_hvp<n, m, true>(K, zc, lam, (size_t)64, EL(mu0, ci), v, gr, y, P.opts.al_full_newton != 0,
+                                  P.cl + ((size_t)tile * (size_t)P.n_cl) * 64 + lane);  // ... and limits (DevProblem::cl)
         } else
         al_grad_hvp<n, m, (VAR & 4) != 0>(K, z, lam, (size_t)64, EL(mu0, ci), v, gr, y, P.opts.al_full_newton != 0);
       }

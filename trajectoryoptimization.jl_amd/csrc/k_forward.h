@@ -109,6 +109,7 @@ __device__ __forceinline__ void forward_candidate(const KArgs& a, int tile, int 
   const bool has_gl = P.gl != nullptr;  // wave-uniform (a kernel argument): the branches on it are scalar
   const double* gl0 = TILE_PTR(P.gl, P.n_costs * (n + m));
   const double* cp0 = TILE_PTR(P.cp, P.n_cp);  // per-trajectory constraint parameters (general variants)
+  const double* cl0 = TILE_PTR(P.cl, P.n_cl);  // ... and limits
   const int ci0 = P.cost_index[0];
   double h0 = 0.0;
   if constexpr (SIMPLE) {
@@ -123,7 +124,8 @@ __device__ __forceinline__ void forward_candidate(const KArgs& a, int tile, int 
   if constexpr (CONS) {
     for (int ci = 0; ci < P.n_cons; ++ci) {
       ConC& K = P.cons[ci];
-      if (K.fast == 2 && K.k1 == 0 && K.k2 >= N - 2 && K.p <= m + 1 && ncs < 2) {
+      // (a constraint with per-trajectory limits stays out of the register cache, whose soff is wave-uniform: it takes the table path)
+      if (K.fast == 2 && K.k1 == 0 && K.k2 >= N - 2 && K.p <= m + 1 && ncs < 2 && !(GEN && K.cl_off >= 0)) {
         if (ncs == 0) cs0.load(K, ci, lam0, mu0); else cs1.load(K, ci, lam0, mu0);
         ++ncs;
       } else if (K.k1 <= N - 2) ++uncached;  // applies to some stage knot: needs the descriptor-table path
@@ -196,7 +198,7 @@ __device__ __forceinline__ void forward_candidate(const KArgs& a, int tile, int 
         if (ncs > 0) Ja += cs0.term(ub);
         if (ncs > 1) Ja += cs1.term(ub);
         Jk += Ja;
-      } else Jk += knot_al_cached<M, GEN>(P, k, xb, ub, lam0, mu0, ncs, cs0, cs1, cp0);
+      } else Jk += knot_al_cached<M, GEN>(P, k, xb, ub, lam0, mu0, ncs, cs0, cs1, cp0, cl0);
     }
     J += Jk;
     model_step<M, double, (MODE & 4) ? INTEG_RK4 : -1>(mp, integrator, k, xb, ub, h, xn);
@@ -218,7 +220,7 @@ __device__ __forceinline__ void forward_candidate(const KArgs& a, int tile, int 
     double u0[m];
 #pragma unroll
     for (int j = 0; j < m; ++j) u0[j] = 0.0;
-    J += knot_cost<M, GEN>(P, N - 1, xb, u0, lam0, mu0, true, gl0, cp0);
+    J += knot_cost<M, GEN>(P, N - 1, xb, u0, lam0, mu0, true, gl0, cp0, cl0);
   }
   if constexpr (KLDS) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // no DMA may still be in flight when the next pass refills the buffers
   J_out = J; g_out = gsum / (N - 1); ok_out = ok;
@@ -740,6 +742,7 @@ __device__ __forceinline__ void fwd2_account(const KArgs& a, int tile, int lane,
   const bool has_gl = P.gl != nullptr;  // wave-uniform (a kernel argument): the branches on it are scalar
   const double* gl0 = TILE_PTR(P.gl, P.n_costs * (n + m));
   const double* cp0 = TILE_PTR(P.cp, P.n_cp);  // per-trajectory constraint parameters (general variants)
+  const double* cl0 = TILE_PTR(P.cl, P.n_cl);  // ... and limits
   const int ci0 = P.cost_index[0];
   double h0 = 0.0;
   if constexpr (SIMPLE) {
@@ -753,7 +756,8 @@ __device__ __forceinline__ void fwd2_account(const KArgs& a, int tile, int lane,
   if constexpr (CONS) {
     for (int ci = 0; ci < P.n_cons; ++ci) {
       ConC& K = P.cons[ci];
-      if (K.fast == 2 && K.k1 == 0 && K.k2 >= N - 2 && K.p <= m + 1 && ncs < 2) {
+      // (a constraint with per-trajectory limits stays out of the register cache, whose soff is wave-uniform: it takes the table path)
+      if (K.fast == 2 && K.k1 == 0 && K.k2 >= N - 2 && K.p <= m + 1 && ncs < 2 && !(GEN && K.cl_off >= 0)) {
         if (ncs == 0) cs0.load(K, ci, lam0, mu0); else cs1.load(K, ci, lam0, mu0);
         ++ncs;
       } else if (K.k1 <= N - 2) ++uncached;
@@ -801,7 +805,7 @@ __device__ __forceinline__ void fwd2_account(const KArgs& a, int tile, int lane,
         if (ncs > 0) Ja += cs0.term(ub);
         if (ncs > 1) Ja += cs1.term(ub);
         Jk += Ja;
-      } else Jk += knot_al_cached<M, GEN>(P, k, xb, ub, lam0, mu0, ncs, cs0, cs1, cp0);
+      } else Jk += knot_al_cached<M, GEN>(P, k, xb, ub, lam0, mu0, ncs, cs0, cs1, cp0, cl0);
     }
     J += Jk;
     // admissibility (k_forward checks x_{k+1} and u_k in iteration k: the same set of values, seen one knot later here)
@@ -829,7 +833,7 @@ __device__ __forceinline__ void fwd2_account(const KArgs& a, int tile, int lane,
     double u0[m];
 #pragma unroll
     for (int j = 0; j < m; ++j) u0[j] = 0.0;
-    J += knot_cost<M, GEN>(P, N - 1, xb, u0, lam0, mu0, true, gl0, cp0);
+    J += knot_cost<M, GEN>(P, N - 1, xb, u0, lam0, mu0, true, gl0, cp0, cl0);
   }
   J_out = J; g_out = gsum / (N - 1); ok_out = ok;
 }

@@ -125,7 +125,7 @@ __global__ void __launch_bounds__(64) k_outer_violation(KArgs a) {
   for (int i = 0; i < n; ++i) x[i] = EL(X, k * n + i);
 #pragma unroll
   for (int i = 0; i < m; ++i) u[i] = (k < N - 1) ? EL(U, k * m + i) : 0.0;
-  EL(TILE_PTR(a.knotbuf, N), k) = (P.n_cons > 0) ? knot_violation<M>(P, k, x, u, TILE_PTR(P.cp, P.n_cp)) : 0.0;
+  EL(TILE_PTR(a.knotbuf, N), k) = (P.n_cons > 0) ? knot_violation<M>(P, k, x, u, TILE_PTR(P.cp, P.n_cp), TILE_PTR(P.cl, P.n_cl)) : 0.0;
 }
 
 template <class M>
@@ -181,9 +181,9 @@ __global__ void __launch_bounds__(64) k_outer_update(KArgs a) {
 #pragma unroll
     for (int i = 0; i < nz; ++i) zc[i] = z[i];
     con_shift<nz>(P, K, TILE_PTR(P.cp, P.n_cp), zc);
-    con_dual_update<nz>(K, zc, lam, (size_t)64, EL(mu0, ci), P.opts.dual_max);
+    con_dual_update<nz>(K, zc, lam, (size_t)64, EL(mu0, ci), P.opts.dual_max, TILE_PTR(P.cl, P.n_cl));
   }
-  EL(TILE_PTR(a.knotbuf, N), k) = knot_cost<M>(P, k, x, u, lam0, mn0, true, TILE_PTR(P.gl, P.n_costs * nz), TILE_PTR(P.cp, P.n_cp));
+  EL(TILE_PTR(a.knotbuf, N), k) = knot_cost<M>(P, k, x, u, lam0, mn0, true, TILE_PTR(P.gl, P.n_costs * nz), TILE_PTR(P.cp, P.n_cp), TILE_PTR(P.cl, P.n_cl));
 }
 
 template <class M>
@@ -293,7 +293,7 @@ __global__ void __launch_bounds__(64) k_constraint_eval(KArgs a, int ci, double*
   double coef[nz];
   for (int r = 0; r < p; ++r) {
     double cval;
-    if (K.selector) cval = sel_row<nz>(K, z, r); else cval = con_row<nz>(K, z, r, coef);
+    if (K.selector) cval = sel_row<nz>(K, z, r, TILE_PTR(P.cl, P.n_cl)); else cval = con_row<nz>(K, z, r, coef);
     if (vals) vals[(size_t)r + p * kb] = cval;
     if (jac) {
       for (int col = 0; col < w; ++col) {

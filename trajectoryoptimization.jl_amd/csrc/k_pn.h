@@ -140,8 +140,14 @@ PN_FN const double* pn_cp0(const DevProblem& P, const double* w) {
   const int b = (int)w[PN_H_TRAJ];
   return P.cp + ((size_t)(b >> 6) * (size_t)P.n_cp) * 64 + (b & 63);
 }
+// ... and into DevProblem::cl (per-trajectory constraint limits); a constraint is flagged only while cl is set
+PN_FN const double* pn_cl0(const DevProblem& P, const double* w) {
+  if (!P.cl) return nullptr;
+  const int b = (int)w[PN_H_TRAJ];
+  return P.cl + ((size_t)(b >> 6) * (size_t)P.n_cl) * 64 + (b & 63);
+}
 template <class M, bool GRAD, class Fn>
-PN_FN void pn_for_candidates(const DevProblem& P, int k, const double* zin, const double* cp0, Fn&& f) {
+PN_FN void pn_for_candidates(const DevProblem& P, int k, const double* zin, const double* cp0, const double* cl0, Fn&& f) {
   constexpr int nz = M::n + M::m;
   int qi = 0;
   double gz[nz], coef[nz], z[nz];
@@ -153,12 +159,12 @@ PN_FN void pn_for_candidates(const DevProblem& P, int k, const double* zin, cons
     const int p = K.p;
     if (K.d.sense == TO_CONE_SECOND_ORDER) {
       double a2 = 0.0;
-      for (int r = 0; r < p - 1; ++r) { const double c = sel_row<nz>(K, z, r); a2 += c * c; }
-      const double a = sqrt(a2), s = sel_row<nz>(K, z, p - 1);
+      for (int r = 0; r < p - 1; ++r) { const double c = sel_row<nz>(K, z, r, cl0); a2 += c * c; }
+      const double a = sqrt(a2), s = sel_row<nz>(K, z, p - 1, cl0);
       if (GRAD) {
         for (int j = 0; j < nz; ++j) gz[j] = 0.0;
         if (a > 0.0)
-          for (int r = 0; r < p - 1; ++r) { const int j = K.sidx[r]; if (j >= 0) gz[j] += (sel_row<nz>(K, z, r) / a) * K.ssgn[r]; }
+          for (int r = 0; r < p - 1; ++r) { const int j = K.sidx[r]; if (j >= 0) gz[j] += (sel_row<nz>(K, z, r, cl0) / a) * K.ssgn[r]; }
         const int js = K.sidx[p - 1];
         if (js >= 0) gz[js] -= K.ssgn[p - 1];
       }
@@ -167,7 +173,7 @@ PN_FN void pn_for_candidates(const DevProblem& P, int k, const double* zin, cons
     } else if (K.selector) {
       for (int r = 0; r < p; ++r) {
         if (GRAD) { for (int j = 0; j < nz; ++j) gz[j] = 0.0; const int j = K.sidx[r]; if (j >= 0) gz[j] = K.ssgn[r]; }
-        f(qi, sel_row<nz>(K, z, r), gz, K.d.sense == TO_CONE_ZERO);
+        f(qi, sel_row<nz>(K, z, r, cl0), gz, K.d.sense == TO_CONE_ZERO);
         ++qi;
       }
     } else {
@@ -312,7 +318,7 @@ PN_FN double pn_eval(const PnArgs& q, double* w, const PnLds& L, const double* x
     int na = 0;
     const bool terminal = (k == N - 1);
     if (refresh) {
-      pn_for_candidates<M, true>(P, k, z, pn_cp0(P, w), [&](int qi, double val, const double* gz, bool eq) {
+      pn_for_candidates<M, true>(P, k, z, pn_cp0(P, w), pn_cl0(P, w), [&](int qi, double val, const double* gz, bool eq) {
         if (!(eq || val >= -tol_a)) return;
         double ge[nc], g2 = 0.0;
         pn_project_row<M>(z, gz, terminal, ge);
@@ -323,7 +329,7 @@ PN_FN double pn_eval(const PnArgs& q, double* w, const PnLds& L, const double* x
       });
       *R.mask = mask;
     } else {
-      pn_for_candidates<M, false>(P, k, z, pn_cp0(P, w), [&](int qi, double val, const double*, bool) {
+      pn_for_candidates<M, false>(P, k, z, pn_cp0(P, w), pn_cl0(P, w), [&](int qi, double val, const double*, bool) {
         if (!(mask >> qi & 1ull)) return;
         dst[ne + na++] = val; pn_upd_max(mx, fabs(val));
       });
@@ -391,7 +397,7 @@ PN_FN void pn_lin_rows(const PnArgs& q, double* w, int k) {
   const bool terminal = (k == P.N - 1);
   const unsigned long long mask = *R.mask;
   int na = 0;
-  pn_for_candidates<M, true>(P, k, R.Z, pn_cp0(P, w), [&](int qi, double, const double* gz, bool) {
+  pn_for_candidates<M, true>(P, k, R.Z, pn_cp0(P, w), pn_cl0(P, w), [&](int qi, double, const double* gz, bool) {
     if (!(mask >> qi & 1ull)) return;
     pn_project_row<M>(R.Z, gz, terminal, R.C + (size_t)na * nc);
     ++na;
@@ -853,7 +859,7 @@ PN_FN void pn_begin(const PnArgs& q, int b, double* w, double* lds_mem, int roun
     double e[ne], mx = 0.0;
     pn_defect<M, PM>(P, k, zp, R.Z, x0, e, mp);
     for (int i = 0; i < ne; ++i) pn_upd_max(mx, fabs(e[i]));
-    if (P.n_cons > 0) pn_upd_max(mx, knot_violation<M>(P, k, R.Z, R.Z + n, pn_cp0(P, w)));
+    if (P.n_cons > 0) pn_upd_max(mx, knot_violation<M>(P, k, R.Z, R.Z + n, pn_cp0(P, w), pn_cl0(P, w)));
     R.loc[0] = mx;
   }
   PN_SYNC();

@@ -80,6 +80,7 @@ __global__ void __launch_bounds__(64) k_policy_rollout(KArgs a, PolicyArgs pa) {
   double* pUo = pa.Uw + ((size_t)blockIdx.x * (size_t)((N - 1) * m)) * 64 + hw;
   const double* gl0 = TILE_PTR(P.gl, P.n_costs * (n + m));
   const double* cp0 = TILE_PTR(P.cp, P.n_cp);
+  const double* cl0 = TILE_PTR(P.cl, P.n_cl);
   double mp[16];  // the PLANT's parameters; the law's x̄, ū, K, d are the planning model's
   if constexpr (LANE_PLANT) {
     const double* pp = pa.plants + c * 16;
@@ -154,7 +155,7 @@ __global__ void __launch_bounds__(64) k_policy_rollout(KArgs a, PolicyArgs pa) {
     }
     pUo += m * 64;
     J += knot_cost<M, true>(P, k, xb, ub, nullptr, nullptr, false, gl0, cp0);
-    if (has_cons) { const double v = knot_violation<M>(P, k, xb, ub, cp0); if (!(v <= cm)) cm = v; }
+    if (has_cons) { const double v = knot_violation<M>(P, k, xb, ub, cp0, cl0); if (!(v <= cm)) cm = v; }
     model_step<M, double, FI>(mp, integrator, k, xb, ub, P.dt[k], xn);
     if constexpr (NOISE_W) {  // x_{k+1} = state_add(f(x_k, u_k), w_k): no dt scaling; the limit test below sees the noisy state
       double w[ne], xf[n];
@@ -191,7 +192,7 @@ __global__ void __launch_bounds__(64) k_policy_rollout(KArgs a, PolicyArgs pa) {
 #pragma unroll
     for (int j = 0; j < m; ++j) u0[j] = 0.0;
     J += knot_cost<M, true>(P, N - 1, xb, u0, nullptr, nullptr, false, gl0, cp0);
-    if (has_cons) { const double v = knot_violation<M>(P, N - 1, xb, u0, cp0); if (!(v <= cm)) cm = v; }
+    if (has_cons) { const double v = knot_violation<M>(P, N - 1, xb, u0, cp0, cl0); if (!(v <= cm)) cm = v; }
   }
   if constexpr (KLDS) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   if (live) {

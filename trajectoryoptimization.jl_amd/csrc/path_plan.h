@@ -234,6 +234,23 @@ inline void path_report(const PathPlan& p, const PathTraits& t, int h_diag, int 
   info[7] = p.repack_block0 != 0 ? 1 : 0;                        // repacked last line-search round
   if (working_set_repack(p, t, plants) && B >= p.rp_min) info[7] |= 2;   // repacked working set (iLQR solves)
 }
+// What the cost and constraint tables of a handle say about the kernel variants it needs (trajopt_hip.hip upload_tables fills it whenever a cost, a
+// constraint or a per-trajectory array changes): DevProblem::expand_variant — bit0: a QuadraticCost / ErrorQuadratic exists; bit1: constraints exist;
+// bit2: the general variant — and whether the forward pass takes a general variant (forward_mode's `general`).  Per-trajectory constraint LIMITS
+// (con_limits: some constraint reads DevProblem::cl, to_set_constraint_limits_batch) route a handle exactly as per-trajectory constraint
+// PARAMETERS (con_params: DevProblem::cp) do: bit 2 forced — expansion variant 7, forward `mode | 8` — which rules out the scan kernel, the fused
+// cooperative kernel and the packed Quadrotor expansion; compaction, the fused lane kernel and the repacked working set stay as the plan has them
+// (the repacked set carries cl the way it carries cp, trajopt_hip.hip rp_setup).
+struct TableFlags {
+  bool dense_costs = false, cons = false, non_selector = false;  // from the descriptors
+  bool con_params = false, con_limits = false, plants = false;   // a constraint flagged for cp / for cl; DevProblem::pm set
+};
+inline int expand_variant_of(const TableFlags& f) {
+  return (f.dense_costs ? 1 : 0) | (f.cons ? 2 : 0) | ((f.non_selector || f.con_params || f.con_limits || f.plants) ? 4 : 0);
+}
+inline bool forward_general(int expand_variant, bool cost_terms /* gl */, bool con_params /* cp */, bool con_limits /* cl */) {
+  return (expand_variant & 5) != 0 || cost_terms || con_params || con_limits;
+}
 // Forward-pass kernel variant (k_forward.h MODE bits): bit0 simple stage cost, bit1 constraints, bit2 compile-time RK4 (models that
 // pin it), bit3 dense costs / generic constraints / per-trajectory terms, bit4 unit-SOC; `mask` holds the compiled ones.  -1: none fits.
 inline int forward_mode(bool simple_stage, bool has_cons, bool rk4, bool general, bool unit_soc, uint32_t mask) {

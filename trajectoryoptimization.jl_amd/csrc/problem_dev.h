@@ -7,6 +7,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <utility>
 
 #include "../../include/trajopt_hip.h"
@@ -24,6 +25,8 @@ struct DevCon {
   double soff[TO_MAX_P];
   int cp_off;               // >= 0: this constraint sees z = [x; u] shifted by the per-trajectory block DevProblem::cp[cp_off .. cp_off + n + m)
                             // (to_set_constraint_params_batch: one GoalConstraint target per trajectory); -1: shared parameters only
+  int cl_off;               // >= 0: a selector constraint whose soff[r] is read per trajectory from DevProblem::cl[cl_off + r], r < p
+                            // (to_set_constraint_limits_batch: one set of bounds / one cone value per trajectory); -1: shared limits only
 };
 
 // Read-only descriptor tables are addressed through the CONSTANT address space: with a wave-uniform address the
@@ -64,6 +67,13 @@ struct DevProblem {
   // sits at pm[((b >> 6) * 16 + i) * 64 + (b & 63)].  NULL (the default): every trajectory is planned on mp.  Read by the flagged (PM)
   // kernel instances only — the others keep mp wave-uniform in SGPRs and never look at this pointer.
   const double* pm;
+  // Per-trajectory constraint limits (to_set_constraint_limits_batch: the bounds of a BoundConstraint, the value of a second-order-cone
+  // NormConstraint, one set per trajectory): tiled array, L = n_cl = the summed p of every constraint; entry i of trajectory b sits at
+  // cl[((b >> 6) * n_cl + i) * 64 + (b & 63)].  The block of a flagged constraint (DevCon::cl_off) holds the values of soff[r] THEMSELVES: row r
+  // of trajectory b is ssgn[r] * (z - cl_b[r]), the expression a single-trajectory problem built with that limit evaluates.  A constraint is
+  // flagged only while cl is set.  NULL (the default): every trajectory shares the descriptors.  Read by the GENERAL kernel variants only.
+  const double* cl;
+  int n_cl;
 };
 
 // The 16 model parameters of trajectory b into registers (the flagged kernel instances, once, ahead of their knot loops): indexed by the
@@ -81,6 +91,15 @@ __device__ __forceinline__ void con_shift(const DevProblem& P, ConC& K, const do
 #pragma unroll
     for (int i = 0; i < nz; ++i) z[i] -= cp0[(size_t)(K.cp_off + i) * 64];
   }
+}
+
+// soff[r] of selector constraint K as this lane's trajectory sees it.  cl0: the lane's pointer to entry 0 of DevProblem::cl — indexed by the
+// TRAJECTORY, like load_plant — or nothing: the callers that pass no pointer (every kernel variant that is not a general one) compile to the
+// descriptor read they always had.  The branch is wave-uniform (K.cl_off is descriptor data), as con_shift's is.
+__device__ __forceinline__ double con_soff(ConC& K, int r, std::nullptr_t) { return K.soff[r]; }
+__device__ __forceinline__ double con_soff(ConC& K, int r, const double* cl0) {
+  if (K.cl_off >= 0) return cl0[(size_t)(K.cl_off + r) * 64];
+  return K.soff[r];
 }
 
 // cost of the per-trajectory linear terms of cost ci at (x, u), and their gradient (added to g); gl0 = this lane's pointer to entry 0
@@ -550,16 +569,18 @@ __device__ __forceinline__ void visit_rows(ConC& K, int D, F&& f) {
 }
 
 // value of row r of a selector constraint
-template <int nz>
-__device__ __forceinline__ double sel_row(ConC& K, const double* z, int r) {
+// (cl0, here and below: see con_soff)
+template <int nz, class L = std::nullptr_t>
+__device__ __forceinline__ double sel_row(ConC& K, const double* z, int r, L cl0 = nullptr) {
   const int j = K.sidx[r];
-  return j < 0 ? K.soff[r] : K.ssgn[r] * (pick<nz>(z, j) - K.soff[r]);
+  const double so = con_soff(K, r, cl0);
+  return j < 0 ? so : K.ssgn[r] * (pick<nz>(z, j) - so);
 }
 
 // AL penalty of one constraint at one knot.  lam: pointer to row 0 of this knot's duals
 // (batch-fastest: row r at lam[r*stride]).
-template <int n, int m, bool GENERIC = true>
-__device__ __forceinline__ double al_term(ConC& K, const double* z, const double* lam, size_t stride, double mu) {
+template <int n, int m, bool GENERIC = true, class L = std::nullptr_t>
+__device__ __forceinline__ double al_term(ConC& K, const double* z, const double* lam, size_t stride, double mu, L cl0 = nullptr) {
   constexpr int nz = n + m;
   const int p = K.p;
   double J = 0.0;
@@ -568,12 +589,12 @@ __device__ __forceinline__ double al_term(ConC& K, const double* z, const double
     double a2 = 0.0, l2 = 0.0;
     visit_rows<n, m>(K, p - 1, [&](int r, auto idx) {
       const double l = lam[r * stride];
-      const double lb = l - mu * (K.ssgn[r] * (zget<nz>(z, idx) - K.soff[r]));
+      const double lb = l - mu * (K.ssgn[r] * (zget<nz>(z, idx) - con_soff(K, r, cl0)));
       l2 += l * l;
       a2 += lb * lb;
     });
     const double ls = lam[(p - 1) * stride];
-    const double s = ls - mu * K.soff[p - 1];
+    const double s = ls - mu * con_soff(K, p - 1, cl0);
     l2 += ls * ls;
     const double a = sqrt(a2);
     double pn;
@@ -584,7 +605,7 @@ __device__ __forceinline__ double al_term(ConC& K, const double* z, const double
   } else if (K.selector) {
     const bool eq = (K.d.sense == TO_CONE_ZERO);
     visit_rows<n, m>(K, p, [&](int r, auto idx) {
-      const double l = lam[r * stride], c = K.ssgn[r] * (zget<nz>(z, idx) - K.soff[r]);
+      const double l = lam[r * stride], c = K.ssgn[r] * (zget<nz>(z, idx) - con_soff(K, r, cl0));
       const bool active = eq || (c >= 0.0) || (l > 0.0);
       J += l * c + (active ? 0.5 * mu * c * c : 0.0);
     });
@@ -723,21 +744,21 @@ __device__ __forceinline__ void con_curvature_v(ConC& K, int r, const double* z,
 
 // full_newton (to_solver_opts::al_full_newton): the Hessian-vector product also carries the constraint curvature
 // sum_r ybar_r d2c_r/dz2 v (non-selector constraints; selector rows are affine and the SOC closed forms are already exact).
-template <int n, int m, bool GENERIC = true, int REGROWS = 0>
+template <int n, int m, bool GENERIC = true, int REGROWS = 0, class L = std::nullptr_t>
 __device__ __forceinline__ void al_grad_hvp(ConC& K, const double* z, const double* lam, size_t stride_rt, double mu,
-                                            const double* v, double* g, double* y, bool full_newton = false) {
+                                            const double* v, double* g, double* y, bool full_newton = false, L cl0 = nullptr) {
   constexpr int nz = n + m;
   const size_t stride = REGROWS > 0 ? (size_t)1 : stride_rt;
   const int p = K.p;
   if (K.d.sense == TO_CONE_SECOND_ORDER) {
     double a2 = 0.0, lw = 0.0;  // lw = lb_v · w_v with w = ∇c v
     visit_rows<n, m, (REGROWS > 0)>(K, p - 1, [&](int r, auto idx) {
-      const double lb = lam[r * stride] - mu * (K.ssgn[r] * (zget<nz>(z, idx) - K.soff[r]));
+      const double lb = lam[r * stride] - mu * (K.ssgn[r] * (zget<nz>(z, idx) - con_soff(K, r, cl0)));
       a2 += lb * lb;
       lw += lb * (K.ssgn[r] * zget<nz>(v, idx));
     });
     const double llast = REGROWS > 0 ? pick<(REGROWS > 0 ? REGROWS : 1)>(lam, p - 1) : lam[(p - 1) * stride];
-    const double s = llast - mu * K.soff[p - 1];
+    const double s = llast - mu * con_soff(K, p - 1, cl0);
     const double a = sqrt(a2);
     if (a <= -s) return;  // Π = 0, ∇Π = 0
     const bool inside = (a <= s);
@@ -746,7 +767,7 @@ __device__ __forceinline__ void al_grad_hvp(ConC& K, const double* z, const doub
     const double k3 = inside ? 0.0 : (0.5 * s) * (ra * ra * ra);
     visit_rows<n, m, (REGROWS > 0)>(K, p - 1, [&](int r, auto idx) {
       const double sg = K.ssgn[r];
-      const double lb = lam[r * stride] - mu * (sg * (zget<nz>(z, idx) - K.soff[r]));
+      const double lb = lam[r * stride] - mu * (sg * (zget<nz>(z, idx) - con_soff(K, r, cl0)));
       zadd<nz>(g, idx, -sg * (cf * lb));                       // −∇c'Π(lb)
       const double w = sg * zget<nz>(v, idx);
       zadd<nz>(y, idx, mu * sg * (cf * w - k3 * lb * lw));     // µ ∇c' ∇Π(lb) ∇c v  (the s-row of ∇c is zero)
@@ -755,7 +776,7 @@ __device__ __forceinline__ void al_grad_hvp(ConC& K, const double* z, const doub
     const bool eq = (K.d.sense == TO_CONE_ZERO);
     visit_rows<n, m, (REGROWS > 0)>(K, p, [&](int r, auto idx) {
       const double sg = K.ssgn[r];
-      const double l = lam[r * stride], c = sg * (zget<nz>(z, idx) - K.soff[r]);
+      const double l = lam[r * stride], c = sg * (zget<nz>(z, idx) - con_soff(K, r, cl0));
       const bool active = eq || (c >= 0.0) || (l > 0.0);
       zadd<nz>(g, idx, sg * (l + (active ? mu * c : 0.0)));
       zadd<nz>(y, idx, active ? mu * zget<nz>(v, idx) : 0.0);
@@ -843,20 +864,20 @@ __device__ __forceinline__ void al_grad_hvp_ctrl(const ConExp<m>& C, const doubl
 }
 
 // max violation of one constraint at one knot
-template <int nz>
-__device__ __forceinline__ double con_violation(ConC& K, const double* z) {
+template <int nz, class L = std::nullptr_t>
+__device__ __forceinline__ double con_violation(ConC& K, const double* z, L cl0 = nullptr) {
   const int p = K.p;
   double vmax = 0.0;
   if (K.d.sense == TO_CONE_SECOND_ORDER) {
     double a2 = 0.0, s = 0.0;
-    for (int r = 0; r < p; ++r) { const double c = sel_row<nz>(K, z, r); if (r < p - 1) a2 += c * c; else s = c; }
+    for (int r = 0; r < p; ++r) { const double c = sel_row<nz>(K, z, r, cl0); if (r < p - 1) a2 += c * c; else s = c; }
     const double a = sqrt(a2);
-    if (a <= -s) { for (int r = 0; r < p; ++r) { const double v = fabs(sel_row<nz>(K, z, r)); if (!(v <= vmax)) vmax = v; } }
+    if (a <= -s) { for (int r = 0; r < p; ++r) { const double v = fabs(sel_row<nz>(K, z, r, cl0)); if (!(v <= vmax)) vmax = v; } }
     else if (a <= s) vmax = 0.0;
     else {
       const double cf = 0.5 * (1 + s / a);
       for (int r = 0; r < p; ++r) {
-        const double c = sel_row<nz>(K, z, r);
+        const double c = sel_row<nz>(K, z, r, cl0);
         const double pc = (r < p - 1) ? c * cf : a * cf;
         const double v = fabs(c - pc);
         if (!(v <= vmax)) vmax = v;
@@ -866,7 +887,7 @@ __device__ __forceinline__ double con_violation(ConC& K, const double* z) {
   }
   double coef[nz];
   for (int r = 0; r < p; ++r) {
-    const double c = K.selector ? sel_row<nz>(K, z, r) : con_row<nz>(K, z, r, coef);
+    const double c = K.selector ? sel_row<nz>(K, z, r, cl0) : con_row<nz>(K, z, r, coef);
     const double v = (K.d.sense == TO_CONE_ZERO) ? fabs(c) : fmax(0.0, c);
     if (!(v <= vmax)) vmax = v;
   }
@@ -874,15 +895,15 @@ __device__ __forceinline__ double con_violation(ConC& K, const double* z) {
 }
 
 // dual update of one constraint at one knot (lam in place)
-template <int nz>
-__device__ __forceinline__ void con_dual_update(ConC& K, const double* z, double* lam, size_t stride, double mu, double dual_max) {
+template <int nz, class L = std::nullptr_t>
+__device__ __forceinline__ void con_dual_update(ConC& K, const double* z, double* lam, size_t stride, double mu, double dual_max, L cl0 = nullptr) {
   const int p = K.p;
   if (K.d.sense == TO_CONE_SECOND_ORDER) {
     double a2 = 0.0, s = 0.0;
-    for (int r = 0; r < p; ++r) { const double lb = lam[r * stride] - mu * sel_row<nz>(K, z, r); if (r < p - 1) a2 += lb * lb; else s = lb; }
+    for (int r = 0; r < p; ++r) { const double lb = lam[r * stride] - mu * sel_row<nz>(K, z, r, cl0); if (r < p - 1) a2 += lb * lb; else s = lb; }
     const double a = sqrt(a2);
     for (int r = 0; r < p; ++r) {
-      const double lb = lam[r * stride] - mu * sel_row<nz>(K, z, r);
+      const double lb = lam[r * stride] - mu * sel_row<nz>(K, z, r, cl0);
       double out;
       if (a <= -s) out = 0.0;
       else if (a <= s) out = lb;
@@ -893,7 +914,7 @@ __device__ __forceinline__ void con_dual_update(ConC& K, const double* z, double
   }
   double coef[nz];
   for (int r = 0; r < p; ++r) {
-    const double c = K.selector ? sel_row<nz>(K, z, r) : con_row<nz>(K, z, r, coef);
+    const double c = K.selector ? sel_row<nz>(K, z, r, cl0) : con_row<nz>(K, z, r, coef);
     const double l = lam[r * stride] + mu * c;
     lam[r * stride] = (K.d.sense == TO_CONE_ZERO) ? fmax(-dual_max, fmin(dual_max, l)) : fmin(dual_max, fmax(0.0, l));
   }

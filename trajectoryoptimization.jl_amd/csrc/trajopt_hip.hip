@@ -231,12 +231,14 @@ int upload_tables(to_handle* h) {
     bool simple = k0 != TO_COST_QUADRATIC && k0 != TO_COST_ERROR_QUADRATIC;
     for (int k = 1; k < N - 1; ++k) simple = simple && h->cost_index[k] == h->cost_index[0] && h->dt[k] == h->dt[0];
     P.simple_stage = simple ? 1 : 0;
-    bool dense = false, generic = false;
-    for (const auto& c : h->costs) dense = dense || c.kind == TO_COST_QUADRATIC || c.kind == TO_COST_ERROR_QUADRATIC;
-    for (const auto& c : h->cons) generic = generic || !c.selector;
-    for (const auto& c : h->cons) generic = generic || c.cp_off >= 0;  // per-trajectory parameters are read by the general variants only
-    generic = generic || P.pm != nullptr;  // ... and per-trajectory model parameters by the flagged instances of the general variants only
-    P.expand_variant = (dense ? 1 : 0) | (h->cons.empty() ? 0 : 2) | (generic ? 4 : 0);
+    TableFlags tf;
+    for (const auto& c : h->costs) tf.dense_costs = tf.dense_costs || c.kind == TO_COST_QUADRATIC || c.kind == TO_COST_ERROR_QUADRATIC;
+    tf.cons = !h->cons.empty();
+    for (const auto& c : h->cons) {  // per-trajectory parameters / limits are read by the general variants only
+      tf.non_selector = tf.non_selector || !c.selector; tf.con_params = tf.con_params || c.cp_off >= 0; tf.con_limits = tf.con_limits || c.cl_off >= 0;
+    }
+    tf.plants = P.pm != nullptr;  // ... and per-trajectory model parameters by the flagged instances of the general variants only
+    P.expand_variant = expand_variant_of(tf);  // (path_plan.h)
     // unit-SOC forward-pass variants (problem_dev.h unit_soc_desc): at least one control-block constraint, and all of them unit
     bool any_ctrl = false, all_unit = true;
     for (const auto& c : h->cons)
@@ -244,7 +246,7 @@ int upload_tables(to_handle* h) {
         any_ctrl = true;
         const bool u = P.m == 1 ? unit_soc_desc<1>(c.d.sense, c.fast, c.p, c.ssgn, c.soff) : P.m == 2 ? unit_soc_desc<2>(c.d.sense, c.fast, c.p, c.ssgn, c.soff)
                      : P.m == 3 ? unit_soc_desc<3>(c.d.sense, c.fast, c.p, c.ssgn, c.soff) : unit_soc_desc<4>(c.d.sense, c.fast, c.p, c.ssgn, c.soff);
-        all_unit = all_unit && u;
+        all_unit = all_unit && u && c.cl_off < 0;  // (the UNIT variants hold the shared bound in an SGPR: not while the cone carries per-trajectory limits)
       }
     P.unit_soc = (any_ctrl && all_unit) ? 1 : 0;
     if (const char* env = std::getenv("TRAJOPT_UNIT_SOC")) if (!std::atoi(env)) P.unit_soc = 0;  // A/B knob
@@ -298,7 +300,7 @@ int launch_forward(to_handle* h, bool accept = true, bool two_wave = false) {
     if (accept) TRY(launch_accept(h));
     return TO_OK;
   }
-  const int mode = forward_mode(P.simple_stage, P.n_cons > 0, P.integrator == INTEG_RK4, (P.expand_variant & 5) || P.gl || P.cp, P.unit_soc, h->traits.forward);
+  const int mode = forward_mode(P.simple_stage, P.n_cons > 0, P.integrator == INTEG_RK4, forward_general(P.expand_variant, P.gl != nullptr, P.cp != nullptr, P.cl != nullptr), P.unit_soc, h->traits.forward);
   if (mode < 0) return fail(TO_ERR_UNSUPPORTED, "forward-pass variant not compiled for this model");
   if ((two_wave || h->plan.fwd2 == 1) && h->ops->forward2[mode]) TRY(h->ops->forward2[mode](h));
   else TRY(h->ops->forward[0][mode](h));
@@ -382,6 +384,7 @@ int rp_setup(to_handle* h) {
   // re-solve behind an AL solve: per-trajectory values) — moved along, never copied home
   if (P.n_cons > 0) { add(&a.lam, 3, (int)P.n_duals); add(&a.mu, 3, P.n_cons); }
   if (a.P.cp) add(&a.P.cp, 3, P.n_cp);
+  if (a.P.cl) add(&a.P.cl, 3, P.n_cl);  // per-trajectory constraint limits travel with their trajectories, like cp
   for (double** f : {&a.J, &a.dJ, &a.grad, &a.rho, &a.drho, &a.cmax}) add(f, 1, 1);
   for (int** f : {&a.status, &a.iterations, &a.it_inner, &a.outer, &a.dJzero, &a.ls_index, &a.active, &a.budget, &a.bpfail, &a.acc, &a.accp}) add(f, 2, 1);
   if ((int)h->rp_arr.size() > RP_MAX) return fail(TO_ERR_UNSUPPORTED, "repack table too long");
@@ -1264,10 +1267,14 @@ int to_set_constraint(to_handle* h, int32_t id, const to_constraint_desc* c) {
   const DevCon& old = h->cons[id];
   if (ci.p != old.p || ci.k1 != old.k1 || ci.k2 != old.k2) return fail(TO_ERR_DIMENSION_MISMATCH, "replacement constraint must keep p and the knot range");
   ci.dual_off = old.dual_off;
-  h->cons[id] = ci;  // (cp_off = -1: the replaced constraint starts on shared parameters again)
+  h->cons[id] = ci;  // (cp_off = cl_off = -1: the replaced constraint starts on shared parameters and limits again)
   bool any = false;
   for (const DevCon& c : h->cons) any = any || c.cp_off >= 0;
   if (!any) h->a.P.cp = nullptr;
+  if (!h->cl_host.empty()) h->cl_host[id].clear();
+  any = false;
+  for (const DevCon& c : h->cons) any = any || c.cl_off >= 0;
+  if (!any) h->a.P.cl = nullptr;
   return upload_tables(h);
 }
 // One parameter set per TRAJECTORY for constraint con_id.  GOAL: params[p, B] = xf_b[inds]; LINEAR: params[p, B] = b_b.  Stored as the shift of
@@ -1322,6 +1329,72 @@ int to_clear_constraint_params_batch(to_handle* h) {
   CHECK_H(h); CHECK_IDLE(h); TRY(use_device(h));
   for (DevCon& c : h->cons) c.cp_off = -1;
   h->a.P.cp = nullptr;
+  return upload_tables(h);
+}
+
+// One set of limits per TRAJECTORY for the selector constraint con_id (DevProblem::cl; desc_lower.h lower_constraint_limits has the layouts and
+// the checks).  The whole tiled array is rebuilt on the host from what every flagged constraint was given and the descriptors of the others —
+// the lanes behind the batch carry the descriptor's values: idle lanes compute along on valid data — and goes up in one copy.
+static int upload_constraint_limits(to_handle* h) {
+  DevProblem& P = h->a.P;
+  const int B = P.B, n_cl = P.n_cl;
+  const size_t tiles = (size_t)P.Bp / 64 + 1;  // (+ one spare tile, like the nominal states)
+  if (!h->d_cl) TRY(dev_alloc(h, &h->d_cl, tiles * n_cl * 64));
+  std::vector<double> tiled(tiles * n_cl * 64), rows;
+  for (size_t i = 0; i < h->cons.size(); ++i) {
+    const DevCon& c = h->cons[i];
+    const bool set = !h->cl_host[i].empty();
+    if (set) TRY(lower_constraint_limits(c, B, h->cl_host[i].data(), &rows));
+    for (size_t t = 0; t < tiles; ++t)
+      for (int r = 0; r < c.p; ++r)
+        for (int l = 0; l < 64; ++l) {
+          const size_t b = t * 64 + l;
+          tiled[(t * n_cl + h->cl_base[i] + r) * 64 + l] = (set && b < (size_t)B) ? rows[r + (size_t)c.p * b] : c.soff[r];
+        }
+  }
+  HIPCHECK(hipMemcpyAsync(h->d_cl, tiled.data(), tiled.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  HIPCHECK(hipStreamSynchronize(h->stream));
+  return TO_OK;
+}
+int to_set_constraint_limits_batch(to_handle* h, int32_t id, const double* limits) {
+  CHECK_H(h); CHECK_IDLE(h); CHECK_P(limits); TRY(use_device(h));
+  if (id < 0 || id >= (int)h->cons.size()) return fail(TO_ERR_ARGUMENT, "constraint id out of range");
+  DevCon& ci = h->cons[id];
+  DevProblem& P = h->a.P;
+  std::vector<double> rows;
+  TRY(lower_constraint_limits(ci, P.B, limits, &rows));  // every refusal, before anything changes
+  int q = 0;
+  TRY(constraint_limits_q(ci, &q));
+  if (h->cl_host.empty()) {
+    h->cl_host.assign(h->cons.size(), std::vector<double>());
+    h->cl_base.assign(h->cons.size(), 0);
+    int L = 0;
+    for (size_t i = 0; i < h->cons.size(); ++i) { h->cl_base[i] = L; L += h->cons[i].p; }
+    P.n_cl = L;
+  }
+  h->cl_host[id].assign(limits, limits + (size_t)q * P.B);
+  TRY(upload_constraint_limits(h));
+  ci.cl_off = h->cl_base[id];
+  P.cl = h->d_cl;
+  TRY(upload_tables(h));  // (expand_variant bit 2, unit_soc and the compact cost block follow the flags)
+  return check_guards(h, "to_set_constraint_limits_batch");
+}
+int to_get_constraint_limits_batch(to_handle* h, int32_t id, double* limits) {
+  CHECK_H(h); CHECK_IDLE(h); CHECK_P(limits);
+  if (id < 0 || id >= (int)h->cons.size()) return fail(TO_ERR_ARGUMENT, "constraint id out of range");
+  const DevCon& ci = h->cons[id];
+  int q = 0;
+  TRY(constraint_limits_q(ci, &q));
+  const int B = h->a.P.B;
+  if (ci.cl_off >= 0) std::memcpy(limits, h->cl_host[id].data(), sizeof(double) * q * B);
+  else for (int b = 0; b < B; ++b) shared_constraint_limits(ci, q, limits + (size_t)q * b);
+  return TO_OK;
+}
+int to_clear_constraint_limits_batch(to_handle* h) {
+  CHECK_H(h); CHECK_IDLE(h); TRY(use_device(h));
+  for (DevCon& c : h->cons) c.cl_off = -1;
+  for (auto& v : h->cl_host) v.clear();
+  h->a.P.cl = nullptr;
   return upload_tables(h);
 }
 
