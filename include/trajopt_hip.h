@@ -70,7 +70,9 @@ extern "C" {
  * without them as one that plans every trajectory on to_problem_desc::model_params.  The same holds for to_set_constraint_limits_batch /
  * to_get_constraint_limits_batch / to_clear_constraint_limits_batch (the bounds of a BoundConstraint, the value of a second-order-cone
  * NormConstraint, one set per trajectory): added with TO_ABI_VERSION and TO_ABI_MINOR unchanged, found by symbol lookup; a library
- * without them shares every limit among the trajectories of a handle. */
+ * without them shares every limit among the trajectories of a handle.  And for to_set_time_steps_batch / to_get_time_steps_batch /
+ * to_clear_time_steps_batch (one set of time steps — one horizon — per trajectory): added with TO_ABI_VERSION and TO_ABI_MINOR unchanged,
+ * found by symbol lookup; a library without them steps every trajectory of a handle by to_problem_desc::dt. */
 #define TO_ABI_VERSION 7
 #define TO_ABI_MINOR 1
 
@@ -439,6 +441,24 @@ int to_clear_model_params_batch(to_handle* h);
 int to_set_constraint_limits_batch(to_handle* h, int32_t con_id, const double* limits /* [q*B], q fastest */);
 int to_get_constraint_limits_batch(to_handle* h, int32_t con_id, double* limits /* [q*B] */);
 int to_clear_constraint_limits_batch(to_handle* h);
+/* One set of TIME STEPS per TRAJECTORY: every trajectory of the handle is planned on its own horizon — a sweep over final times, the
+ * bisection of a minimum-time search, a fleet whose members replan at different rates.  dt[(N-1), B] (knot fastest, then trajectory): column
+ * b is read exactly like to_problem_desc::dt.  While steps are set, everything on the handle that reads a time step — the dynamics of the
+ * rollout, the expansion, the line search, the defect and the projected-Newton polish, to_discrete_jacobian, cost_dt_scaling in every cost
+ * value and expansion, to_policy_rollout / to_policy_rollout_mc (sample c steps by the steps of ITS trajectory; the process noise stays "per
+ * step") — uses dt_b[k]: what trajectory b evaluates is what a single-trajectory problem built with dt = dt_b evaluates.  Every value must be
+ * finite and > 0 — TO_ERR_ARGUMENT otherwise, the message names the first offending trajectory and knot; there is no "must sum to tf - t0"
+ * check: trajectory b ends at tf_b = t0 + sum_k dt_b[k].  Models: those of to_set_model_params_batch (double integrator D = 1, 2, 3, Cartpole,
+ * quaternion Quadrotor); TO_ERR_UNSUPPORTED, with the model's name, for Quadrotor{MRP} / {RodriguesParam}, the hybrid double integrator, model
+ * vectors and InfeasibleModel (its slack cost is built from R_inf / dt on the host).  The setter leaves X, U, duals and gains as they are.
+ * The solves run the kernel instances of to_set_model_params_batch (to_solver_path reports no fused and no scan kernel and no
+ * repacked working set), with which — and with to_set_cost_linear_batch, to_set_constraint_params_batch, to_set_constraint_limits_batch — it
+ * coexists on one handle.  to_get_... returns what was set, or the descriptor's steps repeated B times; to_clear_... returns the handle to the
+ * descriptor's steps — a solve after it is bit-identical to the same solve on a fresh handle.  Not announced by TO_ABI_MINOR: look the
+ * symbols up (ABI history above). */
+int to_set_time_steps_batch(to_handle* h, const double* dt /* [(N-1)*B], knot fastest, then trajectory */);
+int to_get_time_steps_batch(to_handle* h, double* dt /* [(N-1)*B] */);
+int to_clear_time_steps_batch(to_handle* h);
 
 /* ---- the hot path, phase by phase ----------------------------------------------------------- */
 int to_rollout(to_handle* h);                                   /* rollout!  src/problem.jl:330-340 */

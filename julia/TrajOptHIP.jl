@@ -794,6 +794,43 @@ function clear_constraint_limits_batch!(p::BatchProblem)
     check(ccall((:to_clear_constraint_limits_batch, lib), Cint, (Ptr{Cvoid},), p.handle))
     nothing
 end
+"""
+    set_time_steps_batch!(p, dt)       # dt :: (N-1, B)
+One set of time steps per trajectory (`to_set_time_steps_batch`): column `b` is read like `to_problem_desc::dt`, and trajectory `b` is
+planned — rolled out, expanded, solved, polished — with it, as a `Problem(...; dt = dt[:, b])` of its own is; its final time is
+`t0 + sum(dt[:, b])`.  `set_final_times_batch!(p, tf)` (`tf :: (B,)`) stores the uniform steps `(tf[b] - t0) / (N - 1)`;
+`time_steps_batch(p)` returns what is set (the problem's steps repeated if nothing is), `clear_time_steps_batch!(p)` returns to the
+problem's steps.  Models: those of `set_model_params_batch!`.  Added without raising `TO_ABI_MINOR`: a library that lacks them is detected
+by symbol lookup (`has_time_steps_batch()`).
+"""
+has_time_steps_batch() = Libdl.dlsym(Libdl.dlopen(lib), :to_set_time_steps_batch; throw_error = false) !== nothing
+function set_time_steps_batch!(p::BatchProblem, dt::Matrix{Float64})
+    has_time_steps_batch() || error("libtrajopt_hip.so does not export to_set_time_steps_batch")
+    size(dt) == (p.N - 1, p.B) || throw(DimensionMismatch("dt must be (N-1, B)"))
+    check(ccall((:to_set_time_steps_batch, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}), p.handle, dt))
+    nothing
+end
+function set_final_times_batch!(p::BatchProblem, tf::Vector{Float64})
+    length(tf) == p.B || throw(DimensionMismatch("tf must be (B,)"))
+    dt = Matrix{Float64}(undef, p.N - 1, p.B)
+    for b in 1:p.B
+        dt[:, b] .= (tf[b] - TO.get_initial_time(p.prob)) / (p.N - 1)
+    end
+    size(dt) == (p.N - 1, p.B) || throw(DimensionMismatch("dt must be (N-1, B)"))
+    set_time_steps_batch!(p, dt)
+end
+function time_steps_batch(p::BatchProblem)
+    has_time_steps_batch() || error("libtrajopt_hip.so does not export to_get_time_steps_batch")
+    dt = zeros(p.N - 1, p.B)
+    size(dt) == (p.N - 1, p.B) || throw(DimensionMismatch("dt must be (N-1, B)"))
+    check(ccall((:to_get_time_steps_batch, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}), p.handle, dt))
+    dt
+end
+function clear_time_steps_batch!(p::BatchProblem)
+    has_time_steps_batch() || error("libtrajopt_hip.so does not export to_clear_time_steps_batch")
+    check(ccall((:to_clear_time_steps_batch, lib), Cint, (Ptr{Cvoid},), p.handle))
+    nothing
+end
 function clear_goal_state_batch!(p::BatchProblem)
     check(ccall((:to_clear_cost_linear_batch, lib), Cint, (Ptr{Cvoid},), p.handle))
     check(ccall((:to_clear_constraint_params_batch, lib), Cint, (Ptr{Cvoid},), p.handle))
@@ -947,7 +984,7 @@ function profile(p::BatchProblem)
     (kernel_ms = ms, launches = launches)
 end
 
-export LinearMap, MassDoubleIntegrator, BatchProblem, set_model_params_batch!, model_params_batch, clear_model_params_batch!, has_model_params_batch, set_constraint_limits_batch!, get_constraint_limits_batch, clear_constraint_limits_batch!, has_constraint_limits_batch, policy_rollout, PolicyOpts, PolicyResult, policy_rollout_mc, policy_noise_draws, PolicyNoise, abi_minor, SolverOpts, solver_options, default_options, solve_ilqr!, solve_al!, solve_pn!, solve_altro!, solve_async!, wait_solve!, dynamics_defect, expand!, backwardpass!, forwardpass!,
+export LinearMap, MassDoubleIntegrator, BatchProblem, set_model_params_batch!, model_params_batch, clear_model_params_batch!, has_model_params_batch, set_constraint_limits_batch!, get_constraint_limits_batch, clear_constraint_limits_batch!, has_constraint_limits_batch, set_time_steps_batch!, set_final_times_batch!, time_steps_batch, clear_time_steps_batch!, has_time_steps_batch, policy_rollout, PolicyOpts, PolicyResult, policy_rollout_mc, policy_noise_draws, PolicyNoise, abi_minor, SolverOpts, solver_options, default_options, solve_ilqr!, solve_al!, solve_pn!, solve_altro!, solve_async!, wait_solve!, dynamics_defect, expand!, backwardpass!, forwardpass!,
     stage_costs, al_cost, dynamics_jacobians, cost_expansion, gains, cost_gradient_hessian, discrete_jacobian, duals, set_duals!,
     reset_duals!, dual_update!, comm_unique_id, comm_init_rank!, allgather!, allgather_stats, comm_shards, comm_destroy!, solver_path, knot_dims, device_count, build_id
 

@@ -257,11 +257,16 @@ HIP_ONLY = {
     "set_constraint_limits_batch": [_H, C.c_int32, _PD],
     "get_constraint_limits_batch": [_H, C.c_int32, _PD],
     "clear_constraint_limits_batch": [_H],
+    # one set of time steps per trajectory (OPTIONAL_HIP below)
+    "set_time_steps_batch": [_H, _PD],
+    "get_time_steps_batch": [_H, _PD],
+    "clear_time_steps_batch": [_H],
 }
 # Entry points added without raising TO_ABI_MINOR (include/trajopt_hip.h, ABI history): detected by symbol lookup.  A library that does
 # not export them still loads; the names are then absent from Library._fn and the wrappers in api.py raise UnsupportedError.
 OPTIONAL_HIP = ("set_model_params_batch", "get_model_params_batch", "clear_model_params_batch",
-                "set_constraint_limits_batch", "get_constraint_limits_batch", "clear_constraint_limits_batch")
+                "set_constraint_limits_batch", "get_constraint_limits_batch", "clear_constraint_limits_batch",
+                "set_time_steps_batch", "get_time_steps_batch", "clear_time_steps_batch")
 
 
 class Library:

@@ -43,7 +43,8 @@ __all__ = [
     "GoalConstraint", "BoundConstraint", "NormConstraint", "CircleConstraint", "SphereConstraint", "CollisionConstraint", "QuatVecEq",
     "LinearConstraint", "StateBound", "ControlBound", "IndexedConstraint", "change_dimension",
     "ConstraintList", "add_constraint", "num_constraints", "constraint_hessians",
-    "KnotPoint", "Problem", "rollout", "policy_rollout", "PolicyRollout", "PolicyNoise", "policy_noise_draws", "set_model_params", "model_params", "clear_model_params", "cost", "states", "controls", "initial_controls", "initial_states",
+    "KnotPoint", "Problem", "rollout", "policy_rollout", "PolicyRollout", "PolicyNoise", "policy_noise_draws", "set_model_params", "model_params", "clear_model_params",
+    "set_time_steps_batch", "set_final_times_batch", "time_steps", "clear_time_steps_batch", "cost", "states", "controls", "initial_controls", "initial_states",
     "set_initial_state", "set_goal_state", "update_trajectory", "get_constraints", "get_objective", "get_model",
     "get_initial_state", "get_final_state", "get_trajectory", "gettimes",
     "SolverOptions", "iLQRSolver", "ALSolver", "ALTROSolver", "ProjectedNewtonSolver", "dynamics_defect", "solve", "SolvePipeline", "iterations", "status", "max_violation",
@@ -1512,6 +1513,48 @@ def clear_model_params(prob):
     """Back to the problem's model for every trajectory (to_clear_model_params_batch)."""
     _need_model_params_batch(prob)
     prob._call("clear_model_params_batch")
+
+
+def _need_time_steps_batch(prob):
+    if "set_time_steps_batch" not in prob._lib._fn:
+        raise UnsupportedError("per-trajectory time steps need a HIP library that exports to_set_time_steps_batch "
+                               "(the CPU oracle steps every trajectory by the problem's dt)")
+
+
+def set_time_steps_batch(prob, dt):
+    """One set of time steps per TRAJECTORY (to_set_time_steps_batch): ``dt`` is [B, N-1]; trajectory ``b`` is planned — rolled out, expanded,
+    solved, polished, simulated by ``policy_rollout`` — with the steps ``dt[b]``, exactly as a single problem built with ``dt=dt[b]`` is.  Its
+    final time is ``t0 + dt[b].sum()``; nothing has to sum to the problem's ``tf``.  X, U, duals and gains stay as they are."""
+    _need_time_steps_batch(prob)
+    h = np.asarray(dt, dtype=np.float64)
+    if h.shape != (prob.B, prob.N - 1):
+        raise DimensionMismatch(f"dt must be [B={prob.B}, N-1={prob.N - 1}]; got {h.shape}")
+    prob._call("set_time_steps_batch", prob._pd(np.ascontiguousarray(h)))
+
+
+def set_final_times_batch(prob, tf):
+    """One final time per TRAJECTORY: ``tf`` is [B]; trajectory ``b`` gets the uniform steps ``(tf[b] - t0) / (N - 1)`` — the expression a
+    ``Problem`` built with ``tf=tf[b]`` forms for its own uniform step (``set_time_steps_batch`` with them)."""
+    _need_time_steps_batch(prob)
+    t = np.asarray(tf, dtype=np.float64)
+    if t.shape != (prob.B,):
+        raise DimensionMismatch(f"tf must be [B={prob.B}]; got {t.shape}")
+    h = (t - prob.t0) / (prob.N - 1)
+    set_time_steps_batch(prob, np.repeat(h[:, None], prob.N - 1, axis=1))
+
+
+def time_steps(prob):
+    """[B, N-1]: the time steps every trajectory is planned with (to_get_time_steps_batch; the problem's own, repeated, if none are set)."""
+    _need_time_steps_batch(prob)
+    h = np.empty((prob.B, prob.N - 1))
+    prob._call("get_time_steps_batch", prob._pd(h))
+    return h
+
+
+def clear_time_steps_batch(prob):
+    """Back to the problem's time steps for every trajectory (to_clear_time_steps_batch)."""
+    _need_time_steps_batch(prob)
+    prob._call("clear_time_steps_batch")
 
 
 def cost(prob):

@@ -131,17 +131,18 @@ __device__ __forceinline__ double* slot_ptr(double* nominal, double* cand, const
 // GEN = false: no dense QuadraticCost and no non-selector constraint in the tables (those branches are compiled out)
 // gl0: this lane's pointer into DevProblem::gl (per-trajectory linear cost terms; nullptr: none)
 // cp0 / cl0: this lane's pointers into DevProblem::cp / cl (per-trajectory constraint parameters / limits; general variants only)
-template <class M, bool GEN = true>
+// dt0: dt_lane of this lane's trajectory (per-trajectory time steps, problem_dev.h step_dt), or nothing: the shared steps, read as ever
+template <class M, bool GEN = true, class D = std::nullptr_t>
 __device__ __forceinline__ double knot_cost(const DevProblem& P, int k, const double* x, const double* u, const double* lam0,
                                             const double* mu0, bool with_al, const double* gl0 = nullptr, const double* cp0 = nullptr,
-                                            const double* cl0 = nullptr) {
+                                            const double* cl0 = nullptr, D dt0 = nullptr) {
   constexpr int n = M::n, m = M::m, nz = n + m;
   const int cidx = P.cost_index[k];
   double Jk = cost_eval<n, m, GEN>(P.costs[cidx], x, u);
   if constexpr (GEN) {
     if (P.gl) Jk += goal_lin_cost<n, m>(gl0, cidx, x, u);  // (P.gl: wave-uniform; gl0 is only meaningful with it)
   }
-  if (P.opts.cost_dt_scaling && k < P.N - 1) Jk *= P.dt[k];
+  if (P.opts.cost_dt_scaling && k < P.N - 1) Jk *= step_dt(P, k, dt0);
   if (with_al && P.n_cons > 0) {
     double z[nz];
 #pragma unroll
@@ -250,6 +251,7 @@ __device__ __forceinline__ void trajectory_pass(const KArgs& a, int tile, int la
   double* mu0 = TILE_PTR(a.mu, P.n_cons);
   const double* cp0 = TILE_PTR(P.cp, P.n_cp);
   const double* cl0 = TILE_PTR(P.cl, P.n_cl);
+  const double* dt0 = dt_lane(P, tile * 64 + lane);
   double J = 0.0, cmax = 0.0;
   for (int k = 0; k < N; ++k) {
     double x[n], u[m];
@@ -275,7 +277,7 @@ __device__ __forceinline__ void trajectory_pass(const KArgs& a, int tile, int la
       }
     }
     if (cmax_out && P.n_cons > 0) { const double v = knot_violation<M>(P, k, x, u, cp0, cl0); if (!(v <= cmax)) cmax = v; }
-    if (J_out) J += knot_cost<M>(P, k, x, u, lam0, mu0, with_al, TILE_PTR(P.gl, P.n_costs * nz), cp0, cl0);
+    if (J_out) J += knot_cost<M>(P, k, x, u, lam0, mu0, with_al, TILE_PTR(P.gl, P.n_costs * nz), cp0, cl0, dt0);
   }
   if (J_out) *J_out = J;
   if (cmax_out) *cmax_out = cmax;

@@ -258,6 +258,32 @@ inline void shared_constraint_limits(const DevCon& ci, int q, double* out) {
   for (int i = 0; i < q; ++i) out[i] = ci.soff[q == 1 && ci.d.kind == TO_CON_NORM ? ci.p - 1 : i];
 }
 
+// Per-trajectory time steps (to_set_time_steps_batch): dt[(N-1), B], knot fastest, column b read exactly like to_problem_desc::dt.
+// lower_time_steps checks every value — finite and > 0, the check the descriptor's own steps get at to_create; there is NO "must sum to
+// tf - t0" check: trajectory b ends at its own tf_b = t0 + sum_k dt_b[k] — and tiles them the way DevProblem::dtb is read: step k of
+// trajectory b at tiled[((b >> 6) * (N - 1) + k) * 64 + (b & 63)], Bp / 64 tiles and one spare tile (like the nominal states and
+// DevProblem::pm); the lanes behind the batch and the spare tile carry the SHARED steps (idle lanes compute along on valid data).
+inline size_t time_steps_tiled_len(int N, int Bp) { return ((size_t)Bp / 64 + 1) * (size_t)(N - 1) * 64; }
+inline int lower_time_steps(int N, int B, int Bp, const double* dt, const double* shared /* [N-1] */, std::vector<double>* tiled) {
+  const int L = N - 1;
+  for (int b = 0; b < B; ++b)
+    for (int k = 0; k < L; ++k) {
+      const double v = dt[k + (size_t)L * b];
+      if (!std::isfinite(v) || !(v > 0.0))
+        return fail(TO_ERR_ARGUMENT, "to_set_time_steps_batch: time step " + std::to_string(k) + " of trajectory " + std::to_string(b) +
+                                         (std::isfinite(v) ? " is not > 0" : " is not finite"));
+    }
+  const size_t tiles = (size_t)Bp / 64 + 1;
+  tiled->assign(time_steps_tiled_len(N, Bp), 0.0);
+  for (size_t t = 0; t < tiles; ++t)
+    for (int k = 0; k < L; ++k)
+      for (int l = 0; l < 64; ++l) {
+        const size_t b = t * 64 + l;
+        (*tiled)[(t * L + k) * 64 + l] = b < (size_t)B ? dt[k + (size_t)L * b] : shared[k];
+      }
+  return TO_OK;
+}
+
 // rot: attitude representation of the model's state (to_rotation), -1 for vector-space models
 inline int validate_cost(int n, int rot, const to_cost_desc& c) {
   if (c.kind != TO_COST_DIAGONAL && c.kind != TO_COST_QUADRATIC && c.kind != TO_COST_DIAGONAL_QUAT && c.kind != TO_COST_ERROR_QUADRATIC)

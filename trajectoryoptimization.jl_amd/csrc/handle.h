@@ -10,6 +10,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "common.h"
@@ -79,7 +80,11 @@ struct to_handle_s {
   std::vector<char> gl_set; // [n_costs] cost i carries per-trajectory linear terms (all clear: DevProblem::gl goes back to null)
   double* d_gl = nullptr;   // per-trajectory linear cost terms (DevProblem::gl), tiled, L = n_costs * (n + m); allocated on first use
   double* d_pm = nullptr;   // per-trajectory model parameters (DevProblem::pm), tiled, L = 16, one spare tile; allocated on first use
-  std::vector<double> pm_host;  // [16, B] host copy of what to_set_model_params_batch was given (empty: shared parameters)
+  std::vector<double> pm_host;  // [16, B] host copy of what DevProblem::pm holds: what to_set_model_params_batch was given, or — pm_own false, the handle
+                                // carries per-trajectory time steps only — the shared parameters repeated (empty: DevProblem::pm is null)
+  bool pm_own = false;      // to_set_model_params_batch is in effect (to_clear_model_params_batch / to_clear_time_steps_batch: which of the two keeps pm alive)
+  double* d_dtb = nullptr;  // per-trajectory time steps (DevProblem::dtb), tiled, L = N - 1, one spare tile; allocated on first use
+  std::vector<double> dtb_host;  // [N-1, B] what to_set_time_steps_batch was given (empty: shared steps)
   double* d_cp = nullptr;   // per-trajectory constraint parameters (DevProblem::cp), tiled, L = (n + m) * number of constraints; allocated on first use
   double* d_cl = nullptr;   // per-trajectory constraint limits (DevProblem::cl), tiled, L = n_cl = summed p of the constraints, one spare tile; allocated on first use
   std::vector<int> cl_base;                 // [n_cons] first row of constraint i's block in d_cl
@@ -235,5 +240,20 @@ void g_free(to_handle* h, void* p);
 int check_guards(to_handle* h, const char* where);
 
 inline dim3 grid_b(const to_handle* h, int y = 1, int z = 1) { return dim3(h->a.P.Bp / BLOCK, y, z); }
+
+// Per-trajectory time steps (DevProblem::dtb) ride on the flagged instances, which exist twice (problem_dev.h step_dt_of): body(bool_constant<DT>)
+// with DT = the handle carries them.  Chosen here, inside the launcher of entry [1] (ops.h, ops_lane.h, ops_pn.h): the ModelOps table does not grow, a handle with plants alone
+// launches the kernels it always did, and the unflagged launchers (PM = false) never see a DT instance.
+template <class M> struct TimeStepsModel : std::false_type {};  // the models to_set_time_steps_batch accepts
+template <int D> struct TimeStepsModel<DoubleIntegratorModel<D>> : std::true_type {};
+template <> struct TimeStepsModel<CartpoleModel> : std::true_type {};
+template <> struct TimeStepsModel<QuadrotorModel> : std::true_type {};
+template <class M, bool PM, class F>
+int with_time_steps(const to_handle* h, F&& body) {
+  if constexpr (PM && TimeStepsModel<M>::value) {
+    if (h->a.P.dtb != nullptr) return body(std::true_type{});
+  }
+  return body(std::false_type{});
+}
 
 }  // namespace to

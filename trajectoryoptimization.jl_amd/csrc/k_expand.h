@@ -25,10 +25,12 @@ namespace to {
 // compact cost block is block-diagonal with r and v on 1 x 1 blocks (KArgs::h_compact), so entry jc of the product is exactly the diagonal
 // entry of column jc and every other entry is what the own direction alone gives — and the gradient does not depend on the direction.
 template <class M> struct ExpandPack { static constexpr bool ok = M::lie && (M::att == ATT_QUAT || M::att == ATT_MRP || M::att == ATT_RP) && M::ne == 12 && M::m == 4 && Tm<M>::fits; };
-template <class M, int FIXED_INTEG, int VAR, int LAY, bool PACK = false>
+// DT (the flagged instances on a handle with per-trajectory time steps): dt0 = the trajectory's own steps (problem_dev.h step_dt_of)
+template <class M, int FIXED_INTEG, int VAR, int LAY, bool PACK = false, bool DT = false>
 __device__ __forceinline__ void expand_knot(const KArgs& a, int gtile, int lane, int tile, int lane64, int b, int j, int k, bool valid,
                                             const double* x, const double* u, const double* x1, const ConExp<M::m>& ce0,
-                                            const ConExp<M::m>& ce1, bool table_cons, const double* mp, int jc = -1, bool valid_c = false) {
+                                            const ConExp<M::m>& ce1, bool table_cons, const double* mp, int jc = -1, bool valid_c = false,
+                                            const double* dt0 = nullptr) {
   constexpr int n = M::n, m = M::m, ne = M::ne, nz = n + m, nc = ne + m;
   static_assert(!PACK || (LAY == 2 && ExpandPack<M>::ok), "packed expansion: compact tangent-matrix layout of the rigid body");
   constexpr int NEP = Tm<M>::NEP, RS = Tm<M>::RS, NR = Tm<M>::NR;
@@ -73,7 +75,7 @@ __device__ __forceinline__ void expand_knot(const KArgs& a, int gtile, int lane,
     for (int i = 0; i < n; ++i) xd[i] = Dual(x[i], v[i]);
 #pragma unroll
     for (int i = 0; i < m; ++i) ud[i] = Dual(u[i], v[n + i]);
-    model_step<M, Dual, FIXED_INTEG>(mp, P.integrator, k, xd, ud, P.dt[k], xn);
+    model_step<M, Dual, FIXED_INTEG>(mp, P.integrator, k, xd, ud, step_dt_of<DT>(P, k, dt0), xn);
     double t[n], col[ne];
 #pragma unroll
     for (int i = 0; i < n; ++i) t[i] = xn[i].d;
@@ -108,7 +110,7 @@ __device__ __forceinline__ void expand_knot(const KArgs& a, int gtile, int lane,
   cost_grad_hvp<n, m, (VAR & 1) != 0>(P.costs[P.cost_index[k]], x, u, terminal, v, gr, y);
   if (P.gl) goal_lin_grad<n, m>(P.gl + ((size_t)tile * (size_t)(P.n_costs * nz)) * 64 + lane64, P.cost_index[k], terminal, gr);  // per-trajectory q, r
   if (P.opts.cost_dt_scaling && !terminal) {
-    const double h = P.dt[k];
+    const double h = step_dt_of<DT>(P, k, dt0);
 #pragma unroll
     for (int i = 0; i < nz; ++i) { gr[i] *= h; y[i] *= h; }
   }
@@ -278,7 +280,7 @@ __host__ __device__ constexpr int expand_kc() {
 #define TO_EXPAND_WAVES 1  // minimum waves per SIMD k_expand is compiled for (register cap 512 / waves)
 #endif
 constexpr int EXPAND_PACK_G = 6, EXPAND_PACK_R = 10;  // packed expansion: trajectories per wave x differentiated columns (lanes 60..63 idle)
-template <class M, int FIXED_INTEG, int VAR, int LAY, bool PACK = false, bool PM = false>
+template <class M, int FIXED_INTEG, int VAR, int LAY, bool PACK = false, bool PM = false, bool DT = false>
 __global__ void __launch_bounds__(64, TO_EXPAND_WAVES) k_expand(KArgs a) {
   static_assert(!PM || !PACK, "per-trajectory model parameters: the general variants only (DESIGN.md §4c)");
   constexpr int n = M::n, m = M::m, ne = M::ne, nc = ne + m, KC = expand_kc<M, VAR>();
@@ -334,6 +336,7 @@ __global__ void __launch_bounds__(64, TO_EXPAND_WAVES) k_expand(KArgs a) {
   double pmr[PM ? 16 : 1];
   const double* mp = P.mp;
   if constexpr (PM) { load_plant(P, b, pmr); mp = pmr; }
+  const double* dt0 = dt_lane_of<DT>(P, b);
   double x[n], u[m], x1[n], x2[n], un[m];
 #pragma unroll
   for (int i = 0; i < n; ++i) { x[i] = EL(X, k0 * n + i); x1[i] = (k0 + 1 < N) ? EL(X, (k0 + 1) * n + i) : 0.0; }
@@ -361,7 +364,7 @@ __global__ void __launch_bounds__(64, TO_EXPAND_WAVES) k_expand(KArgs a) {
         for (int i = 0; i < m; ++i) EL(U0, k * m + i) = u[i];
       }
     }
-    expand_knot<M, FIXED_INTEG, VAR, LAY, PACK>(a, gtile, lane, tile, lane64, b, j, k, valid, x, u, x1, ce0, ce1, table_cons, mp, jc, lane_ok);
+    expand_knot<M, FIXED_INTEG, VAR, LAY, PACK, DT>(a, gtile, lane, tile, lane64, b, j, k, valid, x, u, x1, ce0, ce1, table_cons, mp, jc, lane_ok, dt0);
     if (KC > 1) {
 #pragma unroll
       for (int i = 0; i < n; ++i) { x[i] = x1[i]; x1[i] = x2[i]; }
@@ -406,15 +409,15 @@ __global__ void __launch_bounds__(64) k_expand_const_columns(KArgs a) {
 // expand_lane_knot: the expansion of knot k of this lane's trajectory INTO REGISTERS, in the lane layout's own order
 // (k_backward.h, LaneLay): Mk[i*nc + j] = [A B][i][j] (not touched at the terminal knot), H[sym(i, j)] = upper triangle of
 // the cost (+AL) block, g[j] = gradient.  Same calls and the same order of the constraint terms as expand_knot's table path.
-template <class M, int FIXED_INTEG, int VAR>
+template <class M, int FIXED_INTEG, int VAR, bool DT = false>  // (DT, dt0: as in expand_knot)
 __device__ __forceinline__ void expand_lane_knot(const KArgs& a, int tile, int lane, int k, const double* x, const double* u,
-                                                 double* Mk, double* H, double* g, const double* mp) {
+                                                 double* Mk, double* H, double* g, const double* mp, const double* dt0 = nullptr) {
   static_assert(!M::lie, "lane expansion: vector-space models only (identity error-state maps)");
   constexpr int n = M::n, m = M::m, ne = M::ne, nz = n + m, nc = ne + m;
   const DevProblem& P = a.P;
   const bool terminal = (k == P.N - 1);
   if constexpr (has_stage_jac<M>::value && FIXED_INTEG == INTEG_RK4) {
-    if (!terminal) cartpole_rk4_jac(mp, x, u, P.dt[k], Mk);  // chain rule over hand-derived stage partials (models.h)
+    if (!terminal) cartpole_rk4_jac(mp, x, u, step_dt_of<DT>(P, k, dt0), Mk);  // chain rule over hand-derived stage partials (models.h)
   } else
   if (!terminal) {  // every column of [A B] in one pass
     MDual<nc> xd[n], ud[m], xn[n];
@@ -422,7 +425,7 @@ __device__ __forceinline__ void expand_lane_knot(const KArgs& a, int tile, int l
     for (int i = 0; i < n; ++i) { xd[i].v = x[i]; xd[i].d[i] = 1.0; }
 #pragma unroll
     for (int i = 0; i < m; ++i) { ud[i].v = u[i]; ud[i].d[ne + i] = 1.0; }
-    model_step<M, MDual<nc>, FIXED_INTEG>(mp, P.integrator, k, xd, ud, P.dt[k], xn);
+    model_step<M, MDual<nc>, FIXED_INTEG>(mp, P.integrator, k, xd, ud, step_dt_of<DT>(P, k, dt0), xn);
 #pragma unroll
     for (int i = 0; i < ne; ++i)
 #pragma unroll
@@ -442,7 +445,7 @@ __device__ __forceinline__ void expand_lane_knot(const KArgs& a, int tile, int l
     // Same products and sums as the general path computes for unit vectors (its multiplications by 0 and 1 are exact).
     CostC& C = P.costs[P.cost_index[k]];
     if (C.kind == TO_COST_DIAGONAL) {
-      const double sc = (P.opts.cost_dt_scaling && !terminal) ? P.dt[k] : 1.0;
+      const double sc = (P.opts.cost_dt_scaling && !terminal) ? step_dt_of<DT>(P, k, dt0) : 1.0;
       double gr[nz];
 #pragma unroll
       for (int i = 0; i < n; ++i) gr[i] = C.Q[i] * x[i] + C.q[i];
@@ -467,7 +470,7 @@ __device__ __forceinline__ void expand_lane_knot(const KArgs& a, int tile, int l
     cost_grad_hvp<n, m, (VAR & 1) != 0>(P.costs[P.cost_index[k]], x, u, terminal, v, gr, y);
     if (P.gl) goal_lin_grad<n, m>(P.gl + ((size_t)tile * (size_t)(P.n_costs * nz)) * 64 + lane, P.cost_index[k], terminal, gr);  // per-trajectory q, r
     if (P.opts.cost_dt_scaling && !terminal) {
-      const double h = P.dt[k];
+      const double h = step_dt_of<DT>(P, k, dt0);
 #pragma unroll
       for (int i = 0; i < nz; ++i) { gr[i] *= h; y[i] *= h; }
     }
@@ -499,7 +502,7 @@ __device__ __forceinline__ void expand_lane_knot(const KArgs& a, int tile, int l
 
 // the expansion as a kernel of its own (phase API, and the solve loop when the fused backward pass is switched off):
 // writes the lane layout as whole 512-byte rows, lane = trajectory.  grid (Bp / 64, N).
-template <class M, int FIXED_INTEG, int VAR, bool PM = false>
+template <class M, int FIXED_INTEG, int VAR, bool PM = false, bool DT = false>
 __global__ void __launch_bounds__(64) k_expand_lane(KArgs a) {
   constexpr int n = M::n, m = M::m, ne = M::ne, nc = ne + m;
   using L = LaneLay<M>;
@@ -532,7 +535,7 @@ __global__ void __launch_bounds__(64) k_expand_lane(KArgs a) {
   double pmr[PM ? 16 : 1];  // PM: the trajectory's own model parameters (here lane = trajectory; padding lanes hold the shared ones)
   const double* mp = P.mp;
   if constexpr (PM) { load_plant(P, b, pmr); mp = pmr; }
-  expand_lane_knot<M, FIXED_INTEG, VAR>(a, tile, lane, k, x, u, Mk, H, g, mp);
+  expand_lane_knot<M, FIXED_INTEG, VAR, DT>(a, tile, lane, k, x, u, Mk, H, g, mp, dt_lane_of<DT>(P, b));
   if (!live) return;
   if (!terminal) {
     double* Ml = a.Mc + (((size_t)tile * (size_t)(N - 1) + k) * (ne * nc)) * 64 + lane;

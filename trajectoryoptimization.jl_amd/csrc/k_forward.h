@@ -72,6 +72,7 @@ __host__ __device__ inline int gains_lds_doubles(int TW) {  // per buffer, whole
 // bit2: RK4 fixed at compile time; bit3: dense costs / non-selector constraints possible (else compiled out);
 // bit4: the register-cached control constraints are unit SOCs (problem_dev.h unit_soc_desc);
 // bit5: one plant per trajectory — the mp[] copy below comes from DevProblem::pm, indexed by the trajectory b (one-wave general variants only).
+// bit6 (with bit5): one set of time steps per trajectory — the step of knot k comes from DevProblem::dtb, indexed by the trajectory b.
 // kbuf: the wave's two LDS buffers for DMA-staged gains (M::lds_gains); krow: this lane's row offset in a buffer.
 template <class M, int MODE>
 __device__ __forceinline__ void forward_candidate(const KArgs& a, int tile, int lane, int b, bool live, double alpha, int wblock, double* kbuf,
@@ -111,6 +112,7 @@ __device__ __forceinline__ void forward_candidate(const KArgs& a, int tile, int 
   const double* cp0 = TILE_PTR(P.cp, P.n_cp);  // per-trajectory constraint parameters (general variants)
   const double* cl0 = TILE_PTR(P.cl, P.n_cl);  // ... and limits
   const int ci0 = P.cost_index[0];
+  const double* dt0 = dt_lane_of<(MODE & 64) != 0>(P, b);  // bit6: the trajectory's own time steps (DevProblem::dtb; with bit5, picked by the launcher)
   double h0 = 0.0;
   if constexpr (SIMPLE) {
     if constexpr (KLDS) { sc.load(P.costs[P.cost_index[0]], kbuf + 2 * (size_t)kbuf_len, hw); WAVE_SYNC(); }
@@ -186,7 +188,7 @@ __device__ __forceinline__ void forward_candidate(const KArgs& a, int tile, int 
     }
     pUo += m * 64;
     gsum += gk;
-    const double h = SIMPLE ? h0 : P.dt[k];
+    const double h = SIMPLE ? h0 : step_dt_of<(MODE & 64) != 0>(P, k, dt0);
     double Jk = SIMPLE ? sc.eval(xb, ub) : cost_eval<n, m, GEN>(P.costs[P.cost_index[k]], xb, ub);
     if constexpr (GEN) {  // per-trajectory q, r: in the general variants only (launch_forward picks one when DevProblem::gl is set), so that
       if (has_gl) Jk += goal_lin_cost<n, m>(gl0, SIMPLE ? ci0 : (int)P.cost_index[k], xb, ub);  // the default kernels keep their loops as they were

@@ -5,7 +5,8 @@
 namespace to {
 
 // ------------------------------------------------------------------------------------------------ rollout!
-template <class M, int FIXED_INTEG, bool PM = false>  // PM: one plant per trajectory (DevProblem::pm), loaded ahead of the knot loop
+// PM: one plant per trajectory (DevProblem::pm), loaded ahead of the knot loop; DT: and its own time steps (DevProblem::dtb; problem_dev.h step_dt_of)
+template <class M, int FIXED_INTEG, bool PM = false, bool DT = false>
 __global__ void __launch_bounds__(64) k_rollout(KArgs a) {  // src/problem.jl:334-340 — open-loop simulate from x0
   constexpr int n = M::n, m = M::m;
   TILE_LANE();
@@ -19,6 +20,7 @@ __global__ void __launch_bounds__(64) k_rollout(KArgs a) {  // src/problem.jl:33
   double pmr[PM ? 16 : 1];
   const double* mp = P.mp;
   if constexpr (PM) { load_plant(P, b, pmr); mp = pmr; }
+  const double* dt0 = dt_lane_of<DT>(P, b);
 #pragma unroll
   for (int i = 0; i < n; ++i) { x[i] = EL(x0, i); EL(X, i) = x[i]; }
   int lim = 0;  // first knot beyond max_state_value / max_control_value: the state it arrives at first, then the control (Altro's rollout!)
@@ -26,7 +28,7 @@ __global__ void __launch_bounds__(64) k_rollout(KArgs a) {  // src/problem.jl:33
   for (int k = 0; k < P.N - 1; ++k) {
 #pragma unroll
     for (int i = 0; i < m; ++i) u[i] = EL(U, k * m + i);
-    model_step<M, double, FIXED_INTEG>(mp, P.integrator, k, x, u, P.dt[k], xn);
+    model_step<M, double, FIXED_INTEG>(mp, P.integrator, k, x, u, step_dt_of<DT>(P, k, dt0), xn);
     double mx = 0.0, mu = 0.0;
 #pragma unroll
     for (int i = 0; i < n; ++i) { x[i] = xn[i]; EL(X, (k + 1) * n + i) = x[i]; const double v = fabs(x[i]); mx = !(v <= mx) ? v : mx; }
@@ -56,13 +58,14 @@ __global__ void __launch_bounds__(64) k_cost(KArgs a, int with_al, double* out, 
     const double* X = X_SLOT_PTR(a, b, c);
     const double* U = U_SLOT_PTR(a, b, c);
     double* o = TILE_PTR(Jk, N);
+    const double* dt0 = dt_lane(P, b);
     for (int k = 0; k < N; ++k) {
       double x[n], u[m];
 #pragma unroll
       for (int i = 0; i < n; ++i) x[i] = EL(X, k * n + i);
 #pragma unroll
       for (int i = 0; i < m; ++i) u[i] = (k < N - 1) ? EL(U, k * m + i) : 0.0;
-      EL(o, k) = knot_cost<M>(P, k, x, u, nullptr, nullptr, false, TILE_PTR(P.gl, P.n_costs * (n + m)));
+      EL(o, k) = knot_cost<M>(P, k, x, u, nullptr, nullptr, false, TILE_PTR(P.gl, P.n_costs * (n + m)), nullptr, nullptr, dt0);
     }
     return;
   }
@@ -183,7 +186,7 @@ __global__ void __launch_bounds__(64) k_outer_update(KArgs a) {
     con_shift<nz>(P, K, TILE_PTR(P.cp, P.n_cp), zc);
     con_dual_update<nz>(K, zc, lam, (size_t)64, EL(mu0, ci), P.opts.dual_max, TILE_PTR(P.cl, P.n_cl));
   }
-  EL(TILE_PTR(a.knotbuf, N), k) = knot_cost<M>(P, k, x, u, lam0, mn0, true, TILE_PTR(P.gl, P.n_costs * nz), TILE_PTR(P.cp, P.n_cp), TILE_PTR(P.cl, P.n_cl));
+  EL(TILE_PTR(a.knotbuf, N), k) = knot_cost<M>(P, k, x, u, lam0, mn0, true, TILE_PTR(P.gl, P.n_costs * nz), TILE_PTR(P.cp, P.n_cp), TILE_PTR(P.cl, P.n_cl), dt_lane(P, b));
 }
 
 template <class M>
@@ -236,7 +239,7 @@ __global__ void __launch_bounds__(64) k_cost_derivs(KArgs a, double* grad, doubl
     for (int i = 0; i < nz; ++i) v[i] = (i == j) ? 1.0 : 0.0;
     cost_grad_hvp<n, m>(P.costs[P.cost_index[k]], x, u, terminal, v, g, y);
     if (P.gl) goal_lin_grad<n, m>(TILE_PTR(P.gl, P.n_costs * nz), P.cost_index[k], terminal, g);
-    const double sc = (P.opts.cost_dt_scaling && !terminal) ? P.dt[k] : 1.0;
+    const double sc = (P.opts.cost_dt_scaling && !terminal) ? step_dt(P, k, dt_lane(P, b)) : 1.0;
 #pragma unroll
     for (int i = 0; i < nz; ++i) {
       if (hess) hess[(size_t)i + nz * ((size_t)j + nz * kb)] = sc * y[i];
@@ -246,7 +249,7 @@ __global__ void __launch_bounds__(64) k_cost_derivs(KArgs a, double* grad, doubl
 }
 
 // RD.jacobian! of the discretised dynamics on the full state: F[n, n+m, N-1, B]
-template <class M, bool PM = false>
+template <class M, bool PM = false, bool DT = false>
 __global__ void __launch_bounds__(64) k_discrete_jacobian(KArgs a, double* F) {
   constexpr int n = M::n, m = M::m, nz = n + m;
   TILE_LANE();
@@ -264,7 +267,7 @@ __global__ void __launch_bounds__(64) k_discrete_jacobian(KArgs a, double* F) {
   double pmr[PM ? 16 : 1];
   const double* mp = P.mp;
   if constexpr (PM) { load_plant(P, b, pmr); mp = pmr; }
-  model_step<M, Dual>(mp, P.integrator, k, xd, ud, P.dt[k], xn);
+  model_step<M, Dual>(mp, P.integrator, k, xd, ud, step_dt_of<DT>(P, k, dt_lane_of<DT>(P, b)), xn);
   const size_t kb = (size_t)k + (size_t)(N - 1) * b;
 #pragma unroll
   for (int i = 0; i < n; ++i) F[(size_t)i + n * ((size_t)j + nz * kb)] = xn[i].d;

@@ -210,14 +210,16 @@ PN_FN const double* pn_plant(const DevProblem& P, int b, double* buf) {
 }
 
 // defect arriving at knot k (ne): the initial condition at k = 0, f(x_{k-1}, u_{k-1}) (-) x_k otherwise
-// (PM: mp = the polished trajectory's own model parameters, DevProblem::pm; otherwise P.mp and the argument is not looked at)
-template <class M, bool PM = false>
-PN_FN void pn_defect(const DevProblem& P, int k, const double* zprev, const double* z, const double* x0, double* e, const double* mp = nullptr) {
+// (PM: mp = the polished trajectory's own model parameters, DevProblem::pm; DT: dt0 = that trajectory's own time steps, DevProblem::dtb
+// (problem_dev.h step_dt_of); otherwise P.mp / P.dt and the arguments are not looked at)
+template <class M, bool PM = false, bool DT = false>
+PN_FN void pn_defect(const DevProblem& P, int k, const double* zprev, const double* z, const double* x0, double* e, const double* mp = nullptr,
+                     const double* dt0 = nullptr) {
   constexpr int n = M::n;
   // branch-free in k (the lanes of a wave sit on different knots): the step is always taken, the operands selected
   const int kp = k > 0 ? k - 1 : 0;
   double f[n], a[n], b[n];
-  model_step<M, double>(PM ? mp : P.mp, P.integrator, kp, zprev, zprev + n, P.dt[kp], f);
+  model_step<M, double>(PM ? mp : P.mp, P.integrator, kp, zprev, zprev + n, step_dt_of<DT>(P, kp, dt0), f);
   for (int i = 0; i < n; ++i) { a[i] = (k == 0) ? z[i] : f[i]; b[i] = (k == 0) ? x0[i] : z[i]; }
   state_diff<M>(a, b, e);
 }
@@ -299,8 +301,9 @@ PN_FN double pn_reduce_max(const PnArgs& q, double* w, const PnLds& L PN_LANE_PA
 
 // d on the active set of the point Z (cand = false) or Zb (true), into d or dn.  refresh: choose the active set from the values
 // first.  Returns |d|_inf.
-template <class M, bool PM = false>
-PN_FN double pn_eval(const PnArgs& q, double* w, const PnLds& L, const double* x0, bool cand, bool refresh, int dst_vec PN_LANE_PARAM, const double* mp = nullptr) {
+template <class M, bool PM = false, bool DT = false>
+PN_FN double pn_eval(const PnArgs& q, double* w, const PnLds& L, const double* x0, bool cand, bool refresh, int dst_vec PN_LANE_PARAM, const double* mp = nullptr,
+                  const double* dt0 = nullptr) {
   constexpr int n = M::n, m = M::m, ne = M::ne, nz = n + m, nc = ne + m;
   const DevProblem& P = q.a.P;
   const int N = P.N;
@@ -312,7 +315,7 @@ PN_FN double pn_eval(const PnArgs& q, double* w, const PnLds& L, const double* x
     if (k > 0) { const PnRec<M> Rp = pn_rec<M>(q, w, k - 1); zp = cand ? Rp.Zb : Rp.Z; }
     double* dst = R.v(dst_vec);
     double e[ne], mx = 0.0;
-    pn_defect<M, PM>(P, k, zp, z, x0, e, mp);
+    pn_defect<M, PM, DT>(P, k, zp, z, x0, e, mp, dt0);
     for (int i = 0; i < ne; ++i) { dst[i] = e[i]; pn_upd_max(mx, fabs(e[i])); }
     unsigned long long mask = refresh ? 0ull : *R.mask;
     int na = 0;
@@ -341,11 +344,12 @@ PN_FN double pn_eval(const PnArgs& q, double* w, const PnLds& L, const double* x
 }
 
 // inverse metric of knot k, entry j of nc: 1 / (max(diag of the error-state OBJECTIVE Hessian, 0) + rho_primal)
-template <class M>
-PN_FN double pn_metric_dir(const DevProblem& P, int k, const double* z, bool terminal, int j) {
+// (DT: dt0 = the polished trajectory's own time steps, DevProblem::dtb; problem_dev.h step_dt_of)
+template <class M, bool DT = false>
+PN_FN double pn_metric_dir(const DevProblem& P, int k, const double* z, bool terminal, int j, const double* dt0 = nullptr) {
   constexpr int n = M::n, m = M::m, ne = M::ne, nz = n + m;
   CostC& C = P.costs[P.cost_index[k]];
-  const double sc = (P.opts.cost_dt_scaling && !terminal) ? P.dt[k] : 1.0;
+  const double sc = (P.opts.cost_dt_scaling && !terminal) ? step_dt_of<DT>(P, k, dt0) : 1.0;
   double v[nz], g[nz], y[nz];
   errstate_col<M>(z, j < ne ? j : 0, v);
   for (int i = 0; i < n; ++i) v[i] = (j < ne) ? v[i] : 0.0;
@@ -369,8 +373,8 @@ PN_FN double pn_metric_dir(const DevProblem& P, int k, const double* z, bool ter
 // Linearisation, item by item (one lane per item).  k_pn_lin_col, items [0, (N-1) nc): column j of the error-state Jacobian [A B]
 // of step k by a dual number through the RK stages (ForwardDiff-equivalent, like k_expand), stored in the record of the knot the
 // defect arrives at.  k_pn_lin_knot, one wave per knot: metric (lane = entry) and active constraint rows of the knot.
-template <class M, bool PM = false>
-PN_FN void pn_lin_column(const PnArgs& q, double* w, int it, const double* mp = nullptr) {
+template <class M, bool PM = false, bool DT = false>
+PN_FN void pn_lin_column(const PnArgs& q, double* w, int it, const double* mp = nullptr, const double* dt0 = nullptr) {
   constexpr int n = M::n, m = M::m, ne = M::ne, nz = n + m, nc = ne + m;
   const DevProblem& P = q.a.P;
   const int k = it / nc, j = it % nc;
@@ -382,7 +386,7 @@ PN_FN void pn_lin_column(const PnArgs& q, double* w, int it, const double* mp = 
   Dual xd[n], ud[m], xn[n];
   for (int i = 0; i < n; ++i) xd[i] = Dual(R.Z[i], v[i]);
   for (int i = 0; i < m; ++i) ud[i] = Dual(R.Z[n + i], v[n + i]);
-  model_step<M, Dual>(PM ? mp : P.mp, P.integrator, k, xd, ud, P.dt[k], xn);
+  model_step<M, Dual>(PM ? mp : P.mp, P.integrator, k, xd, ud, step_dt_of<DT>(P, k, dt0), xn);
   double y[n], col[ne];
   for (int i = 0; i < n; ++i) y[i] = xn[i].d;
   errstate_invmul<M>(Rn.Z, y, col);
@@ -821,7 +825,7 @@ PN_FN void pn_reg_solve(const PnArgs& q, double* w, const PnLds& L PN_LANE_PARAM
 // that is within constraint_tolerance, the budget of n_steps + 1 linearisations is spent (Altro projection_solve!: while count
 // <= n_steps) or the last factorisation failed: evaluate what the trajectory violates now (constraints as max_violation reports
 // them, and defects), write it back, set the status.  Otherwise the trajectory is ACTIVE for k_pn_lin / k_pn_project.
-template <class M, bool PM = false>
+template <class M, bool PM = false, bool DT = false>
 PN_FN void pn_begin(const PnArgs& q, int b, double* w, double* lds_mem, int round PN_LANE_PARAM) {
   constexpr int n = M::n, m = M::m, ne = M::ne, nz = n + m;
   const KArgs& a = q.a;
@@ -847,7 +851,8 @@ PN_FN void pn_begin(const PnArgs& q, int b, double* w, double* lds_mem, int roun
   const bool failed = w[PN_H_FAILED] != 0.0;
   double pmr[PM ? 16 : 1];  // PM: the polished trajectory's own model parameters (wave-uniform: one trajectory per workgroup)
   const double* mp = pn_plant<PM>(P, b, pmr);
-  const double viol = pn_eval<M, PM>(q, w, L, x0, false, true, PN_VD PN_LANE_ARG, mp);
+  const double* dt0 = dt_lane_of<DT>(P, b);
+  const double viol = pn_eval<M, PM, DT>(q, w, L, x0, false, true, PN_VD PN_LANE_ARG, mp, dt0);
   if (!(viol <= o.constraint_tolerance || round > o.n_steps || failed)) {
     PN_FOR(j, 1) { w[PN_H_STATE] = (double)PN_ACTIVE; w[PN_H_VIOL] = viol; }
     PN_SYNC();
@@ -857,7 +862,7 @@ PN_FN void pn_begin(const PnArgs& q, int b, double* w, double* lds_mem, int roun
     const PnRec<M> R = pn_rec<M>(q, w, k);
     const double* zp = pn_rec<M>(q, w, k > 0 ? k - 1 : 0).Z;
     double e[ne], mx = 0.0;
-    pn_defect<M, PM>(P, k, zp, R.Z, x0, e, mp);
+    pn_defect<M, PM, DT>(P, k, zp, R.Z, x0, e, mp, dt0);
     for (int i = 0; i < ne; ++i) pn_upd_max(mx, fabs(e[i]));
     if (P.n_cons > 0) pn_upd_max(mx, knot_violation<M>(P, k, R.Z, R.Z + n, pn_cp0(P, w), pn_cl0(P, w)));
     R.loc[0] = mx;
@@ -879,7 +884,7 @@ PN_FN void pn_begin(const PnArgs& q, int b, double* w, double* lds_mem, int roun
 }
 
 // ... second part, after the linearisation: Altro _projection_solve! on the frozen active set
-template <class M, bool PM = false>
+template <class M, bool PM = false, bool DT = false>
 PN_FN void pn_project(const PnArgs& q, int b, double* w, double* lds_mem PN_LANE_PARAM) {
   constexpr int n = M::n, m = M::m, ne = M::ne, nz = n + m;
   const KArgs& a = q.a;
@@ -896,6 +901,7 @@ PN_FN void pn_project(const PnArgs& q, int b, double* w, double* lds_mem PN_LANE
   const double viol = w[PN_H_VIOL];
   double pmr[PM ? 16 : 1];
   const double* mp = pn_plant<PM>(P, b, pmr);
+  const double* dt0 = dt_lane_of<DT>(P, b);
   PN_SYNC();  // every lane has read the header before lane 0 rewrites it
   PN_FOR(j, 1) w[PN_H_STEPS] += 1.0;
 #if defined(TO_PN_TIMING) && !defined(TO_PN_HOST)
@@ -923,7 +929,7 @@ PN_FN void pn_project(const PnArgs& q, int b, double* w, double* lds_mem PN_LANE
         for (int j = 0; j < m; ++j) R.Zb[n + j] = (k < N - 1) ? R.Z[n + j] + alpha * R.dZ[ne + j] : 0.0;
       }
       PN_SYNC();
-      { PN_TIC(); v = pn_eval<M, PM>(q, w, L, x0, true, false, PN_VDN PN_LANE_ARG, mp); PN_TOC(2); }
+      { PN_TIC(); v = pn_eval<M, PM, DT>(q, w, L, x0, true, false, PN_VDN PN_LANE_ARG, mp, dt0); PN_TOC(2); }
       if (v < viol_prev) { accepted = true; break; }
       alpha *= 0.5;
     }
@@ -946,47 +952,47 @@ PN_FN void pn_project(const PnArgs& q, int b, double* w, double* lds_mem PN_LANE
 }
 
 #ifndef TO_PN_HOST
-template <class M, bool PM = false>
+template <class M, bool PM = false, bool DT = false>  // (DT: the instance the launcher picks while DevProblem::dtb is set, ops_pn.h)
 __global__ void __launch_bounds__(64) k_pn_begin(PnArgs q, int round) {
   extern __shared__ double pn_lds_mem[];
   const int b = q.list[q.base + blockIdx.x];
-  pn_begin<M, PM>(q, b, q.ws + (size_t)blockIdx.x * (size_t)q.koff[q.a.P.N], pn_lds_mem, round, (int)threadIdx.x);
+  pn_begin<M, PM, DT>(q, b, q.ws + (size_t)blockIdx.x * (size_t)q.koff[q.a.P.N], pn_lds_mem, round, (int)threadIdx.x);
 }
-template <class M, bool PM = false>
+template <class M, bool PM = false, bool DT = false>
 __global__ void __launch_bounds__(64) k_pn_project(PnArgs q) {
   extern __shared__ double pn_lds_mem[];
   const int b = q.list[q.base + blockIdx.x];
-  pn_project<M, PM>(q, b, q.ws + (size_t)blockIdx.x * (size_t)q.koff[q.a.P.N], pn_lds_mem, (int)threadIdx.x);
+  pn_project<M, PM, DT>(q, b, q.ws + (size_t)blockIdx.x * (size_t)q.koff[q.a.P.N], pn_lds_mem, (int)threadIdx.x);
 }
 // grid (trajectories of the launch, ceil(items / 64)), EXEC full (a lane beyond the end repeats the last item).  Two kernels:
 // the dual-number RK step of the Quadrotor takes every register there is, the knot items (cost / constraint descriptors that
 // differ between the lanes' knots: lane-divergent branches) must not share its allocation (spill placement).
-template <class M, bool PM = false>
+template <class M, bool PM = false, bool DT = false>
 __global__ void __launch_bounds__(64) k_pn_lin_col(PnArgs q) {
   constexpr int nc = M::ne + M::m;
   double* w = q.ws + (size_t)blockIdx.x * (size_t)q.koff[q.a.P.N];
   if (w[PN_H_STATE] != (double)PN_ACTIVE) return;
   double pmr[PM ? 16 : 1];
   const double* mp = pn_plant<PM>(q.a.P, PM ? q.list[q.base + blockIdx.x] : 0, pmr);
-  pn_lin_column<M, PM>(q, w, min((int)(blockIdx.y * 64 + threadIdx.x), (q.a.P.N - 1) * nc - 1), mp);
+  pn_lin_column<M, PM, DT>(q, w, min((int)(blockIdx.y * 64 + threadIdx.x), (q.a.P.N - 1) * nc - 1), mp, dt_lane_of<DT>(q.a.P, DT ? q.list[q.base + blockIdx.x] : 0));
 }
 // one WAVE per knot (grid.y = N): the knot's cost and constraint descriptors are wave-uniform then — scalar loads, uniform
 // branches (with a lane per knot the dense-cost branches of lanes on differently-costed knots diverged around the register-hungry
 // ErrorQuadratic duals, exactly where hipcc's spill placement is unsafe: DESIGN.md §6).  Lane j < nc owns metric entry j; the
 // active rows are built by every lane alike (same values to the same addresses).
-template <class M>
+template <class M, bool DT = false>
 __global__ void __launch_bounds__(64) k_pn_lin_knot(PnArgs q) {
   constexpr int nc = M::ne + M::m;
   double* w = q.ws + (size_t)blockIdx.x * (size_t)q.koff[q.a.P.N];
   if (w[PN_H_STATE] != (double)PN_ACTIVE) return;
   const int k = blockIdx.y, j = min((int)threadIdx.x, nc - 1);
   const PnRec<M> R = pn_rec<M>(q, w, k);
-  R.W[j] = pn_metric_dir<M>(q.a.P, k, R.Z, k == q.a.P.N - 1, j);
+  R.W[j] = pn_metric_dir<M, DT>(q.a.P, k, R.Z, k == q.a.P.N - 1, j, dt_lane_of<DT>(q.a.P, DT ? q.list[q.base + blockIdx.x] : 0));
   pn_lin_rows<M>(q, w, k);
 }
 
 // max |x_1 (-) x0|, |f(x_k, u_k) (-) x_{k+1}| of the nominal trajectory (to_dynamics_defect): one lane per trajectory
-template <class M, bool PM = false>
+template <class M, bool PM = false, bool DT = false>
 __global__ void __launch_bounds__(64) k_defect(KArgs a, double* out) {
   constexpr int n = M::n, m = M::m, ne = M::ne;
   TILE_LANE();
@@ -999,13 +1005,14 @@ __global__ void __launch_bounds__(64) k_defect(KArgs a, double* out) {
   for (int i = 0; i < n; ++i) { x0[i] = EL(x0t, i); z[i] = EL(X, i); }
   double pmr[PM ? 16 : 1];
   const double* mp = pn_plant<PM>(P, b, pmr);
-  pn_defect<M, PM>(P, 0, z, z, x0, e, mp);
+  const double* dt0 = dt_lane_of<DT>(P, b);
+  pn_defect<M, PM, DT>(P, 0, z, z, x0, e, mp, dt0);
   for (int i = 0; i < ne; ++i) pn_upd_max(mx, fabs(e[i]));
   for (int k = 1; k < P.N; ++k) {
     for (int i = 0; i < n; ++i) zp[i] = z[i];
     for (int i = 0; i < m; ++i) zp[n + i] = EL(U, (k - 1) * m + i);
     for (int i = 0; i < n; ++i) z[i] = EL(X, k * n + i);
-    pn_defect<M, PM>(P, k, zp, z, x0, e, mp);
+    pn_defect<M, PM, DT>(P, k, zp, z, x0, e, mp, dt0);
     for (int i = 0; i < ne; ++i) pn_upd_max(mx, fabs(e[i]));
   }
   out[b] = mx;

@@ -52,7 +52,17 @@ struct PolicyKnot {
   }
 };
 
-template <class M, bool UNIFORM, int FI, int NZ = 0>
+// objective value of one stage knot; DT (a handle with per-trajectory time steps, DevProblem::dtb): scaled by the trajectory's own step
+template <class M, bool DT>
+__device__ __forceinline__ double policy_knot_cost(const DevProblem& P, int k, const double* x, const double* u, const double* gl0, const double* cp0,
+                                                   [[maybe_unused]] const double* dt0) {
+  if constexpr (DT) return knot_cost<M, true>(P, k, x, u, nullptr, nullptr, false, gl0, cp0, nullptr, dt0);
+  else return knot_cost<M, true>(P, k, x, u, nullptr, nullptr, false, gl0, cp0);
+}
+
+// DT: sample c steps by the time steps of ITS trajectory b (DevProblem::dtb).  A handle with per-trajectory steps always runs a one-plant-per-
+// sample instance (NZ bit 2), and its launcher picks DT = true (ops.h; problem_dev.h step_dt_of)
+template <class M, bool UNIFORM, int FI, int NZ = 0, bool DT = false>
 __global__ void __launch_bounds__(64) k_policy_rollout(KArgs a, PolicyArgs pa) {
   constexpr bool NOISE_W = (NZ & 1) != 0, NOISE_V = (NZ & 2) != 0, LANE_PLANT = (NZ & 4) != 0;
   constexpr int n = M::n, m = M::m, ne = M::ne, RSK = Gains<M>::RSK;
@@ -81,6 +91,7 @@ __global__ void __launch_bounds__(64) k_policy_rollout(KArgs a, PolicyArgs pa) {
   const double* gl0 = TILE_PTR(P.gl, P.n_costs * (n + m));
   const double* cp0 = TILE_PTR(P.cp, P.n_cp);
   const double* cl0 = TILE_PTR(P.cl, P.n_cl);
+  const double* dt0 = dt_lane_of<DT>(P, b);
   double mp[16];  // the PLANT's parameters; the law's x̄, ū, K, d are the planning model's
   if constexpr (LANE_PLANT) {
     const double* pp = pa.plants + c * 16;
@@ -154,9 +165,9 @@ __global__ void __launch_bounds__(64) k_policy_rollout(KArgs a, PolicyArgs pa) {
       if (store) EL(pUo, j) = uj;
     }
     pUo += m * 64;
-    J += knot_cost<M, true>(P, k, xb, ub, nullptr, nullptr, false, gl0, cp0);
+    J += policy_knot_cost<M, DT>(P, k, xb, ub, gl0, cp0, dt0);
     if (has_cons) { const double v = knot_violation<M>(P, k, xb, ub, cp0, cl0); if (!(v <= cm)) cm = v; }
-    model_step<M, double, FI>(mp, integrator, k, xb, ub, P.dt[k], xn);
+    model_step<M, double, FI>(mp, integrator, k, xb, ub, step_dt_of<DT>(P, k, dt0), xn);
     if constexpr (NOISE_W) {  // x_{k+1} = state_add(f(x_k, u_k), w_k): no dt scaling; the limit test below sees the noisy state
       double w[ne], xf[n];
 #pragma unroll

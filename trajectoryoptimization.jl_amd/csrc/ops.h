@@ -53,7 +53,9 @@ int with_variant(const to_handle* h, F&& body) {
 // (PM, here and below: the flagged instance that loads one plant per trajectory, DevProblem::pm — instantiated by the ops_plants_*.hip units)
 template <class M, bool PM = false>
 int op_rollout(to_handle* h) {
-  return with_integrator<M>(h, [&](auto fi) { return launch(k_rollout<M, decltype(fi)::value, PM>, grid_b(h), dim3(BLOCK), 0, h->stream, h->a); });
+  return with_integrator<M>(h, [&](auto fi) {
+    return with_time_steps<M, PM>(h, [&](auto dt) { return launch(k_rollout<M, decltype(fi)::value, PM, decltype(dt)::value>, grid_b(h), dim3(BLOCK), 0, h->stream, h->a); });
+  });
 }
 template <class M>
 int op_cost(to_handle* h, int with_al, double* out, double* Jk) {
@@ -83,7 +85,7 @@ int op_cost_derivs(to_handle* h, double* dg, double* dh) {
 template <class M, bool PM = false>
 int op_discrete_jacobian(to_handle* h, double* F) {
   const DevProblem& P = h->a.P;
-  return launch(k_discrete_jacobian<M, PM>, grid_b(h, P.N - 1, P.n + P.m), dim3(BLOCK), 0, h->stream, h->a, F);
+  return with_time_steps<M, PM>(h, [&](auto dt) { return launch(k_discrete_jacobian<M, PM, decltype(dt)::value>, grid_b(h, P.N - 1, P.n + P.m), dim3(BLOCK), 0, h->stream, h->a, F); });
 }
 template <class M>
 int op_constraint_eval(to_handle* h, int ci, double* vals, double* jac) {
@@ -143,14 +145,17 @@ int op_expand_pm(to_handle* h) {
   const dim3 grid((P.B + h->G - 1) / h->G, (P.N + kc - 1) / kc);
   if (h->a.bwd_lane || h->a.h_compact) return fail(TO_ERR_UNSUPPORTED, "per-trajectory model parameters: expansion layout without a flagged instance");
   return with_integrator<M>(h, [&](auto fi) {
-    constexpr int FI = decltype(fi)::value;
-    if constexpr (M::mfma_backward) {
-      if (h->a.bwd_mfma) return launch(k_expand<M, FI, 7, 1, false, true>, grid, dim3(BLOCK), 0, h->stream, h->a);
-    }
-    if constexpr (!M::mfma_backward || M::coop_backward) {
-      if (!h->a.bwd_mfma) return launch(k_expand<M, FI, 7, 0, false, true>, grid, dim3(BLOCK), 0, h->stream, h->a);
-    }
-    return fail(TO_ERR_UNSUPPORTED, "per-trajectory model parameters: expansion not compiled for this model and layout");
+    return with_time_steps<M, true>(h, [&](auto dt) {
+      constexpr int FI = decltype(fi)::value;
+      constexpr bool DT = decltype(dt)::value;
+      if constexpr (M::mfma_backward) {
+        if (h->a.bwd_mfma) return launch(k_expand<M, FI, 7, 1, false, true, DT>, grid, dim3(BLOCK), 0, h->stream, h->a);
+      }
+      if constexpr (!M::mfma_backward || M::coop_backward) {
+        if (!h->a.bwd_mfma) return launch(k_expand<M, FI, 7, 0, false, true, DT>, grid, dim3(BLOCK), 0, h->stream, h->a);
+      }
+      return fail(TO_ERR_UNSUPPORTED, "per-trajectory model parameters: expansion not compiled for this model and layout");
+    });
   });
 }
 template <class M>
@@ -213,7 +218,10 @@ int op_forward(to_handle* h) {
   const KArgs& a = h->a;
   const int TW = a.TW;
   const size_t lds = M::lds_gains ? sizeof(double) * (2 * gains_lds_doubles<M>(TW) + StageCostLds<M::n, M::m>::size) : 0;  // two gains buffers + the stage-cost table
-  return launch(k_forward<M, MODE>, dim3((a.P.Bp + TW - 1) / TW), dim3(BLOCK), lds, h->stream, a);
+  // (the flagged variants, bit 5, with per-trajectory time steps: bit 6)
+  return with_time_steps<M, (MODE & 32) != 0>(h, [&](auto dt) {
+    return launch(k_forward<M, (MODE | (decltype(dt)::value ? 64 : 0))>, dim3((a.P.Bp + TW - 1) / TW), dim3(BLOCK), lds, h->stream, a);
+  });
 }
 
 // accepted steps re-rolled from their stored controls (k_accept_roll; models without write-through)
@@ -230,9 +238,12 @@ int op_policy_rollout(to_handle* h, const PolicyArgs& pa, int waves) {
   const bool uniform = pa.TPW == 0;
   const size_t lds = M::lds_gains ? sizeof(double) * 2 * gains_lds_doubles<M>(uniform ? 1 : pa.TPW) : 0;  // two gains buffers
   return with_integrator<M>(h, [&](auto fi) {
-    constexpr int FI = decltype(fi)::value;
-    if (uniform) return launch(k_policy_rollout<M, true, FI, NZ>, dim3(waves), dim3(BLOCK), lds, h->stream, h->a, pa);
-    return launch(k_policy_rollout<M, false, FI, NZ>, dim3(waves), dim3(BLOCK), lds, h->stream, h->a, pa);
+    return with_time_steps<M, (NZ & 4) != 0>(h, [&](auto dt) {  // (a handle with per-trajectory time steps runs a one-plant-per-sample instance)
+      constexpr int FI = decltype(fi)::value;
+      constexpr bool DT = decltype(dt)::value;
+      if (uniform) return launch(k_policy_rollout<M, true, FI, NZ, DT>, dim3(waves), dim3(BLOCK), lds, h->stream, h->a, pa);
+      return launch(k_policy_rollout<M, false, FI, NZ, DT>, dim3(waves), dim3(BLOCK), lds, h->stream, h->a, pa);
+    });
   });
 }
 

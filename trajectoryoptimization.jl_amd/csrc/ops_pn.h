@@ -20,18 +20,21 @@ int op_pn_launch(to_handle* h, int slot0, int count, hipStream_t stream, const t
   const size_t lds = sizeof(double) * (size_t)pn_lds_doubles<M>(q.nbmax);
   constexpr int nc = M::ne + M::m;
   const int col_blocks = ((N - 1) * nc + 63) / 64, knot_blocks = N;
-  for (int round = 0; round <= opts->n_steps; ++round) {  // (n_steps >= 0: desc_lower.h) n_steps + 2 rounds, the last one its begin only
-    enqueue(k_pn_begin<M, PM>, dim3(count), dim3(64), lds, stream, q, round);
-    enqueue(k_pn_lin_col<M, PM>, dim3(count, col_blocks), dim3(64), 0, stream, q);
-    enqueue(k_pn_lin_knot<M>, dim3(count, knot_blocks), dim3(64), 0, stream, q);
-    enqueue(k_pn_project<M, PM>, dim3(count), dim3(64), lds, stream, q);
-  }
-  return launch(k_pn_begin<M, PM>, dim3(count), dim3(64), lds, stream, q, opts->n_steps + 1);
+  return with_time_steps<M, PM>(h, [&](auto dt) {  // (DT: the flagged kernels on a handle with per-trajectory time steps, ops.h)
+    constexpr bool DT = decltype(dt)::value;
+    for (int round = 0; round <= opts->n_steps; ++round) {  // (n_steps >= 0: desc_lower.h) n_steps + 2 rounds, the last one its begin only
+      enqueue(k_pn_begin<M, PM, DT>, dim3(count), dim3(64), lds, stream, q, round);
+      enqueue(k_pn_lin_col<M, PM, DT>, dim3(count, col_blocks), dim3(64), 0, stream, q);
+      enqueue(k_pn_lin_knot<M, DT>, dim3(count, knot_blocks), dim3(64), 0, stream, q);
+      enqueue(k_pn_project<M, PM, DT>, dim3(count), dim3(64), lds, stream, q);
+    }
+    return launch(k_pn_begin<M, PM, DT>, dim3(count), dim3(64), lds, stream, q, opts->n_steps + 1);
+  });
 }
 
 template <class M, bool PM = false>
 int op_defect(to_handle* h, double* out) {
-  return launch(k_defect<M, PM>, grid_b(h), dim3(BLOCK), 0, h->stream, h->a, out);
+  return with_time_steps<M, PM>(h, [&](auto dt) { return launch(k_defect<M, PM, decltype(dt)::value>, grid_b(h), dim3(BLOCK), 0, h->stream, h->a, out); });
 }
 
 }  // namespace to

@@ -241,12 +241,18 @@ inline void path_report(const PathPlan& p, const PathTraits& t, int h_diag, int 
 // PARAMETERS (con_params: DevProblem::cp) do: bit 2 forced — expansion variant 7, forward `mode | 8` — which rules out the scan kernel, the fused
 // cooperative kernel and the packed Quadrotor expansion; compaction, the fused lane kernel and the repacked working set stay as the plan has them
 // (the repacked set carries cl the way it carries cp, trajopt_hip.hip rp_setup).
+// Per-trajectory TIME STEPS (time_steps: DevProblem::dtb set, to_set_time_steps_batch) ride on the flagged instances that load one plant per
+// trajectory — only they read the step per trajectory — so such a handle IS a `plants` handle to every predicate above (routed_as_plants),
+// whether or not the caller also gave each trajectory its own plant.
 struct TableFlags {
   bool dense_costs = false, cons = false, non_selector = false;  // from the descriptors
   bool con_params = false, con_limits = false, plants = false;   // a constraint flagged for cp / for cl; DevProblem::pm set
+  bool time_steps = false;                                       // DevProblem::dtb set
 };
+inline bool routed_as_plants(bool plants /* pm */, bool time_steps /* dtb */) { return plants || time_steps; }
+inline bool routed_as_plants(const TableFlags& f) { return routed_as_plants(f.plants, f.time_steps); }
 inline int expand_variant_of(const TableFlags& f) {
-  return (f.dense_costs ? 1 : 0) | (f.cons ? 2 : 0) | ((f.non_selector || f.con_params || f.con_limits || f.plants) ? 4 : 0);
+  return (f.dense_costs ? 1 : 0) | (f.cons ? 2 : 0) | ((f.non_selector || f.con_params || f.con_limits || routed_as_plants(f)) ? 4 : 0);
 }
 inline bool forward_general(int expand_variant, bool cost_terms /* gl */, bool con_params /* cp */, bool con_limits /* cl */) {
   return (expand_variant & 5) != 0 || cost_terms || con_params || con_limits;

@@ -74,6 +74,11 @@ struct DevProblem {
   // flagged only while cl is set.  NULL (the default): every trajectory shares the descriptors.  Read by the GENERAL kernel variants only.
   const double* cl;
   int n_cl;
+  // Per-trajectory time steps (to_set_time_steps_batch: one horizon per trajectory): tiled array, L = N - 1; step k of trajectory b sits at
+  // dtb[((b >> 6) * (N - 1) + k) * 64 + (b & 63)] and is read exactly where a handle on shared steps reads dt[k].  NULL (the default): every
+  // trajectory steps by dt.  While it is set pm is set too (the shared plant repeated when the caller gave none): the time step rides on the
+  // flagged (PM) kernel instances, and on a wave-uniform branch in the cost kernels that have no such instance.
+  const double* dtb;
 };
 
 // The 16 model parameters of trajectory b into registers (the flagged kernel instances, once, ahead of their knot loops): indexed by the
@@ -82,6 +87,33 @@ __device__ __forceinline__ void load_plant(const DevProblem& P, int b, double* m
   const double* pp = P.pm + ((size_t)(b >> 6) * 16) * 64 + (b & 63);
 #pragma unroll
   for (int i = 0; i < 16; ++i) mp[i] = pp[(size_t)i * 64];
+}
+
+// This lane's pointer to step 0 of trajectory b in DevProblem::dtb (null while the steps are shared): indexed by the TRAJECTORY, like load_plant.
+__device__ __forceinline__ const double* dt_lane(const DevProblem& P, int b) {
+  return P.dtb != nullptr ? P.dtb + ((size_t)(b >> 6) * (size_t)(P.N - 1)) * 64 + (b & 63) : nullptr;
+}
+// The time step of knot k as this lane's trajectory sees it.  dt0: what dt_lane returned — or nothing: the callers that pass no pointer (every
+// kernel instance a handle with per-trajectory steps never runs) compile to the descriptor read they always had.  The branch is wave-uniform
+// (P.dtb is a kernel argument), as con_shift's is, and its not-taken side is that read.
+__device__ __forceinline__ double step_dt(const DevProblem& P, int k, std::nullptr_t) { return P.dt[k]; }
+__device__ __forceinline__ double step_dt(const DevProblem& P, int k, const double* dt0) {
+  if (P.dtb != nullptr) return dt0[(size_t)k * 64];
+  return P.dt[k];
+}
+// ... and in the flagged kernels, which exist twice: DT = false, the instance a handle with plants alone runs — the code it always was — and
+// DT = true, the one the launcher picks while P.dtb is set (ops.h; the ModelOps table does not grow).  A branch on P.dtb inside those kernels'
+// knot loops splits basic blocks, hipcc's default floating-point contraction then pairs other products with other sums, and a handle with
+// plants alone must keep computing the bits it computed before the steps existed (tests/test_gpu_time_steps.py holds it to a recorded fixture).
+template <bool DT>
+__device__ __forceinline__ const double* dt_lane_of(const DevProblem& P, [[maybe_unused]] int b) {
+  if constexpr (DT) return P.dtb + ((size_t)(b >> 6) * (size_t)(P.N - 1)) * 64 + (b & 63);
+  else return nullptr;
+}
+template <bool DT>
+__device__ __forceinline__ double step_dt_of(const DevProblem& P, int k, [[maybe_unused]] const double* dt0) {
+  if constexpr (DT) return dt0[(size_t)k * 64];
+  else return P.dt[k];
 }
 
 // z = [x; u] as constraint K sees it for this lane's trajectory (cp0: the lane's pointer to entry 0 of DevProblem::cp; blocks of nz = n + m)

@@ -238,6 +238,7 @@ int upload_tables(to_handle* h) {
       tf.non_selector = tf.non_selector || !c.selector; tf.con_params = tf.con_params || c.cp_off >= 0; tf.con_limits = tf.con_limits || c.cl_off >= 0;
     }
     tf.plants = P.pm != nullptr;  // ... and per-trajectory model parameters by the flagged instances of the general variants only
+    tf.time_steps = P.dtb != nullptr;  // ... on which per-trajectory time steps ride
     P.expand_variant = expand_variant_of(tf);  // (path_plan.h)
     // unit-SOC forward-pass variants (problem_dev.h unit_soc_desc): at least one control-block constraint, and all of them unit
     bool any_ctrl = false, all_unit = true;
@@ -269,7 +270,8 @@ int launch_set_active(to_handle* h, int v, int clear_bpfail = 1) {
   return launch(k_set_active, grid_b(h), dim3(BLOCK), 0, h->stream, h->a, v, clear_bpfail);
 }
 // THE plants choice: DevProblem::pm set — one plant per trajectory — selects entry [1] of the kernels that read model parameters (handle.h ModelOps)
-inline int plants(const to_handle* h) { return h->a.P.pm != nullptr; }
+// (per-trajectory time steps, DevProblem::dtb, ride on the same entries: path_plan.h routed_as_plants; pm is set while dtb is)
+inline int plants(const to_handle* h) { return routed_as_plants(h->a.P.pm != nullptr, h->a.P.dtb != nullptr) ? 1 : 0; }
 int launch_rollout(to_handle* h) { return h->ops->rollout[plants(h)](h); }
 int launch_defect(to_handle* h, double* out) { return h->ops->defect[plants(h)](h, out); }
 int launch_pn(to_handle* h, int slot0, int count, hipStream_t stream, const to_solver_opts* opts) {
@@ -293,7 +295,7 @@ int launch_accept(to_handle* h) {  // materialise accepted candidate slots on sl
 // per-trajectory state machine (k_forward.h), in the kernel variant path_plan.h forward_mode picks
 int launch_forward(to_handle* h, bool accept = true, bool two_wave = false) {
   const DevProblem& P = h->a.P;  // (the general variants also with per-trajectory linear cost terms / constraint parameters: only they read them)
-  if (P.pm) {  // one plant per trajectory: the general variants that load it per trajectory, as one-wave workgroups (stage cost read per knot)
+  if (plants(h)) {  // one plant per trajectory: the general variants that load it per trajectory, as one-wave workgroups (stage cost read per knot)
     const int pmode = forward_mode(false, P.n_cons > 0, P.integrator == INTEG_RK4, true, false, h->traits.forward_plants);
     if (pmode < 0) return fail(TO_ERR_UNSUPPORTED, "forward-pass variant with per-trajectory model parameters not compiled for this model");
     TRY(h->ops->forward[1][pmode](h));
@@ -671,7 +673,7 @@ int solve_impl(to_handle* h, to_solve_stats* st, int al_mode) {
   a.al_mode = al_mode;
   a.control = 1;
   h->rp_arr.clear();  // the table of carried arrays is rebuilt per solve (per-trajectory cost terms may have appeared)
-  a.compact = solve_compact(h->plan, P.pm != nullptr);
+  a.compact = solve_compact(h->plan, plants(h) != 0);
   const int max_steps = (al_mode ? P.opts.iterations_total : P.opts.iterations) + 1;
   if (h->counter_len < max_steps) {
     int* c = nullptr;
@@ -716,7 +718,7 @@ int solve_impl(to_handle* h, to_solve_stats* st, int al_mode) {
       if (h->profile) HIPCHECK(hipEventRecord(h->ev[4 * step + 0], h->stream));
       // what this step launches (path_plan.h), from the last active count the host has seen (results do not depend on it)
       const PathPlan& pl = h->plan;
-      const StepPlan sp = plan_step(pl, h->traits, a.h_diag, P.expand_variant, a.compact, last_active, P.B, P.pm != nullptr);
+      const StepPlan sp = plan_step(pl, h->traits, a.h_diag, P.expand_variant, a.compact, last_active, P.B, plants(h) != 0);
       if (sp.kind == STEP_SPLIT) TRY(launch_expand(h));
       if (h->profile) HIPCHECK(hipEventRecord(h->ev[4 * step + 1], h->stream));
       switch (sp.kind) {
@@ -767,7 +769,7 @@ int solve_impl(to_handle* h, to_solve_stats* st, int al_mode) {
   int early_thr = (al_mode && h->pn_early > 0) ? P.B / early_div : -1, early_left = h->pn_early;
   bool snapshot_pending = false;
   // repacked working set (above): iLQR solves of the small models on the fused lane path with compaction
-  bool repack = !al_mode && a.compact && working_set_repack(h->plan, h->traits, P.pm != nullptr);
+  bool repack = !al_mode && a.compact && working_set_repack(h->plan, h->traits, plants(h) != 0);
   if (max_steps > 0) TRY(enqueue_chunk());
   while (!done && waited < nchunks) {
     if (repack && last_active >= 1 && (double)last_active <= h->plan.rp_at * (double)a.P.B && a.P.B >= h->plan.rp_min) {
@@ -1114,7 +1116,7 @@ void* to_stream(to_handle* h) { return h ? (void*)h->stream : nullptr; }
 
 int to_solver_path(const to_handle* h, int32_t* info) {
   CHECK_H(h); CHECK_P(info);
-  path_report(h->plan, h->traits, h->a.h_diag, h->a.P.expand_variant, h->a.P.B, info, h->a.P.pm != nullptr);
+  path_report(h->plan, h->traits, h->a.h_diag, h->a.P.expand_variant, h->a.P.B, info, plants(h) != 0);
   return TO_OK;
 }
 int to_knot_dims(const to_handle* h, int32_t* nx, int32_t* nu) {
@@ -1413,6 +1415,30 @@ static int model_params_supported(const to_handle* h, const char* who) {
                                         " (double integrator, Cartpole and quaternion Quadrotor only)");
   return TO_OK;
 }
+// params[16, B] (NULL: the shared parameters for every trajectory) -> DevProblem::pm and its host copy
+static int upload_plants(to_handle* h, const double* params) {
+  DevProblem& P = h->a.P;
+  const int B = P.B;
+  const size_t tiles = (size_t)P.Bp / 64 + 1;  // (+ one spare tile, like the nominal states)
+  if (!h->d_pm) TRY(dev_alloc(h, &h->d_pm, tiles * 16 * 64));
+  // tiled on the host; lanes behind the batch carry the shared parameters (idle lanes compute along on valid data)
+  std::vector<double> tiled(tiles * 16 * 64);
+  for (size_t t = 0; t < tiles; ++t)
+    for (int i = 0; i < 16; ++i)
+      for (int l = 0; l < 64; ++l) {
+        const size_t b = t * 64 + l;
+        tiled[(t * 16 + i) * 64 + l] = (params && b < (size_t)B) ? params[16 * b + i] : P.mp[i];
+      }
+  HIPCHECK(hipMemcpyAsync(h->d_pm, tiled.data(), tiled.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  HIPCHECK(hipStreamSynchronize(h->stream));
+  if (params) h->pm_host.assign(params, params + (size_t)16 * B);
+  else {
+    h->pm_host.resize((size_t)16 * B);
+    for (int b = 0; b < B; ++b) std::memcpy(&h->pm_host[(size_t)16 * b], P.mp, sizeof(double) * 16);
+  }
+  P.pm = h->d_pm;
+  return TO_OK;
+}
 int to_set_model_params_batch(to_handle* h, const double* params) {
   CHECK_H(h); CHECK_IDLE(h); CHECK_P(params); TRY(use_device(h));
   TRY(model_params_supported(h, "to_set_model_params_batch"));
@@ -1427,20 +1453,8 @@ int to_set_model_params_batch(to_handle* h, const double* params) {
     if (!ok) return fail(TO_ERR_ARGUMENT, "to_set_model_params_batch: the parameters of trajectory " + std::to_string(b) +
                                               " change the model's dimensions or attitude representation");
   }
-  const size_t tiles = (size_t)P.Bp / 64 + 1;  // (+ one spare tile, like the nominal states)
-  if (!h->d_pm) TRY(dev_alloc(h, &h->d_pm, tiles * 16 * 64));
-  // tiled on the host; lanes behind the batch carry the shared parameters (idle lanes compute along on valid data)
-  std::vector<double> tiled(tiles * 16 * 64);
-  for (size_t t = 0; t < tiles; ++t)
-    for (int i = 0; i < 16; ++i)
-      for (int l = 0; l < 64; ++l) {
-        const size_t b = t * 64 + l;
-        tiled[(t * 16 + i) * 64 + l] = b < (size_t)B ? params[16 * b + i] : P.mp[i];
-      }
-  HIPCHECK(hipMemcpyAsync(h->d_pm, tiled.data(), tiled.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  HIPCHECK(hipStreamSynchronize(h->stream));
-  h->pm_host.assign(params, params + (size_t)16 * B);
-  P.pm = h->d_pm;
+  TRY(upload_plants(h, params));
+  h->pm_own = true;
   TRY(upload_tables(h));  // (expand_variant bit 2, and with it the compact cost block, follow pm)
   return check_guards(h, "to_set_model_params_batch");
 }
@@ -1455,8 +1469,52 @@ int to_get_model_params_batch(to_handle* h, double* params) {
 int to_clear_model_params_batch(to_handle* h) {
   CHECK_H(h); CHECK_IDLE(h); TRY(use_device(h));
   TRY(model_params_supported(h, "to_clear_model_params_batch"));
-  h->a.P.pm = nullptr;
-  h->pm_host.clear();
+  h->pm_own = false;
+  if (h->a.P.dtb) TRY(upload_plants(h, nullptr));  // per-trajectory time steps ride on the flagged instances: pm stays, on the shared plant
+  else { h->a.P.pm = nullptr; h->pm_host.clear(); }
+  return upload_tables(h);
+}
+
+// One set of time steps per TRAJECTORY (DevProblem::dtb): dt[(N-1), B], knot fastest.  Validation and tiling are host-only code
+// (desc_lower.h lower_time_steps).  The time step rides on the flagged instances that load one plant per trajectory: while
+// dtb is set pm is set too — the shared plant repeated unless to_set_model_params_batch gave each trajectory its own — so the handle is
+// routed exactly as one with `plants` (path_plan.h) and every launcher picks entry [1]; X, U, duals and gains are left as they are.
+static int time_steps_supported(const to_handle* h, const char* who) {
+  if (h->model_key > 4 || !h->ops->plants(h->a.bwd_lane != 0))
+    return fail(TO_ERR_UNSUPPORTED, std::string(who) + ": per-trajectory time steps are not available for the " + model_key_name(h->model_key) +
+                                        " (double integrator, Cartpole and quaternion Quadrotor only)");
+  return TO_OK;
+}
+int to_set_time_steps_batch(to_handle* h, const double* dt) {
+  CHECK_H(h); CHECK_IDLE(h); CHECK_P(dt); TRY(use_device(h));
+  TRY(time_steps_supported(h, "to_set_time_steps_batch"));
+  DevProblem& P = h->a.P;
+  std::vector<double> tiled;
+  TRY(lower_time_steps(P.N, P.B, P.Bp, dt, h->dt.data(), &tiled));
+  if (!h->d_dtb) TRY(dev_alloc(h, &h->d_dtb, tiled.size()));
+  HIPCHECK(hipMemcpyAsync(h->d_dtb, tiled.data(), tiled.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  HIPCHECK(hipStreamSynchronize(h->stream));
+  if (!P.pm) TRY(upload_plants(h, nullptr));
+  h->dtb_host.assign(dt, dt + (size_t)(P.N - 1) * P.B);
+  P.dtb = h->d_dtb;
+  TRY(upload_tables(h));
+  return check_guards(h, "to_set_time_steps_batch");
+}
+int to_get_time_steps_batch(to_handle* h, double* dt) {
+  CHECK_H(h); CHECK_IDLE(h); CHECK_P(dt);
+  TRY(time_steps_supported(h, "to_get_time_steps_batch"));
+  const DevProblem& P = h->a.P;
+  const size_t L = (size_t)P.N - 1;
+  if (P.dtb) std::memcpy(dt, h->dtb_host.data(), sizeof(double) * L * P.B);
+  else for (int b = 0; b < P.B; ++b) std::memcpy(dt + L * b, h->dt.data(), sizeof(double) * L);
+  return TO_OK;
+}
+int to_clear_time_steps_batch(to_handle* h) {
+  CHECK_H(h); CHECK_IDLE(h); TRY(use_device(h));
+  TRY(time_steps_supported(h, "to_clear_time_steps_batch"));
+  h->a.P.dtb = nullptr;
+  h->dtb_host.clear();
+  if (!h->pm_own) { h->a.P.pm = nullptr; h->pm_host.clear(); }
   return upload_tables(h);
 }
 
@@ -1496,7 +1554,7 @@ int to_expand(to_handle* h) {
 static int phase_backward(to_handle* h) {
   TRY(launch_set_active(h, 1));
   const DevProblem& P = h->a.P;
-  if (h->plan.scan == 2 && scan_now(h->plan, h->a.h_diag, P.expand_variant, P.pm != nullptr)) {
+  if (h->plan.scan == 2 && scan_now(h->plan, h->a.h_diag, P.expand_variant, plants(h) != 0)) {
     // TRAJOPT_SCAN=2 (tests): the phase API runs the solve loop's scan kernel so that its gains can be read back and compared
     // (it expands on its own: to_expand's arrays are not used)
     TRY(h->ops->expand_backward_scan(h));
@@ -1570,10 +1628,13 @@ static int policy_rollout_impl(to_handle* h, int32_t S, const double* x0s, const
   // the host fills the per-sample plants array and the one-plant-per-sample instance runs (an explicit plant, shared or per sample, overrides)
   const double* plants_src = (noise && noise->plant_params) ? noise->plant_params : nullptr;
   std::vector<double> own_plants;
-  if (P.pm && !o.plant_params && !plants_src) {
+  // (a handle with per-trajectory time steps, DevProblem::dtb, always takes a one-plant-per-sample instance — only those read the steps per
+  // trajectory — so there an explicit shared plant is repeated for every sample)
+  if (P.pm && !plants_src && (!o.plant_params || P.dtb)) {
     own_plants.resize((size_t)16 * S * B);
     for (int b = 0; b < B; ++b)
-      for (int s = 0; s < S; ++s) std::memcpy(&own_plants[((size_t)b * S + s) * 16], &h->pm_host[(size_t)16 * b], sizeof(double) * 16);
+      for (int s = 0; s < S; ++s)
+        std::memcpy(&own_plants[((size_t)b * S + s) * 16], o.plant_params ? o.plant_params : &h->pm_host[(size_t)16 * b], sizeof(double) * 16);
     plants_src = own_plants.data();
     nz |= 4;
   }
