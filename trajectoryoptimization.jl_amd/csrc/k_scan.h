@@ -29,144 +29,47 @@
 #include "common.h"
 #include "k_backward.h"
 #include "k_expand.h"
+#include "scan_combine.h"
 
 namespace to {
 
-template <int n>
-struct ScanEl {
-  static constexpr int NSY = n * (n + 1) / 2;
-  static constexpr int NV = n * n + 2 * n + 2 * NSY;  // doubles per element
-  double A[n * n], b[n], C[NSY], eta[n], J[NSY];
-  __device__ __forceinline__ static constexpr int sy(int i, int j) { return i <= j ? j * (j + 1) / 2 + i : i * (i + 1) / 2 + j; }
-  __device__ __forceinline__ void identity() {
-#pragma unroll
-    for (int i = 0; i < n; ++i) {
-#pragma unroll
-      for (int j = 0; j < n; ++j) A[i * n + j] = (i == j) ? 1.0 : 0.0;
-      b[i] = 0.0; eta[i] = 0.0;
-    }
-#pragma unroll
-    for (int i = 0; i < NSY; ++i) { C[i] = 0.0; J[i] = 0.0; }
-  }
-};
-
-// in-place solve M X = R (M n x n general, R n x r), no pivoting: M = I + (PSD)(PSD) has eigenvalues >= 1
-template <int n, int r>
-__device__ __forceinline__ void scan_lu_solve(double (&Mx)[n][n], double (&R)[n][r]) {
-  double piv[n];
-#pragma unroll
-  for (int c = 0; c < n; ++c) {
-    piv[c] = rcp_fast(Mx[c][c]);
-#pragma unroll
-    for (int i = c + 1; i < n; ++i) {
-      const double f = Mx[i][c] * piv[c];
-#pragma unroll
-      for (int j = c + 1; j < n; ++j) Mx[i][j] -= f * Mx[c][j];
-#pragma unroll
-      for (int j = 0; j < r; ++j) R[i][j] -= f * R[c][j];
-    }
-  }
-#pragma unroll
-  for (int c = n - 1; c >= 0; --c) {
-#pragma unroll
-    for (int j = 0; j < r; ++j) {
-      double v = R[c][j];
-#pragma unroll
-      for (int i = c + 1; i < n; ++i) v -= Mx[c][i] * R[i][j];
-      R[c][j] = v * piv[c];
-    }
-  }
-}
-
-// o = e1 (earlier span) combined with e2 (the span right after it)
-template <int n>
-__device__ __forceinline__ void scan_combine(const ScanEl<n>& e1, const ScanEl<n>& e2, ScanEl<n>& o) {
-  using E = ScanEl<n>;
-  double Mm[n][n], Mt[n][n];
-#pragma unroll
-  for (int i = 0; i < n; ++i)
-#pragma unroll
-    for (int j = 0; j < n; ++j) {
-      double v = (i == j) ? 1.0 : 0.0;
-#pragma unroll
-      for (int t = 0; t < n; ++t) v += e1.C[E::sy(i, t)] * e2.J[E::sy(t, j)];
-      Mm[i][j] = v;
-      Mt[j][i] = v;
-    }
-  double R[n][2 * n + 1];
-#pragma unroll
-  for (int i = 0; i < n; ++i) {
-#pragma unroll
-    for (int j = 0; j < n; ++j) R[i][j] = e1.A[i * n + j];
-    double v = e1.b[i];
-#pragma unroll
-    for (int t = 0; t < n; ++t) v -= e1.C[E::sy(i, t)] * e2.eta[t];
-    R[i][n] = v;
-#pragma unroll
-    for (int j = 0; j < n; ++j) R[i][n + 1 + j] = e1.C[E::sy(i, j)];
-  }
-  scan_lu_solve<n, 2 * n + 1>(Mm, R);
-  double XC[n][n];
-#pragma unroll
-  for (int i = 0; i < n; ++i) {
-#pragma unroll
-    for (int j = 0; j < n; ++j) {
-      double v = 0.0, w = 0.0;
-#pragma unroll
-      for (int t = 0; t < n; ++t) { v += e2.A[i * n + t] * R[t][j]; w += e2.A[i * n + t] * R[t][n + 1 + j]; }
-      o.A[i * n + j] = v;
-      XC[i][j] = w;
-    }
-    double v = e2.b[i];
-#pragma unroll
-    for (int t = 0; t < n; ++t) v += e2.A[i * n + t] * R[t][n];
-    o.b[i] = v;
-  }
-#pragma unroll
-  for (int j = 0; j < n; ++j)
-#pragma unroll
-    for (int i = 0; i <= j; ++i) {
-      double cij = e2.C[E::sy(i, j)], cji = cij;
-#pragma unroll
-      for (int t = 0; t < n; ++t) { cij += XC[i][t] * e2.A[j * n + t]; cji += XC[j][t] * e2.A[i * n + t]; }
-      o.C[E::sy(i, j)] = 0.5 * (cij + cji);
-    }
-  double Y[n][n + 1];
-#pragma unroll
-  for (int i = 0; i < n; ++i) {
-    double v = e2.eta[i];
-#pragma unroll
-    for (int t = 0; t < n; ++t) v += e2.J[E::sy(i, t)] * e1.b[t];
-    Y[i][0] = v;
-#pragma unroll
-    for (int j = 0; j < n; ++j) {
-      double w = 0.0;
-#pragma unroll
-      for (int t = 0; t < n; ++t) w += e2.J[E::sy(i, t)] * e1.A[t * n + j];
-      Y[i][1 + j] = w;
-    }
-  }
-  scan_lu_solve<n, n + 1>(Mt, Y);
-#pragma unroll
-  for (int i = 0; i < n; ++i) {
-    double v = e1.eta[i];
-#pragma unroll
-    for (int t = 0; t < n; ++t) v += e1.A[t * n + i] * Y[t][0];
-    o.eta[i] = v;
-  }
-#pragma unroll
-  for (int j = 0; j < n; ++j)
-#pragma unroll
-    for (int i = 0; i <= j; ++i) {
-      double a = e1.J[E::sy(i, j)], c = a;
-#pragma unroll
-      for (int t = 0; t < n; ++t) { a += e1.A[t * n + i] * Y[t][1 + j]; c += e1.A[t * n + j] * Y[t][1 + i]; }
-      o.J[E::sy(i, j)] = 0.5 * (a + c);
-    }
-}
-
 __device__ __forceinline__ double scan_shfl(double v, int src_lane) {  // value of lane src_lane (0..63)
   return __shfl(v, src_lane);
+}
+
+// One round of the suffix scan: out = el combined with the element of lane l + d (the neutral element past lane 63).
+// VALUE_ONLY: only (J, eta) of the partner are fetched and only out.eta, out.J are formed (scan_combine.h).
+// SELECT = false: lane 63 is known to hold the neutral element, so the clamped read needs no select behind it.
+template <int n, bool VALUE_ONLY, bool SELECT>
+__device__ __forceinline__ void scan_round(const ScanEl<n>& el, int l, int d, ScanEl<n>& out) {
+  using E = ScanEl<n>;
+  E pe;
+  const int src = l + d;
+  const bool has = src < 64;
+  const int sl = has ? src : 63;
+  if constexpr (VALUE_ONLY) {
+#pragma unroll
+    for (int i = 0; i < n; ++i) pe.eta[i] = scan_shfl(el.eta[i], sl);
+#pragma unroll
+    for (int i = 0; i < E::NSY; ++i) pe.J[i] = scan_shfl(el.J[i], sl);
+    if constexpr (SELECT) {
+      if (!has) {
+#pragma unroll
+        for (int i = 0; i < n; ++i) pe.eta[i] = 0.0;
+#pragma unroll
+        for (int i = 0; i < E::NSY; ++i) pe.J[i] = 0.0;
+      }
+    }
+  } else {
+    const double* pv = (const double*)&el;
+    double* po = (double*)&pe;
+#pragma unroll
+    for (int i = 0; i < E::NV; ++i) po[i] = scan_shfl(pv[i], sl);
+    if constexpr (SELECT) {
+      if (!has) pe.identity();
+    }
+  }
+  scan_combine<n, VALUE_ONLY>(el, pe, out);
 }
 
 // element of one knot from its expansion (diagonal cost block: Hd = its nc diagonal entries)
@@ -362,7 +265,16 @@ __device__ __forceinline__ bool scan_riccati_step(const double* Me, const double
 
 // grid = B workgroups of one wave: trajectory b = blockIdx.x.  LDS: the two knots' expansions of every lane, parked while the
 // scan runs (registers hold two elements and the solver's workspace then).
-template <class M, int FIXED_INTEG, int VAR>
+// TRIM = false: the untrimmed round loop (TRAJOPT_SCAN_TRIM=0, a testing switch: results do not depend on it).
+// TO_SCAN_PRIO: the wave's static issue priority, set once at the top.  With several solves in flight a scan wave (1024 of them at
+// C2: one on every SIMD) lands next to another solve's forward-pass roller; it is the younger and by far the shorter job of the two,
+// and at equal priority the older wave issues first.  Priority 1 lets the short job through: the scan's pipelined duration falls back
+// to what it is alone, the roller pays the same slots either way (profiles/scan_concurrent_solves.md: 1, 2 and 3 measure alike, 0 is
+// slower; -DTO_SCAN_PRIO=p rebuilds an arm).  No arithmetic depends on it.
+#ifndef TO_SCAN_PRIO
+#define TO_SCAN_PRIO 1
+#endif
+template <class M, int FIXED_INTEG, int VAR, bool TRIM = true>
 __global__ void __launch_bounds__(64, 1) k_expand_backward_scan(KArgs a) {
   static_assert(!M::lie && M::ne <= 4 && M::m <= 2, "scan backward pass: small vector-space models");
   constexpr int n = M::n, m = M::m, ne = M::ne, nc = ne + m, RSK = Gains<M>::RSK;
@@ -370,6 +282,9 @@ __global__ void __launch_bounds__(64, 1) k_expand_backward_scan(KArgs a) {
   using E = ScanEl<ne>;
   using LL = LaneLay<M>;
   __shared__ double park[2 * PK * 64];
+#if TO_SCAN_PRIO
+  if constexpr (TRIM) __builtin_amdgcn_s_setprio(TO_SCAN_PRIO);  // (the untrimmed instance stays the kernel it was: the builtin moves its register allocation)
+#endif
   const DevProblem& P = a.P;
   const int N = P.N;
   const int b = blockIdx.x, l = threadIdx.x;
@@ -432,22 +347,26 @@ __global__ void __launch_bounds__(64, 1) k_expand_backward_scan(KArgs a) {
   if (rho == 0.0 && elements_ok) {
     // ---- 3: suffix scan across the lanes: after round d lane l holds the element of blocks l .. l + 2d - 1
     const int NB = (N + 1) / 2;  // blocks on the horizon
+    // TRIM: the last round (d = the largest power of two below NB) feeds step 4 alone, which reads (J, eta) — the value part of the
+    // combination, from the partner's (J, eta): 14 doubles exchanged instead of 44, one solve instead of two.  Lane 63 lies past every
+    // horizon the kernel takes (N <= 126) and holds the neutral element through every round (combine(identity, identity) is the
+    // identity bit for bit: tests/test_scan_combine_host.py), so a lane whose partner lies past lane 63 reads lane 63 as it is.
+    int d = 1;
   #pragma unroll 1
-    for (int d = 1; d < NB; d <<= 1) {
-      E pe;
-      const int src = l + d;
-      const bool has = src < 64;
-      const int sl = has ? src : 63;
-      {
-        const double* pv = (const double*)&el;
-        double* po = (double*)&pe;
-  #pragma unroll
-        for (int i = 0; i < E::NV; ++i) po[i] = scan_shfl(pv[i], sl);
-      }
-      if (!has) pe.identity();
+    for (; (TRIM ? 2 * d : d) < NB; d <<= 1) {
       E out;
-      scan_combine<ne>(el, pe, out);
+      scan_round<ne, false, !TRIM>(el, l, d, out);
       el = out;
+    }
+    if constexpr (TRIM) {
+      if (d < NB) {
+        E out;
+        scan_round<ne, true, false>(el, l, d, out);
+  #pragma unroll
+        for (int i = 0; i < ne; ++i) el.eta[i] = out.eta[i];
+  #pragma unroll
+        for (int i = 0; i < E::NSY; ++i) el.J[i] = out.J[i];
+      }
     }
     // ---- 4: cost-to-go behind this lane's block, then its own knots sequentially
     double S[ne][ne], s[ne];

@@ -1,5 +1,6 @@
 // ops.h — launchers of the model-templated kernels; instantiated per model by the ops_*.hip translation units.
 #pragma once
+#include <cstdlib>
 #include <type_traits>
 
 #include "handle.h"
@@ -207,7 +208,15 @@ int op_expand_backward_scan(to_handle* h) {
   if constexpr (!M::lie && M::ne <= 4 && M::m <= 2) {
     const DevProblem& P = h->a.P;
     if (P.expand_variant != 0 || !h->a.h_diag || P.N > 126) return fail(TO_ERR_UNSUPPORTED, "scan backward pass: outside its scope");
-    return with_integrator<M>(h, [&](auto fi) { return launch(k_expand_backward_scan<M, decltype(fi)::value, 0>, dim3(P.B), dim3(64), 0, h->stream, h->a); });
+    // TRAJOPT_SCAN_TRIM=0: the untrimmed round loop (a testing switch read at the launch, so that one process can compare the two
+    // instances; results do not depend on it)
+    const char* env = std::getenv("TRAJOPT_SCAN_TRIM");
+    const bool trim = !(env && std::atoi(env) == 0);
+    return with_integrator<M>(h, [&](auto fi) {
+      constexpr int FI = decltype(fi)::value;
+      if (!trim) return launch(k_expand_backward_scan<M, FI, 0, false>, dim3(P.B), dim3(64), 0, h->stream, h->a);
+      return launch(k_expand_backward_scan<M, FI, 0, true>, dim3(P.B), dim3(64), 0, h->stream, h->a);
+    });
   }
   return fail(TO_ERR_UNSUPPORTED, "scan backward pass not compiled for this model");
 }
