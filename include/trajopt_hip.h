@@ -339,7 +339,9 @@ int to_create(const to_problem_desc* desc, const to_solver_opts* opts, int devic
 int to_destroy(to_handle* h);
 /* Options are validated (TO_ERR_ARGUMENT for out-of-range values, here and in to_create).  The number of line-search
  * candidate slots is fixed at to_create from iterations_linesearch: raising it later works, with less concurrency than
- * a fresh handle would have. */
+ * a fresh handle would have.  The phase API (to_backward, to_forward, to_dual_update) keeps the regularisation and the
+ * penalties that to_create wrote from bp_reg_initial / penalty_initial until a solve (both) or to_reset_duals (the penalties) rewrites them:
+ * setting those two options later changes the next solve, not the state the phase calls continue from. */
 int to_set_options(to_handle* h, const to_solver_opts* opts);
 int to_get_options(const to_handle* h, to_solver_opts* opts);
 int to_sync(to_handle* h);                 /* block until the handle's stream is idle */
