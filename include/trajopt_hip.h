@@ -21,6 +21,8 @@
  *   to_policy_rollout           <- rollout!(prob) src/problem.jl:330-340 and Altro's rollout!(solver, α), from S start states
  *                                  per trajectory instead of the problem's x0
  *   to_policy_rollout_mc        <- the same with process / measurement noise drawn in the kernel and one plant per sample
+ *   to_mpc_advance              <- the step between two MPC re-solves: that rollout from the measured state, then set_initial_state! and
+ *                                  initial_controls! with the shifted plan (src/problem.jl:255-275), without leaving the device
  *   to_set_* / to_get_*         <- initial_controls!/initial_states!/set_initial_state!/states/controls
  *                                  src/problem.jl:198-310
  *
@@ -72,7 +74,10 @@ extern "C" {
  * NormConstraint, one set per trajectory): added with TO_ABI_VERSION and TO_ABI_MINOR unchanged, found by symbol lookup; a library
  * without them shares every limit among the trajectories of a handle.  And for to_set_time_steps_batch / to_get_time_steps_batch /
  * to_clear_time_steps_batch (one set of time steps — one horizon — per trajectory): added with TO_ABI_VERSION and TO_ABI_MINOR unchanged,
- * found by symbol lookup; a library without them steps every trajectory of a handle by to_problem_desc::dt. */
+ * found by symbol lookup; a library without them steps every trajectory of a handle by to_problem_desc::dt.  And for to_mpc_advance with
+ * to_mpc_opts / to_mpc_result (the receding-horizon step on the device): one symbol and two structs added with TO_ABI_VERSION and
+ * TO_ABI_MINOR unchanged and no existing struct changed in size, found by symbol lookup; with a library without it a host composes the step
+ * from to_policy_rollout, to_set_initial_state, to_set_controls and to_rollout. */
 #define TO_ABI_VERSION 7
 #define TO_ABI_MINOR 1
 
@@ -592,6 +597,49 @@ int to_policy_rollout_mc(to_handle* h, int32_t S, const double* x0s /* [n,S,B] *
  * computed on `device` by the generator the rollout uses.  1 <= pairs <= 256, kind 0 or 1. */
 int to_policy_noise_draws(int device, uint64_t seed, uint32_t traj, uint32_t sample, uint32_t k, uint32_t kind, int32_t pairs,
                           double* z /* [2*pairs] */);
+
+/* ---- the receding-horizon step ---------------------------------------------------------------------
+ * One MPC period on the device: apply the solved law for `shift` knots from the measured state, make the state the plant arrives at
+ * the handle's x0, move the plan forward as the next solve's guess and roll it out.  The call IS to_policy_rollout_mc with S = 1 and
+ * x0s = x_meas — the same law, clamp, plant, noise draws (counter (traj_offset + b, sample_offset, k, kind)) and limit test, the same
+ * kernel instances — except that the closed-loop trajectory x_cl, u_cl stays on the device.  For every trajectory b whose rollout
+ * status is 0:
+ *     x0[b]   <- x_cl[s]                       (0-based knots: the state after s steps of the plant)
+ *     U[b][k] <- V[k + s]   for 0 <= k <= N-2-s,   V = u_cl (TO_MPC_GUESS_CLOSED_LOOP) or the old nominal controls (TO_MPC_GUESS_NOMINAL)
+ *     U[b][k] <- V[N-2] (TO_MPC_TAIL_HOLD) or u_fill (TO_MPC_TAIL_FILL)   for k > N-2-s
+ * A trajectory whose rollout left the limits (status TO_STATE_LIMIT / TO_CONTROL_LIMIT) keeps its x0 and U bit for bit; status and
+ * k_limit say why.  Then the handle's ordinary rollout runs: the handle is in the state that to_set_initial_state + to_set_controls +
+ * to_rollout with those values would have left.  Not touched: duals and penalties (an AL solve resets them at its start), the
+ * per-trajectory arrays (cost terms, constraint parameters and limits, model parameters, time steps) and the gains beyond what
+ * refresh_gains does.  With per-trajectory time steps the steps stay on their knots: the plan moves, the grid does not.
+ * Everything the caller gets back is B (s (n + m) + 2 n) doubles and the five per-trajectory summaries; x_meas == NULL starts from the
+ * handle's own x0 without a host copy.
+ * Errors: mpc == NULL, TO_MPC_TAIL_FILL without u_fill -> TO_ERR_NULL; shift outside 1 .. N-2, an unknown guess or tail, reserved != 0,
+ * a non-finite u_fill, a solve in flight -> TO_ERR_ARGUMENT; TO_MODEL_HYBRID_DOUBLE_INTEGRATOR, TO_MODEL_VECTOR, TO_MODEL_INFEASIBLE ->
+ * TO_ERR_UNSUPPORTED with the model's name (a shift changes which model governs a knot, and slack controls mean nothing once
+ * shifted); everything to_policy_rollout_mc refuses, with its error.  Not announced by TO_ABI_MINOR: look the symbol up (ABI history above). */
+#define TO_MPC_GUESS_CLOSED_LOOP 0
+#define TO_MPC_GUESS_NOMINAL 1
+#define TO_MPC_TAIL_HOLD 0
+#define TO_MPC_TAIL_FILL 1
+typedef struct {
+  int32_t shift;        /* s: knots the plan moves forward, 1 <= s <= N-2 */
+  int32_t guess;        /* 0 = TO_MPC_GUESS_CLOSED_LOOP: the applied controls u_cl of the rollout become the next guess
+                           1 = TO_MPC_GUESS_NOMINAL:     the handle's own nominal controls, shifted */
+  int32_t tail;         /* 0 = TO_MPC_TAIL_HOLD: the s new knots repeat the last control of the chosen sequence
+                           1 = TO_MPC_TAIL_FILL: they take u_fill */
+  int32_t reserved;     /* must be 0 */
+  const double* u_fill; /* [m], required for TAIL_FILL (TO_ERR_NULL), ignored otherwise */
+} to_mpc_opts;
+typedef struct {        /* HOST arrays, any may be NULL */
+  double* x_next;       /* [n,B]      realised state after s steps of the plant = the handle's new x0 */
+  double* X_applied;    /* [n,s+1,B]  closed-loop states of knots 1..s+1 */
+  double* U_applied;    /* [m,s,B]    controls applied on knots 1..s */
+  double* J; double* c_max; double* dx_max; int32_t* status; int32_t* k_limit;   /* [B], to_policy_result semantics at S = 1 */
+} to_mpc_result;
+int to_mpc_advance(to_handle* h, const double* x_meas /* [n,B] or NULL = the handle's x0 */, const to_mpc_opts* mpc,
+                   const to_policy_opts* popts /* NULL = to_policy_rollout's default */, const to_policy_noise* noise /* NULL = none */,
+                   const to_mpc_result* out /* may be NULL */);
 
 /* raw (non error-state) per-knot cost derivatives of the objective at the current trajectory
  * (RD.gradient! / RD.hessian!): grad[(n+m),N,B], hess[(n+m),(n+m),N,B] */

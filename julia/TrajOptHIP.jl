@@ -163,6 +163,29 @@ struct PolicyNoise                   # == to_policy_noise (ABI 7.1)
     plant_params::Ptr{Float64}
 end
 
+struct MpcOpts                       # == to_mpc_opts (found by symbol lookup, like to_mpc_advance)
+    shift::Int32
+    guess::Int32
+    tail::Int32
+    reserved::Int32
+    u_fill::Ptr{Float64}
+end
+
+struct MpcResult                     # == to_mpc_result (host arrays, any may be NULL)
+    x_next::Ptr{Float64}
+    X_applied::Ptr{Float64}
+    U_applied::Ptr{Float64}
+    J::Ptr{Float64}
+    c_max::Ptr{Float64}
+    dx_max::Ptr{Float64}
+    status::Ptr{Int32}
+    k_limit::Ptr{Int32}
+end
+const TO_MPC_GUESS_CLOSED_LOOP = Int32(0)
+const TO_MPC_GUESS_NOMINAL = Int32(1)
+const TO_MPC_TAIL_HOLD = Int32(0)
+const TO_MPC_TAIL_FILL = Int32(1)
+
 @enum SolverStatus::Int32 UNSOLVED = 0 LINESEARCH_FAIL SOLVE_SUCCEEDED MAX_ITERATIONS MAX_ITERATIONS_OUTER MAXIMUM_COST STATE_LIMIT CONTROL_LIMIT NO_PROGRESS COST_INCREASE REGULARIZATION_MAX PROJECTION_FAIL
 
 # ------------------------------------------------------------------------------------------------ errors
@@ -698,6 +721,53 @@ function policy_rollout_mc(p::BatchProblem, X0s::Array{Float64,3}; seed::Integer
     (J = J, c_max = c_max, dx_max = dx_max, status = status, k_limit = k_limit, X = X, U = U)
 end
 """
+    mpc_advance!(p::BatchProblem; x_meas = nothing, shift = 1, guess = :closed_loop, tail = :hold, u_fill = nothing, alpha = 0.0,
+                 refresh_gains = true, u_min = nothing, u_max = nothing, plant = nothing, seed = nothing, sigma_w = nothing, sigma_v = nothing,
+                 traj_offset = 0, sample_offset = 0)
+The step between two MPC re-solves, on the device (`to_mpc_advance`): `policy_rollout` with one sample per trajectory from `x_meas :: (n, B)`
+(`nothing`: the handle's own x0), after which — for every trajectory whose rollout stayed within the limits — the state reached after `shift`
+steps of the plant is the handle's x0 and the plan, moved `shift` knots forward, is its next guess, rolled out.  `guess`: `:closed_loop` (the
+applied controls) or `:nominal` (the handle's own controls, shifted); `tail`: `:hold` or `:fill` (the new knots take `u_fill`).  With `seed` the
+rollout draws `sigma_w` / `sigma_v` noise as `policy_rollout_mc` does.  Duals, penalties, per-trajectory parameters and time steps are not
+shifted.  Returns `(x_next, X, U, J, c_max, dx_max, status, k_limit)` with `x_next :: (n, B)`, `X :: (n, shift+1, B)`, `U :: (m, shift, B)`.
+Added without raising `TO_ABI_MINOR`: a library that lacks it is detected by symbol lookup (`has_mpc_advance()`).
+"""
+has_mpc_advance() = Libdl.dlsym(Libdl.dlopen(lib), :to_mpc_advance; throw_error = false) !== nothing
+function mpc_advance!(p::BatchProblem; x_meas::Union{Nothing,Matrix{Float64}} = nothing, shift::Integer = 1, guess::Symbol = :closed_loop,
+                      tail::Symbol = :hold, u_fill = nothing, alpha::Real = 0.0, refresh_gains::Bool = true, u_min = nothing, u_max = nothing,
+                      plant::Union{Nothing,Vector{Float64}} = nothing, seed::Union{Nothing,Integer} = nothing, sigma_w = nothing,
+                      sigma_v = nothing, traj_offset::Integer = 0, sample_offset::Integer = 0)
+    has_mpc_advance() || error("libtrajopt_hip.so does not export to_mpc_advance")
+    1 <= shift <= p.N - 2 || throw(ArgumentError("shift must be in 1 .. N-2"))
+    guess in (:closed_loop, :nominal) || throw(ArgumentError("guess must be :closed_loop or :nominal"))
+    tail in (:hold, :fill) || throw(ArgumentError("tail must be :hold or :fill"))
+    x_meas === nothing || size(x_meas) == (p.n, p.B) || throw(DimensionMismatch("x_meas must be (n, B)"))
+    ne, s = p.ne, Int(shift)
+    clampvec(v) = v === nothing ? Float64[] : (v isa Real ? fill(Float64(v), p.m) : Vector{Float64}(v))
+    sigmavec(v) = v === nothing ? Float64[] : (v isa Real ? fill(Float64(v), ne) : Vector{Float64}(v))
+    lo, hi, sw, sv, uf = clampvec(u_min), clampvec(u_max), sigmavec(sigma_w), sigmavec(sigma_v), clampvec(u_fill)
+    (isempty(lo) || length(lo) == p.m) && (isempty(hi) || length(hi) == p.m) || throw(DimensionMismatch("u_min / u_max must have length m"))
+    (isempty(sw) || length(sw) == ne) && (isempty(sv) || length(sv) == ne) || throw(DimensionMismatch("sigma_w / sigma_v must have length ne"))
+    tail == :fill && length(uf) != p.m && throw(DimensionMismatch("tail = :fill needs u_fill of length m"))
+    plant === nothing || length(plant) == 16 || throw(DimensionMismatch("plant must hold the 16 model parameters"))
+    x_next, X, U = zeros(p.n, p.B), zeros(p.n, s + 1, p.B), zeros(p.m, s, p.B)
+    J, c_max, dx_max = zeros(p.B), zeros(p.B), zeros(p.B)
+    status, k_limit = zeros(Int32, p.B), zeros(Int32, p.B)
+    pp = plant === nothing ? Float64[] : plant
+    xm = x_meas === nothing ? Float64[] : x_meas
+    ptr(v) = isempty(v) ? Ptr{Float64}(C_NULL) : pointer(v)
+    GC.@preserve lo hi sw sv uf pp xm x_next X U J c_max dx_max status k_limit begin
+        mpc = Ref(MpcOpts(Int32(s), guess == :nominal ? TO_MPC_GUESS_NOMINAL : TO_MPC_GUESS_CLOSED_LOOP,
+            tail == :fill ? TO_MPC_TAIL_FILL : TO_MPC_TAIL_HOLD, Int32(0), tail == :fill ? pointer(uf) : Ptr{Float64}(C_NULL)))
+        opts = Ref(PolicyOpts(Int32(refresh_gains), Int32(0), Float64(alpha), ptr(lo), ptr(hi), ptr(pp)))
+        noise = Ref(PolicyNoise(UInt64(seed === nothing ? 0 : seed), UInt32(traj_offset), UInt32(sample_offset), ptr(sw), ptr(sv), Ptr{Float64}(C_NULL)))
+        out = Ref(MpcResult(pointer(x_next), pointer(X), pointer(U), pointer(J), pointer(c_max), pointer(dx_max), pointer(status), pointer(k_limit)))
+        check(ccall((:to_mpc_advance, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ref{MpcOpts}, Ref{PolicyOpts}, Ref{PolicyNoise}, Ref{MpcResult}),
+            p.handle, ptr(xm), mpc, opts, noise, out))
+    end
+    (x_next = x_next, X = X, U = U, J = J, c_max = c_max, dx_max = dx_max, status = status, k_limit = k_limit)
+end
+"""
     policy_noise_draws(seed, traj, sample, k, kind, pairs; device = 0)
 The `2 pairs` standard normals sample `(traj, sample)` draws at step `k` for noise kind `kind` (0 = w, 1 = v), from the device's generator.
 """
@@ -984,7 +1054,7 @@ function profile(p::BatchProblem)
     (kernel_ms = ms, launches = launches)
 end
 
-export LinearMap, MassDoubleIntegrator, BatchProblem, set_model_params_batch!, model_params_batch, clear_model_params_batch!, has_model_params_batch, set_constraint_limits_batch!, get_constraint_limits_batch, clear_constraint_limits_batch!, has_constraint_limits_batch, set_time_steps_batch!, set_final_times_batch!, time_steps_batch, clear_time_steps_batch!, has_time_steps_batch, policy_rollout, PolicyOpts, PolicyResult, policy_rollout_mc, policy_noise_draws, PolicyNoise, abi_minor, SolverOpts, solver_options, default_options, solve_ilqr!, solve_al!, solve_pn!, solve_altro!, solve_async!, wait_solve!, dynamics_defect, expand!, backwardpass!, forwardpass!,
+export LinearMap, MassDoubleIntegrator, BatchProblem, set_model_params_batch!, model_params_batch, clear_model_params_batch!, has_model_params_batch, set_constraint_limits_batch!, get_constraint_limits_batch, clear_constraint_limits_batch!, has_constraint_limits_batch, set_time_steps_batch!, set_final_times_batch!, time_steps_batch, clear_time_steps_batch!, has_time_steps_batch, policy_rollout, PolicyOpts, PolicyResult, policy_rollout_mc, policy_noise_draws, PolicyNoise, mpc_advance!, has_mpc_advance, MpcOpts, MpcResult, abi_minor, SolverOpts, solver_options, default_options, solve_ilqr!, solve_al!, solve_pn!, solve_altro!, solve_async!, wait_solve!, dynamics_defect, expand!, backwardpass!, forwardpass!,
     stage_costs, al_cost, dynamics_jacobians, cost_expansion, gains, cost_gradient_hessian, discrete_jacobian, duals, set_duals!,
     reset_duals!, dual_update!, comm_unique_id, comm_init_rank!, allgather!, allgather_stats, comm_shards, comm_destroy!, solver_path, knot_dims, device_count, build_id
 

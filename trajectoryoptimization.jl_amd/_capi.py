@@ -163,6 +163,24 @@ class PolicyNoise(C.Structure):
     ]
 
 
+class MpcOpts(C.Structure):
+    _fields_ = [
+        ("shift", C.c_int32), ("guess", C.c_int32), ("tail", C.c_int32), ("reserved", C.c_int32),
+        ("u_fill", C.POINTER(C.c_double)),
+    ]
+
+
+class MpcResult(C.Structure):
+    _fields_ = [
+        ("x_next", C.POINTER(C.c_double)), ("X_applied", C.POINTER(C.c_double)), ("U_applied", C.POINTER(C.c_double)),
+        ("J", C.POINTER(C.c_double)), ("c_max", C.POINTER(C.c_double)), ("dx_max", C.POINTER(C.c_double)),
+        ("status", C.POINTER(C.c_int32)), ("k_limit", C.POINTER(C.c_int32)),
+    ]
+
+
+MPC_GUESS_CLOSED_LOOP, MPC_GUESS_NOMINAL = 0, 1
+MPC_TAIL_HOLD, MPC_TAIL_FILL = 0, 1
+
 _H = C.c_void_p
 _PD = C.POINTER(C.c_double)
 _PI = C.POINTER(C.c_int32)
@@ -261,12 +279,15 @@ HIP_ONLY = {
     "set_time_steps_batch": [_H, _PD],
     "get_time_steps_batch": [_H, _PD],
     "clear_time_steps_batch": [_H],
+    # the receding-horizon step on the device (OPTIONAL_HIP below)
+    "mpc_advance": [_H, _PD, C.POINTER(MpcOpts), C.POINTER(PolicyOpts), C.POINTER(PolicyNoise), C.POINTER(MpcResult)],
 }
 # Entry points added without raising TO_ABI_MINOR (include/trajopt_hip.h, ABI history): detected by symbol lookup.  A library that does
 # not export them still loads; the names are then absent from Library._fn and the wrappers in api.py raise UnsupportedError.
 OPTIONAL_HIP = ("set_model_params_batch", "get_model_params_batch", "clear_model_params_batch",
                 "set_constraint_limits_batch", "get_constraint_limits_batch", "clear_constraint_limits_batch",
-                "set_time_steps_batch", "get_time_steps_batch", "clear_time_steps_batch")
+                "set_time_steps_batch", "get_time_steps_batch", "clear_time_steps_batch",
+                "mpc_advance")
 
 
 class Library:

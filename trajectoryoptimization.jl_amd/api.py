@@ -43,7 +43,7 @@ __all__ = [
     "GoalConstraint", "BoundConstraint", "NormConstraint", "CircleConstraint", "SphereConstraint", "CollisionConstraint", "QuatVecEq",
     "LinearConstraint", "StateBound", "ControlBound", "IndexedConstraint", "change_dimension",
     "ConstraintList", "add_constraint", "num_constraints", "constraint_hessians",
-    "KnotPoint", "Problem", "rollout", "policy_rollout", "PolicyRollout", "PolicyNoise", "policy_noise_draws", "set_model_params", "model_params", "clear_model_params",
+    "KnotPoint", "Problem", "rollout", "policy_rollout", "PolicyRollout", "PolicyNoise", "policy_noise_draws", "mpc_advance", "MpcAdvance", "mpc_run", "MpcRun", "set_model_params", "model_params", "clear_model_params",
     "set_time_steps_batch", "set_final_times_batch", "time_steps", "clear_time_steps_batch", "cost", "states", "controls", "initial_controls", "initial_states",
     "set_initial_state", "set_goal_state", "update_trajectory", "get_constraints", "get_objective", "get_model",
     "get_initial_state", "get_final_state", "get_trajectory", "gettimes",
@@ -1395,6 +1395,26 @@ def policy_rollout(prob, X0s, alpha=0.0, refresh_gains=True, u_min=None, u_max=N
         raise DimensionMismatch(f"X0s must be [B={prob.B}, S >= 1, n={prob.n}]; got {a.shape}")
     a = np.ascontiguousarray(a)
     B, S, N, n, m = prob.B, a.shape[1], prob.N, prob.n, prob.m
+    o, nz, keep = _policy_args(prob, S, alpha, refresh_gains, u_min, u_max, plant, noise, plants)
+    J, cm, dxm = np.empty((B, S)), np.empty((B, S)), np.empty((B, S))
+    st, kl = np.empty((B, S), np.int32), np.empty((B, S), np.int32)
+    X = np.empty((B, S, N, n)) if trajectories else None
+    U = np.empty((B, S, N - 1, m)) if trajectories else None
+    r = capi.PolicyResult()
+    r.J, r.c_max, r.dx_max, r.status, r.k_limit = prob._pd(J), prob._pd(cm), prob._pd(dxm), prob._pi(st), prob._pi(kl)
+    if trajectories:
+        r.X, r.U = prob._pd(X), prob._pd(U)
+    if not mc:
+        prob._call("policy_rollout", S, prob._pd(a), C.byref(o), C.byref(r))
+    else:
+        prob._call("policy_rollout_mc", S, prob._pd(a), C.byref(o), C.byref(nz), C.byref(r))
+    return PolicyRollout(J, cm, dxm, st, kl, X, U)
+
+
+def _policy_args(prob, S, alpha, refresh_gains, u_min, u_max, plant, noise, plants):
+    """to_policy_opts and to_policy_noise of a closed-loop rollout of S samples per trajectory, checked (``policy_rollout``, ``mpc_advance``);
+    the third value keeps the arrays they point into alive."""
+    B, m = prob.B, prob.m
     o = capi.PolicyOpts()
     o.refresh_gains, o.alpha = (1 if refresh_gains else 0), float(alpha)
     keep = []
@@ -1453,19 +1473,121 @@ def policy_rollout(prob, X0s, alpha=0.0, refresh_gains=True, u_min=None, u_max=N
                     pp[b, s, : len(q)] = q
         keep.append(np.ascontiguousarray(pp))
         nz.plant_params = prob._pd(keep[-1])
-    J, cm, dxm = np.empty((B, S)), np.empty((B, S)), np.empty((B, S))
-    st, kl = np.empty((B, S), np.int32), np.empty((B, S), np.int32)
-    X = np.empty((B, S, N, n)) if trajectories else None
-    U = np.empty((B, S, N - 1, m)) if trajectories else None
-    r = capi.PolicyResult()
+    return o, nz, keep
+
+
+def _need_mpc_advance(prob):
+    if "mpc_advance" not in prob._lib._fn:
+        if "policy_rollout" not in prob._lib._fn:
+            raise NotImplementedError("mpc_advance needs the HIP library (the CPU oracle has no closed-loop rollout)")
+        raise UnsupportedError("mpc_advance needs a HIP library that exports to_mpc_advance")
+
+
+class MpcAdvance:
+    """Result of ``mpc_advance``: ``x_next`` [B, n] the state the plant arrived at after ``shift`` steps (the problem's new x0 where
+    ``status`` is 0), ``X`` [B, shift+1, n] the closed-loop states from the measured one on, ``U`` [B, shift, m] the controls applied, and
+    ``J``, ``c_max``, ``dx_max``, ``status``, ``k_limit`` [B] of the whole closed-loop rollout (``PolicyRollout`` semantics at S = 1)."""
+
+    def __init__(self, x_next, X, U, J, c_max, dx_max, status, k_limit):
+        self.x_next, self.X, self.U, self.J, self.c_max, self.dx_max, self.status, self.k_limit = x_next, X, U, J, c_max, dx_max, status, k_limit
+
+
+_MPC_GUESS = {"closed_loop": capi.MPC_GUESS_CLOSED_LOOP, "nominal": capi.MPC_GUESS_NOMINAL}
+_MPC_TAIL = {"hold": capi.MPC_TAIL_HOLD, "fill": capi.MPC_TAIL_FILL}
+
+
+def mpc_advance(prob, x_meas=None, shift=1, guess="closed_loop", tail="hold", u_fill=None, alpha=0.0, refresh_gains=True, u_min=None, u_max=None,
+                plant=None, noise=None):
+    """The step between two MPC re-solves, on the device (to_mpc_advance): ``policy_rollout`` with one sample per trajectory from
+    ``x_meas`` ([B, n] or [n]; None: the problem's own x0, no upload), after which — for every trajectory whose rollout stayed within the
+    limits — the state reached after ``shift`` steps of the plant is the problem's x0, the plan is moved ``shift`` knots forward as the
+    next guess and rolled out.  ``guess``: "closed_loop" (the applied controls) or "nominal" (the problem's own controls, shifted);
+    ``tail``: "hold" (the new knots repeat the last control) or "fill" (they take ``u_fill``, [m] or a scalar).  ``alpha``,
+    ``refresh_gains``, ``u_min`` / ``u_max``, ``plant`` and ``noise`` are ``policy_rollout``'s.  Equal, bit for bit, to
+    ``policy_rollout(..., trajectories=True)``, a shift in numpy, ``set_initial_state``, ``initial_controls`` and ``rollout``; only
+    B (shift (n + m) + 2 n) doubles come back.  A trajectory with a nonzero ``status`` keeps its x0 and controls.  Duals, penalties,
+    per-trajectory parameters and time steps are not shifted.  Returns an ``MpcAdvance``."""
+    _need_mpc_advance(prob)
+    B, N, n, m = prob.B, prob.N, prob.n, prob.m
+    if isinstance(shift, bool) or not isinstance(shift, (int, np.integer)) or not 1 <= shift <= N - 2:
+        raise ArgumentError(f"shift must be an integer in 1 .. N-2 = {N - 2}; got {shift!r}")
+    if guess not in _MPC_GUESS:
+        raise ArgumentError(f"guess must be one of {sorted(_MPC_GUESS)}; got {guess!r}")
+    if tail not in _MPC_TAIL:
+        raise ArgumentError(f"tail must be one of {sorted(_MPC_TAIL)}; got {tail!r}")
+    s = int(shift)
+    mo = capi.MpcOpts()
+    mo.shift, mo.guess, mo.tail = s, _MPC_GUESS[guess], _MPC_TAIL[tail]
+    fill = None
+    if tail == "fill":
+        if u_fill is None:
+            raise ArgumentError('tail="fill" needs u_fill')
+        fill = np.asarray(u_fill, dtype=np.float64)
+        if fill.ndim > 1 or (fill.ndim == 1 and fill.shape[0] != m):
+            raise DimensionMismatch(f"u_fill must be a scalar or [m={m}]; got {fill.shape}")
+        fill = np.ascontiguousarray(np.full(m, float(fill)) if fill.ndim == 0 else fill)
+        if not np.all(np.isfinite(fill)):
+            raise ArgumentError("u_fill must be finite")
+        mo.u_fill = prob._pd(fill)
+    xm = None
+    if x_meas is not None:
+        xm = np.asarray(x_meas, dtype=np.float64)
+        if xm.shape == (n,):
+            xm = np.broadcast_to(xm, (B, n))
+        elif xm.shape != (B, n):
+            raise DimensionMismatch(f"x_meas must be [B={B}, n={n}] or [n]; got {xm.shape}")
+        xm = np.ascontiguousarray(xm)
+    o, nz, keep = _policy_args(prob, 1, alpha, refresh_gains, u_min, u_max, plant, noise, None)
+    x_next, X, U = np.empty((B, n)), np.empty((B, s + 1, n)), np.empty((B, s, m))
+    J, cm, dxm, st, kl = np.empty(B), np.empty(B), np.empty(B), np.empty(B, np.int32), np.empty(B, np.int32)
+    r = capi.MpcResult()
+    r.x_next, r.X_applied, r.U_applied = prob._pd(x_next), prob._pd(X), prob._pd(U)
     r.J, r.c_max, r.dx_max, r.status, r.k_limit = prob._pd(J), prob._pd(cm), prob._pd(dxm), prob._pi(st), prob._pi(kl)
-    if trajectories:
-        r.X, r.U = prob._pd(X), prob._pd(U)
-    if not mc:
-        prob._call("policy_rollout", S, prob._pd(a), C.byref(o), C.byref(r))
-    else:
-        prob._call("policy_rollout_mc", S, prob._pd(a), C.byref(o), C.byref(nz), C.byref(r))
-    return PolicyRollout(J, cm, dxm, st, kl, X, U)
+    prob._call("mpc_advance", prob._pd(xm) if xm is not None else None, C.byref(mo), C.byref(o), C.byref(nz) if noise is not None else None, C.byref(r))
+    x0 = getattr(prob, "x0", None)
+    if x0 is not None:  # the host's copy of what set_initial_state was last given follows the handle
+        prob.x0 = np.where((st == 0)[:, None], x_next, x0)
+    return MpcAdvance(x_next, X, U, J, cm, dxm, st, kl)
+
+
+class MpcRun:
+    """Record of ``mpc_run``: ``X_cl`` [B, steps shift + 1, n] and ``U_cl`` [B, steps shift, m], the closed loop as the plant lived it;
+    ``iterations`` and ``status`` [steps, B] of the solve of every period; ``advance_status`` and ``k_limit`` [steps, B] of every advance (a
+    trajectory with a nonzero entry did not move in that period and its record of the period is the rollout that left the limits)."""
+
+    def __init__(self, X_cl, U_cl, iterations, status, advance_status, k_limit):
+        self.X_cl, self.U_cl, self.iterations, self.status, self.advance_status, self.k_limit = X_cl, U_cl, iterations, status, advance_status, k_limit
+
+
+def mpc_run(solver, steps, shift=1, x_true=None, plant=None, noise=None, before_solve=None, **advance_kw):
+    """The closed loop: ``steps`` periods of solve -> ``mpc_advance`` -> solve ... on ``solver.prob``; the true state never leaves the device
+    between periods.  ``x_true`` ([B, n] or [n]): where the plant starts (None: the problem's x0).  ``plant`` / ``noise``: the plant that is
+    simulated and its noise; period ``t`` draws with ``sample_offset = noise.sample_offset + t``, so the draws of period t, knot k are
+    (trajectory, t, k) and ``policy_noise_draws`` reproduces them.  ``before_solve(prob, t)`` runs before the solve of period t (the hook for
+    ``update_trajectory`` / ``set_goal_state``).  Other keywords go to ``mpc_advance``.  Returns an ``MpcRun``."""
+    prob = solver.prob
+    _need_mpc_advance(prob)
+    steps, s = int(steps), int(shift)
+    if steps < 1:
+        raise ArgumentError(f"steps must be >= 1; got {steps}")
+    if noise is not None and not isinstance(noise, PolicyNoise):
+        raise ArgumentError(f"noise must be a PolicyNoise; got {type(noise).__name__}")
+    B, n, m = prob.B, prob.n, prob.m
+    X_cl, U_cl = np.empty((B, steps * s + 1, n)), np.empty((B, steps * s, m))
+    its, sts = np.empty((steps, B), np.int32), np.empty((steps, B), np.int32)
+    adv, klim = np.empty((steps, B), np.int32), np.empty((steps, B), np.int32)
+    for t in range(steps):
+        if before_solve is not None:
+            before_solve(prob, t)
+        solver.solve()
+        its[t], sts[t] = solver.stats["iterations"], solver.stats["status"]
+        nz = None if noise is None else PolicyNoise(noise.seed, noise.sigma_w, noise.sigma_v, noise.traj_offset, noise.sample_offset + t)
+        r = mpc_advance(prob, x_meas=x_true if t == 0 else None, shift=s, plant=plant, noise=nz, **advance_kw)
+        if t == 0:
+            X_cl[:, 0] = r.X[:, 0]
+        X_cl[:, t * s + 1:(t + 1) * s + 1], U_cl[:, t * s:(t + 1) * s] = r.X[:, 1:], r.U
+        adv[t], klim[t] = r.status, r.k_limit
+    return MpcRun(X_cl, U_cl, its, sts, adv, klim)
 
 
 def _need_model_params_batch(prob):

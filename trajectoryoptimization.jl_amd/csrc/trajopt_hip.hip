@@ -19,6 +19,7 @@
 #include "desc_lower.h"
 #include "handle.h"
 #include "k_generic.h"
+#include "k_mpc.h"
 
 using namespace to;
 
@@ -1582,12 +1583,23 @@ static int check_plant_params(const to_handle* h, const double* pp, const std::s
   if (!ok) return fail(TO_ERR_ARGUMENT, "to_policy_rollout: plant_params" + where + " change the model's dimensions or attitude representation");
   return TO_OK;
 }
-// Both entry points: noise == NULL (or nothing set in it) is to_policy_rollout itself, the NZ = 0 kernel and nothing else.
-static int policy_rollout_impl(to_handle* h, int32_t S, const double* x0s, const to_policy_opts* opts, const to_policy_noise* noise,
-                               const to_policy_result* out) {
-  CHECK_H(h); CHECK_IDLE(h);
-  if (!x0s) return fail(TO_ERR_NULL, "to_policy_rollout: x0s is NULL");
-  if (!out) return fail(TO_ERR_NULL, "to_policy_rollout: out is NULL");
+// One closed-loop rollout as its entry points (to_policy_rollout, to_policy_rollout_mc, to_mpc_advance) share it: the validated options as
+// the kernel's argument block, the kernel instance, the lane map and the per-sample arrays (policy_prepare), then the staging pair of one
+// chunk of waves (policy_staging).  What differs is where the start states come from and where the closed-loop trajectory goes.
+struct PolicyRun {
+  PolicyArgs pa;
+  int nz = 0;          // the kernel's NZ: bit 0 process noise, bit 1 measurement noise, bit 2 one plant per sample
+  bool packed = true;  // lane map
+  int waves = 0;
+  size_t SB = 0;
+  std::vector<double> own_plants;  // the handle's per-trajectory plants repeated per sample (alive until the entry point returns)
+};
+static int policy_launch(to_handle* h, const PolicyRun& r, const PolicyArgs& a, int w) {
+  return r.nz ? h->ops->policy_rollout_mc(h, a, w, r.nz) : h->ops->policy_rollout(h, a, w);
+}
+// noise == NULL (or nothing set in it) is to_policy_rollout itself, the NZ = 0 kernel and nothing else.  force_packed: the packed lane map
+// whatever TRAJOPT_POLICY_MAP says (to_mpc_advance: its S = 1 staging blocks must have the row layout of the nominal tiles, k_mpc.h)
+static int policy_prepare(to_handle* h, int32_t S, const to_policy_opts* opts, const to_policy_noise* noise, bool force_packed, PolicyRun* run) {
   if (S < 1) return fail(TO_ERR_ARGUMENT, "to_policy_rollout: S must be >= 1");
   if (!h->ops->policy_rollout) return fail(TO_ERR_UNSUPPORTED, "policy rollout not compiled for this model");
   to_policy_opts o = {1, 0, 0.0, nullptr, nullptr, nullptr};
@@ -1596,10 +1608,11 @@ static int policy_rollout_impl(to_handle* h, int32_t S, const double* x0s, const
   if (!std::isfinite(o.alpha)) return fail(TO_ERR_ARGUMENT, "to_policy_rollout: alpha must be finite");
   if (o.plant_params) TRY(check_plant_params(h, o.plant_params));
   const DevProblem& P = h->a.P;
-  const int n = P.n, m = P.m, N = P.N, B = P.B;
-  PolicyArgs pa;
+  const int n = P.n, m = P.m, B = P.B;
+  PolicyArgs& pa = run->pa;
   std::memset(&pa, 0, sizeof(pa));
-  int nz = 0;  // the kernel's NZ: bit 0 process noise, bit 1 measurement noise, bit 2 one plant per sample
+  int& nz = run->nz;
+  nz = 0;
   if (noise) {
     const int ne = P.ne;
     if ((noise->sigma_w || noise->sigma_v) && (h->model_key == 7 || h->model_key == 8))
@@ -1627,7 +1640,7 @@ static int policy_rollout_impl(to_handle* h, int32_t S, const double* x0s, const
   // A handle planned on one plant per trajectory (to_set_model_params_batch) simulates each trajectory on ITS plant when the caller names none:
   // the host fills the per-sample plants array and the one-plant-per-sample instance runs (an explicit plant, shared or per sample, overrides)
   const double* plants_src = (noise && noise->plant_params) ? noise->plant_params : nullptr;
-  std::vector<double> own_plants;
+  std::vector<double>& own_plants = run->own_plants;
   // (a handle with per-trajectory time steps, DevProblem::dtb, always takes a one-plant-per-sample instance — only those read the steps per
   // trajectory — so there an explicit shared plant is repeated for every sample)
   if (P.pm && !plants_src && (!o.plant_params || P.dtb)) {
@@ -1640,19 +1653,20 @@ static int policy_rollout_impl(to_handle* h, int32_t S, const double* x0s, const
   }
   if (nz && (!h->ops->policy_rollout_mc || (nz & ~h->ops->policy_noise_mask)))
     return fail(TO_ERR_UNSUPPORTED, "to_policy_rollout_mc: not compiled for this model");
-  auto launch = [&](const PolicyArgs& a, int w) { return nz ? h->ops->policy_rollout_mc(h, a, w, nz) : h->ops->policy_rollout(h, a, w); };
   // lane map: packed while a wave holds at least two trajectories, one trajectory per wave beyond (TRAJOPT_POLICY_MAP=packed forces the
   // per-lane body up to S = 64: the A/B of tools/policy_rollout_probe.py)
   bool packed = S <= 32;
-  if (const char* env = std::getenv("TRAJOPT_POLICY_MAP")) {
-    if (!std::strcmp(env, "packed") && S <= 64) packed = true;
-    if (!std::strcmp(env, "uniform")) packed = false;
-  }
+  if (!force_packed)
+    if (const char* env = std::getenv("TRAJOPT_POLICY_MAP")) {
+      if (!std::strcmp(env, "packed") && S <= 64) packed = true;
+      if (!std::strcmp(env, "uniform")) packed = false;
+    }
+  run->packed = packed;
   pa.S = S; pa.TPW = packed ? 64 / S : 0; pa.WPT = (S + 63) / 64;
   const long long waves_ll = packed ? ((long long)B + pa.TPW - 1) / pa.TPW : (long long)B * pa.WPT;
   if (waves_ll > 0x7fffffffLL / 64) return fail(TO_ERR_ARGUMENT, "to_policy_rollout: S * B is too large for one call");
-  const int waves = (int)waves_ll;
-  const size_t SB = (size_t)S * B;
+  run->waves = (int)waves_ll;
+  const size_t SB = run->SB = (size_t)S * B;
   pa.alpha = o.alpha;
   pa.clamp = (o.u_min || o.u_max) ? 1 : 0;
   for (int j = 0; j < TO_MAX_M; ++j) {
@@ -1674,7 +1688,6 @@ static int policy_rollout_impl(to_handle* h, int32_t S, const double* x0s, const
     h->pol_cap = SB;
   }
   pa.x0s = h->pol_x0s; pa.J = h->pol_J; pa.cmax = h->pol_cmax; pa.dxmax = h->pol_dxmax; pa.status = h->pol_status; pa.klim = h->pol_klim;
-  HIPCHECK(hipMemcpyAsync(h->pol_x0s, x0s, SB * n * sizeof(double), hipMemcpyHostToDevice, h->stream));
   if (nz & 4) {
     if (h->pol_plants_cap < SB) {
       HIPCHECK(hipStreamSynchronize(h->stream));
@@ -1686,34 +1699,66 @@ static int policy_rollout_impl(to_handle* h, int32_t S, const double* x0s, const
     pa.plants = h->pol_plants;
     HIPCHECK(hipMemcpyAsync(h->pol_plants, plants_src, SB * 16 * sizeof(double), hipMemcpyHostToDevice, h->stream));
   }
+  return TO_OK;
+}
+// The closed-loop trajectories go through a bounded staging pair, a chunk of waves at a time (sample-fastest blocks [wave - g0][e][64]):
+// 32 MiB, whatever S * B * N is.  TRAJOPT_POLICY_CHUNK_WAVES overrides the chunk (tests of the chunked path).  Sets pa.store / Xw / Uw.
+static int policy_staging(to_handle* h, PolicyRun* run, long long* chunk_out) {
+  const DevProblem& P = h->a.P;
+  const size_t Lx = (size_t)P.N * P.n, Lu = (size_t)(P.N - 1) * P.m;
+  long long chunk = std::max<long long>(1, (32ll << 20) / (long long)(64 * (Lx + Lu) * sizeof(double)));
+  if (const char* env = std::getenv("TRAJOPT_POLICY_CHUNK_WAVES")) chunk = std::max(1, std::atoi(env));
+  chunk = std::min<long long>(chunk, run->waves);
+  if (h->pol_waves < chunk) {
+    HIPCHECK(hipStreamSynchronize(h->stream));
+    dev_release(h, &h->pol_xw); dev_release(h, &h->pol_uw);
+    h->pol_waves = 0;
+    TRY(dev_alloc(h, &h->pol_xw, (size_t)chunk * Lx * 64, false)); TRY(dev_alloc(h, &h->pol_uw, (size_t)chunk * Lu * 64, false));
+    h->pol_waves = (int)chunk;
+  }
+  run->pa.store = 1; run->pa.Xw = h->pol_xw; run->pa.Uw = h->pol_uw;
+  *chunk_out = chunk;
+  return TO_OK;
+}
+// per-sample results -> the caller's arrays (any may be NULL); the caller synchronises
+static int policy_download_summaries(to_handle* h, size_t SB, double* J, double* c_max, double* dx_max, int32_t* status, int32_t* k_limit) {
+  if (J) HIPCHECK(hipMemcpyAsync(J, h->pol_J, SB * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (c_max) HIPCHECK(hipMemcpyAsync(c_max, h->pol_cmax, SB * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (dx_max) HIPCHECK(hipMemcpyAsync(dx_max, h->pol_dxmax, SB * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (status) HIPCHECK(hipMemcpyAsync(status, h->pol_status, SB * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  if (k_limit) HIPCHECK(hipMemcpyAsync(k_limit, h->pol_klim, SB * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  return TO_OK;
+}
+static int policy_rollout_impl(to_handle* h, int32_t S, const double* x0s, const to_policy_opts* opts, const to_policy_noise* noise,
+                               const to_policy_result* out) {
+  CHECK_H(h); CHECK_IDLE(h);
+  if (!x0s) return fail(TO_ERR_NULL, "to_policy_rollout: x0s is NULL");
+  if (!out) return fail(TO_ERR_NULL, "to_policy_rollout: out is NULL");
+  PolicyRun run;
+  TRY(policy_prepare(h, S, opts, noise, false, &run));
+  PolicyArgs& pa = run.pa;
+  const DevProblem& P = h->a.P;
+  const int n = P.n, m = P.m, N = P.N, waves = run.waves;
+  const size_t SB = run.SB;
+  HIPCHECK(hipMemcpyAsync(h->pol_x0s, x0s, SB * n * sizeof(double), hipMemcpyHostToDevice, h->stream));
   if (!out->X && !out->U) {
-    TRY(launch(pa, waves));
+    TRY(policy_launch(h, run, pa, waves));
   } else {
-    // trajectories: chunks of waves through a bounded staging pair (sample-fastest blocks, then host layout): only the caller's arrays
-    // grow with S * B * N.  TRAJOPT_POLICY_CHUNK_WAVES overrides the chunk (tests of the chunked path).
+    // trajectories: each chunk of waves is transposed to host layout in the staging buffer and downloaded: only the caller's arrays grow with S * B * N
     const size_t Lx = (size_t)N * n, Lu = (size_t)(N - 1) * m;
-    long long chunk = std::max<long long>(1, (32ll << 20) / (long long)(64 * (Lx + Lu) * sizeof(double)));
-    if (const char* env = std::getenv("TRAJOPT_POLICY_CHUNK_WAVES")) chunk = std::max(1, std::atoi(env));
-    chunk = std::min<long long>(chunk, waves);
-    if (h->pol_waves < chunk) {
-      HIPCHECK(hipStreamSynchronize(h->stream));
-      dev_release(h, &h->pol_xw); dev_release(h, &h->pol_uw);
-      h->pol_waves = 0;
-      TRY(dev_alloc(h, &h->pol_xw, (size_t)chunk * Lx * 64, false)); TRY(dev_alloc(h, &h->pol_uw, (size_t)chunk * Lu * 64, false));
-      h->pol_waves = (int)chunk;
-    }
+    long long chunk = 0;
+    TRY(policy_staging(h, &run, &chunk));
     TRY(ensure_stage(h, (size_t)chunk * 64 * (Lx + Lu) * sizeof(double)));
-    pa.store = 1; pa.Xw = h->pol_xw; pa.Uw = h->pol_uw;
     auto first_sample = [&](long long g) -> long long {  // sample index of lane 0 of wave g (the waves enumerate the samples in order)
       if (g >= waves) return (long long)SB;
-      if (packed) return std::min<long long>((long long)SB, g * pa.TPW * (long long)S);
+      if (run.packed) return std::min<long long>((long long)SB, g * pa.TPW * (long long)S);
       const long long b = g / pa.WPT, w = g - b * pa.WPT;
       return b * S + w * 64;
     };
     for (long long g0 = 0; g0 < waves; g0 += chunk) {
       const int ng = (int)std::min<long long>(chunk, waves - g0);
       pa.g0 = (int)g0;
-      TRY(launch(pa, ng));
+      TRY(policy_launch(h, run, pa, ng));
       const long long c0 = first_sample(g0), cnt = first_sample(g0 + ng) - c0;
       double* hx = h->stage;
       double* hu = h->stage + (size_t)cnt * Lx;
@@ -1726,11 +1771,7 @@ static int policy_rollout_impl(to_handle* h, int32_t S, const double* x0s, const
       HIPCHECK(hipStreamSynchronize(h->stream));  // the staging pair is re-used by the next chunk
     }
   }
-  if (out->J) HIPCHECK(hipMemcpyAsync(out->J, h->pol_J, SB * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (out->c_max) HIPCHECK(hipMemcpyAsync(out->c_max, h->pol_cmax, SB * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (out->dx_max) HIPCHECK(hipMemcpyAsync(out->dx_max, h->pol_dxmax, SB * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (out->status) HIPCHECK(hipMemcpyAsync(out->status, h->pol_status, SB * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-  if (out->k_limit) HIPCHECK(hipMemcpyAsync(out->k_limit, h->pol_klim, SB * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+  TRY(policy_download_summaries(h, SB, out->J, out->c_max, out->dx_max, out->status, out->k_limit));
   HIPCHECK(hipStreamSynchronize(h->stream));
   return check_guards(h, "to_policy_rollout");
 }
@@ -1740,6 +1781,71 @@ int to_policy_rollout(to_handle* h, int32_t S, const double* x0s, const to_polic
 int to_policy_rollout_mc(to_handle* h, int32_t S, const double* x0s, const to_policy_opts* opts, const to_policy_noise* noise,
                          const to_policy_result* out) {
   return policy_rollout_impl(h, S, x0s, opts, noise, out);
+}
+
+// ---- the receding-horizon step (k_mpc.h) ---------------------------------------------------------------------------------
+// to_policy_rollout_mc at S = 1 from x_meas, whose closed-loop trajectory stays on the device: per chunk of tiles the policy kernel, then
+// k_mpc_writeback (x0 <- x_cl[s]; the closed-loop guess; the host-layout gather of what was applied) and, for the nominal guess, the
+// in-place shift — all on the handle's stream, no synchronisation between chunks (the staging pair is re-used in stream order).  Then the
+// handle's ordinary rollout of the new (x0, U).  Duals, penalties, per-trajectory arrays and gains are not touched.
+int to_mpc_advance(to_handle* h, const double* x_meas, const to_mpc_opts* mpc, const to_policy_opts* popts, const to_policy_noise* noise,
+                   const to_mpc_result* out) {
+  static_assert(MPC_MAX_M == TO_MAX_M, "MpcArgs::u_fill holds one control");
+  CHECK_H(h); CHECK_IDLE(h);
+  if (!mpc) return fail(TO_ERR_NULL, "to_mpc_advance: mpc is NULL");
+  const DevProblem& P = h->a.P;
+  const int n = P.n, m = P.m, N = P.N, B = P.B;
+  if (h->model_key >= 7)  // a shift changes which model governs a knot (hybrid, model vector); slack controls have no meaning once shifted
+    return fail(TO_ERR_UNSUPPORTED, std::string("to_mpc_advance: not available for the ") + model_key_name(h->model_key) +
+                                        " (TO_MODEL_HYBRID_DOUBLE_INTEGRATOR, TO_MODEL_VECTOR and TO_MODEL_INFEASIBLE cannot shift their plan)");
+  if (mpc->shift < 1 || mpc->shift > N - 2)
+    return fail(TO_ERR_ARGUMENT, "to_mpc_advance: shift must be in 1 .. N-2 = " + std::to_string(N - 2) + "; got " + std::to_string(mpc->shift));
+  if (mpc->guess != TO_MPC_GUESS_CLOSED_LOOP && mpc->guess != TO_MPC_GUESS_NOMINAL)
+    return fail(TO_ERR_ARGUMENT, "to_mpc_advance: guess must be TO_MPC_GUESS_CLOSED_LOOP (0) or TO_MPC_GUESS_NOMINAL (1)");
+  if (mpc->tail != TO_MPC_TAIL_HOLD && mpc->tail != TO_MPC_TAIL_FILL)
+    return fail(TO_ERR_ARGUMENT, "to_mpc_advance: tail must be TO_MPC_TAIL_HOLD (0) or TO_MPC_TAIL_FILL (1)");
+  if (mpc->reserved != 0) return fail(TO_ERR_ARGUMENT, "to_mpc_advance: reserved must be 0");
+  MpcArgs ma;
+  std::memset(&ma, 0, sizeof(ma));
+  if (mpc->tail == TO_MPC_TAIL_FILL) {
+    if (!mpc->u_fill) return fail(TO_ERR_NULL, "to_mpc_advance: TO_MPC_TAIL_FILL needs u_fill");
+    for (int j = 0; j < m; ++j) {
+      if (!std::isfinite(mpc->u_fill[j])) return fail(TO_ERR_ARGUMENT, "to_mpc_advance: u_fill must be finite");
+      ma.u_fill[j] = mpc->u_fill[j];
+    }
+  }
+  PolicyRun run;
+  TRY(policy_prepare(h, 1, popts, noise, true, &run));  // (S = 1, packed: wave g = tile g, lane = b & 63)
+  PolicyArgs& pa = run.pa;
+  const int s = mpc->shift, waves = run.waves;
+  long long chunk = 0;
+  TRY(policy_staging(h, &run, &chunk));
+  // host-layout gather of the call: [x_next n B][X_applied n (s+1) B][U_applied m s B], the parts the caller asked for
+  const size_t cx = (size_t)n * B, cX = (size_t)n * (s + 1) * B, cU = (size_t)m * s * B;
+  TRY(ensure_stage(h, (cx + cX + cU) * sizeof(double)));
+  ma.n = n; ma.m = m; ma.N = N; ma.B = B; ma.s = s; ma.guess = mpc->guess; ma.tail = mpc->tail;
+  ma.Xw = h->pol_xw; ma.Uw = h->pol_uw; ma.status = h->pol_status; ma.x0 = h->a.x0; ma.Us = h->a.Us;
+  ma.x_next = (out && out->x_next) ? h->stage : nullptr;
+  ma.X_applied = (out && out->X_applied) ? h->stage + cx : nullptr;
+  ma.U_applied = (out && out->U_applied) ? h->stage + cx + cX : nullptr;
+  if (x_meas) HIPCHECK(hipMemcpyAsync(h->pol_x0s, x_meas, cx * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  else enqueue(k_mpc_x0_in, dim3((unsigned)waves), dim3(BLOCK), 0, h->stream, (const double*)h->a.x0, h->pol_x0s, n, B);
+  const int rows = std::max((N - 1) * m, (s + 1) * n);
+  for (long long g0 = 0; g0 < waves; g0 += chunk) {
+    const int ng = (int)std::min<long long>(chunk, waves - g0);
+    pa.g0 = ma.g0 = (int)g0;
+    TRY(policy_launch(h, run, pa, ng));
+    enqueue(k_mpc_writeback, dim3((unsigned)ng, (unsigned)std::min(rows, 32)), dim3(BLOCK), 0, h->stream, ma);
+    if (ma.guess == TO_MPC_GUESS_NOMINAL) enqueue(k_mpc_shift_nominal, dim3((unsigned)ng), dim3(BLOCK), 0, h->stream, ma);
+    TRY(launched());
+  }
+  if (ma.x_next) HIPCHECK(hipMemcpyAsync(out->x_next, ma.x_next, cx * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (ma.X_applied) HIPCHECK(hipMemcpyAsync(out->X_applied, ma.X_applied, cX * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (ma.U_applied) HIPCHECK(hipMemcpyAsync(out->U_applied, ma.U_applied, cU * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (out) TRY(policy_download_summaries(h, run.SB, out->J, out->c_max, out->dx_max, out->status, out->k_limit));
+  TRY(launch_rollout(h));  // the state to_set_initial_state + to_set_controls + to_rollout would have left
+  HIPCHECK(hipStreamSynchronize(h->stream));
+  return check_guards(h, "to_mpc_advance");
 }
 // the generator alone (k_policy_noise_draws), so that a parity failure of the stochastic rollout can be localised to it or to the loop
 int to_policy_noise_draws(int device, uint64_t seed, uint32_t traj, uint32_t sample, uint32_t k, uint32_t kind, int32_t pairs, double* z) {
