@@ -78,6 +78,9 @@ struct KArgs {
   int* pcount;    // [1]  ... and their number (k_flags_count / k_flags_write)
   int store_x;    // 1: the forward pass stores every candidate's states (k_accept copies the accepted ones); 0: only their controls —
                   // k_accept_roll (k_forward.h) then re-rolls the accepted candidates.  Set per batch step by the solve loop.
+  int fwd_list;   // 1: list mode (fwd_list.h), armed for a whole solve whose every step is a scan step: the scan kernel of step s writes the
+                  // active trajectories, in index order, to alist[s&1] and k_forward2 takes its trajectories from there; the list's length is
+                  // counter[s-1] (counter[-1]: the trajectories the initial rollout left active, counted by k_rollout).  0 outside such a solve.
 };
 
 // One launch of the closed-loop policy rollout (k_policy.h): S samples per trajectory, sample index c = b*S + s.  Waves are numbered

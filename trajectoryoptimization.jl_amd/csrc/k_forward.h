@@ -13,6 +13,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "fwd_list.h"
 #include "ls_round.h"
 
 #ifndef TO_FWD_WAVES
@@ -424,6 +425,9 @@ __device__ __forceinline__ void forward_finish(const KArgs& a, int tile, int lan
   // Active-list compaction: the lanes of this wave hold OTHER trajectories in the next step, so an accepted step that is not
   // going to be written through by the next expansion is settled now — the whole wave copies the candidate (its own block,
   // lane sl) onto the trajectory's nominal slot, 64 elements per pass, and the slot index is cleared.
+  // (List mode, fwd_list.h, has the same need and meets it elsewhere: the finished trajectory's own wave of the NEXT scan launch, which has
+  // nothing else to do, makes the copy before the next forward pass writes anything — here the copy sat at the end of the launch's
+  // longest wave, 2.3 us per dense step of an unpipelined C2 solve.)
   if (a.compact) {
     unsigned long long todo = __ballot(settle);
     const int Lx = P.N * M::n, Lu = (P.N - 1) * M::m;
@@ -859,7 +863,18 @@ __global__ void __launch_bounds__(128, TO_FWD2_WAVES) k_forward2(KArgs a) {
   const int q = hw / TW, t = hw - q * TW;
   const int b0 = blockIdx.x * TW;
   int b, inrange;
-  if (a.compact) {
+  if (a.fwd_list) {
+    // list mode (fwd_list.h): the list this step's scan kernel wrote, as long as the previous step left trajectories active (counter[-1]:
+    // the initial rollout).  The entry is requested together with the count, not behind it — one round trip, not two, ahead of everything
+    // the wave does; a position past the count holds an entry of an earlier step or nothing at all and is never used: such a lane rides
+    // along on the workgroup's first trajectory (lane 0: position b0 < count).
+    const int pos = b0 + t < P.Bp ? b0 + t : P.Bp - 1;
+    const int entry = a.alist[fwd_list_slot(a.step, P.Bp, pos)];
+    const int cnt = a.counter[a.step - 1];
+    if (b0 >= cnt) return;  // both waves of the workgroup
+    inrange = (b0 + t) < cnt;
+    b = inrange ? entry : __builtin_amdgcn_readfirstlane(entry);
+  } else if (a.compact) {
     const int cnt = a.acount[a.step & 1];
     if (b0 >= cnt) return;  // both waves of the workgroup
     inrange = (b0 + t) < cnt;

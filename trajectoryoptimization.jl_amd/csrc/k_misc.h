@@ -42,6 +42,8 @@ __global__ void __launch_bounds__(64) k_rollout(KArgs a) {  // src/problem.jl:33
     a.status[b] = lim; a.active[b] = 0;
     if (a.al_mode) a.outer[b] = 1;  // (the AL loop counts the outer iteration its first inner solve belongs to)
   }
+  // list mode (fwd_list.h): the length of step 0's list — the trajectories that start the solve active — is decided here
+  if (a.fwd_list && a.control && a.active[b] != 0) atomicAdd(&a.counter[-1], 1);
 }
 
 // ------------------------------------------------------------------------------------------------ cost

@@ -27,6 +27,7 @@
 // and the restart rule of k_backward_lane, no second launch.
 #pragma once
 #include "common.h"
+#include "fwd_list.h"
 #include "k_backward.h"
 #include "k_expand.h"
 #include "scan_combine.h"
@@ -289,8 +290,42 @@ __global__ void __launch_bounds__(64, 1) k_expand_backward_scan(KArgs a) {
   const int N = P.N;
   const int b = blockIdx.x, l = threadIdx.x;
   const int tile = b >> 6, lane = b & 63;
+  // List mode (fwd_list.h): this wave's trajectory goes into this step's list at its rank among the active ones.  The flags of the first
+  // FWD_LIST_CHUNK passes (all there are up to b = 1024) are requested here, next to rho / active, ahead of the wave's first wait: their
+  // round trip is the one the wave spends on active[b] anyway, and nothing below depends on the store.  b is wave-uniform: so are the pass
+  // count and the clamped pass index (a pass past the last re-reads the last and adds nothing); the flags 0 .. b-1 lie inside the batch.
+  // active[b] is requested FIRST and the flags are held as they are until the test on it is behind the wave (the empty asm below): left
+  // alone the compiler compares every flag with zero where it arrives — sixteen counted waits AHEAD of the load of active[b], a whole
+  // round trip more (0.9 us per launch of an unpipelined C2 solve).
+  const int act = a.active[b];
+  const bool listed = a.fwd_list != 0;
+  const int np = listed ? fwd_list_passes(b) : 0;
+  long long lslot = fwd_list_slot(a.step, P.Bp, 0);  // (kernel arguments: fetched here with the others, not where the store needs them)
+  asm volatile("" : "+s"(lslot));
+  int f0[FWD_LIST_CHUNK];
+  if (np > 0) {
+#pragma unroll
+    for (int i = 0; i < FWD_LIST_CHUNK; ++i) f0[i] = a.active[(size_t)(i < np ? i : np - 1) * 64 + l];
+  }
   double rho = a.rho[b], drho = a.drho[b];
-  if (!a.active[b]) return;
+  if (!act) {
+    // List mode: a trajectory that finished in the last step on an accepted candidate still has it in a candidate block, and the coming
+    // forward pass gives that block to other trajectories.  Its wave — idle otherwise — copies it onto the nominal now (what the final
+    // accept would have done) and clears the slot index; nobody reads the nominal of a finished trajectory before the solve ends.
+    if constexpr (M::accept_write_through) {
+      if (listed && a.acc[b] != 0) {
+        const int Lx = N * n, Lu = (N - 1) * m;
+        const double* cx = X_SLOT_PTR(a, b, 1);
+        const double* cu = U_SLOT_PTR(a, b, 1);
+        double* nx = X_SLOT_PTR(a, b, 0);
+        double* nu = U_SLOT_PTR(a, b, 0);
+        for (int e = l; e < Lx; e += 64) EL(nx, e) = EL(cx, e);
+        for (int e = l; e < Lu; e += 64) EL(nu, e) = EL(cu, e);
+        if (l == 0) a.acc[b] = 0;
+      }
+    }
+    return;
+  }
   const int c = M::accept_write_through ? a.acc[b] : 0;
   const double* X = X_SLOT_PTR(a, b, c);
   const double* U = U_SLOT_PTR(a, b, c);
@@ -313,6 +348,23 @@ __global__ void __launch_bounds__(64, 1) k_expand_backward_scan(KArgs a) {
       for (int i = 0; i < n; ++i) x[i] = EL(X, k * n + i);
 #pragma unroll
       for (int i = 0; i < m; ++i) u[i] = terminal ? 0.0 : EL(U, k * m + i);
+      if (kk == 0 && listed) {  // the rank (above), behind the loads of the first knot: it costs their latency nothing
+        int rank = 0;
+        if (np > 0) {
+#pragma unroll
+          for (int i = 0; i < FWD_LIST_CHUNK; ++i) asm volatile("" : "+v"(f0[i]));
+#pragma unroll
+          for (int i = 0; i < FWD_LIST_CHUNK; ++i) rank += fwd_list_rank_add(__ballot(f0[i] != 0), i, b);
+        }
+        for (int p0 = FWD_LIST_CHUNK; p0 < np; p0 += FWD_LIST_CHUNK) {  // b > 1024 only
+          int f[FWD_LIST_CHUNK];
+#pragma unroll
+          for (int i = 0; i < FWD_LIST_CHUNK; ++i) f[i] = a.active[(size_t)(p0 + i < np ? p0 + i : np - 1) * 64 + l];
+#pragma unroll
+          for (int i = 0; i < FWD_LIST_CHUNK; ++i) rank += fwd_list_rank_add(__ballot(f[i] != 0), p0 + i, b);
+        }
+        if (l == 0) a.alist[lslot + rank] = b;
+      }
       if (wt && !beyond) {
 #pragma unroll
         for (int i = 0; i < n; ++i) EL(X0, k * n + i) = x[i];

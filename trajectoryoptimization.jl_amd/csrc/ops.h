@@ -260,7 +260,9 @@ template <class M, int MODE>
 int op_forward2(to_handle* h) {
   const KArgs& a = h->a;
   const int TW = a.TW;
-  return launch(k_forward2<M, MODE>, dim3((a.P.Bp + TW - 1) / TW), dim3(128), sizeof(double) * fwd2_lds_doubles<M>(TW), h->stream, a);
+  // list mode: workgroups for the trajectories still active only (the host's count lags and only ever over-counts; the kernel reads the exact one)
+  const int groups = a.fwd_list ? fwd_list_groups(h->list_active, TW) : (a.P.Bp + TW - 1) / TW;
+  return launch(k_forward2<M, MODE>, dim3(groups), dim3(128), sizeof(double) * fwd2_lds_doubles<M>(TW), h->stream, a);
 }
 template <class M, int LO, int HI>
 void fill_forward2(ModelOps& o) {

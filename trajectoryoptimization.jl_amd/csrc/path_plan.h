@@ -222,6 +222,21 @@ inline StepPlan plan_step(const PathPlan& p, const PathTraits& t, int h_diag, in
   s.two_launch = !s.store_x && p.ls2_cwa && compact_armed && p.fwd2 != 1;
   return s;
 }
+// List mode of a solve (fwd_list.h): the scan kernel of every batch step lists the active trajectories and the two-wave forward pass takes
+// its trajectories from that list — workgroups only for trajectories still active, no k_compact launch.  A finished trajectory's accepted
+// candidate is copied onto the nominal by its own, otherwise idle, wave of the NEXT scan launch, before the forward pass hands the block to
+// other trajectories; a step without the list leaves it in its slot until the final accept, where a later step with the list would overwrite
+// it.  So the mode is decided once per solve: on only when EVERY step plans the scan kernel and the two-wave forward pass whatever active
+// count the host has seen (last_active <= B), on an iLQR solve without the k_compact list.
+//   forward2_compiled: the forward variant of this solve has a two-wave instance (launch_forward falls back to k_forward otherwise);
+//   linear_terms: DevProblem::gl is set (cp / cl / plants rule the scan out through expand_variant); enabled: the TRAJOPT_FWD_LIST switch.
+inline bool solve_forward_list(const PathPlan& p, const PathTraits& t, int h_diag, int expand_variant, int compact_armed, int al_mode, int B, int Bp,
+                               bool plants, bool linear_terms, bool forward2_compiled, bool enabled, int max_bp) {
+  if (!enabled || al_mode || compact_armed || plants || linear_terms || !forward2_compiled || !t.write_through || Bp > max_bp) return false;
+  const StepPlan full = plan_step(p, t, h_diag, expand_variant, compact_armed, B, B, plants);  // the plan is monotone in last_active: the full batch is its worst case
+  if (full.kind != STEP_SCAN || !full.store_x || full.two_launch) return false;
+  return full.two_wave || p.fwd2 == 1;
+}
 // to_solver_path: what a handle's solves run, from the predicates plan_step uses
 inline void path_report(const PathPlan& p, const PathTraits& t, int h_diag, int expand_variant, int B, int32_t info[8], bool plants = false) {
   info[0] = p.bwd_mfma ? 1 : p.bwd_lane ? 2 : 0;

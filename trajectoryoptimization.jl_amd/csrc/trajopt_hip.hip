@@ -17,6 +17,7 @@
 #include <thread>
 
 #include "desc_lower.h"
+#include "fwd_list.h"
 #include "handle.h"
 #include "k_generic.h"
 #include "k_mpc.h"
@@ -501,6 +502,7 @@ int solve(to_handle* h, to_solve_stats* st, int al_mode) {
   rp_finish(h, false);   // (an error path may leave the handle on a working set: back to the home arrays, without the copy)
   h->a.control = 0;  // on every exit path: the phase API must never find the state machine armed
   h->a.compact = 0;  // ... nor take its trajectories from a solve's active list
+  h->a.fwd_list = 0; // (either kind)
   h->a.CW = h->plan.cw_base; h->a.TW = h->plan.tw_base;
   h->a.store_x = 1;      // ... and stores whole candidates
   return rc;
@@ -678,14 +680,22 @@ int solve_impl(to_handle* h, to_solve_stats* st, int al_mode) {
   const int max_steps = (al_mode ? P.opts.iterations_total : P.opts.iterations) + 1;
   if (h->counter_len < max_steps) {
     int* c = nullptr;
-    TRY(g_malloc(h, (void**)&c, sizeof(int) * max_steps, "step counters"));
+    TRY(g_malloc(h, (void**)&c, sizeof(int) * (max_steps + 1), "step counters"));
     h->allocs.push_back(c);
-    a.counter = c;
+    a.counter = c + 1;  // counter[-1]: the trajectories active when step 0 begins (list mode, below)
     if (h->counter_host) HIPCHECK(hipHostFree(h->counter_host));
     HIPCHECK(hipHostMalloc((void**)&h->counter_host, sizeof(int) * max_steps));
     h->counter_len = max_steps;
   }
-  HIPCHECK(hipMemsetAsync(a.counter, 0, sizeof(int) * max_steps, h->stream));
+  HIPCHECK(hipMemsetAsync(a.counter - 1, 0, sizeof(int) * (max_steps + 1), h->stream));
+  {  // list mode (path_plan.h solve_forward_list), for this whole solve or not at all; TRAJOPT_FWD_LIST=0 keeps the forward pass's fixed map
+    const char* env = std::getenv("TRAJOPT_FWD_LIST");
+    const int mode = forward_mode(P.simple_stage, P.n_cons > 0, P.integrator == INTEG_RK4,
+                                  forward_general(P.expand_variant, P.gl != nullptr, P.cp != nullptr, P.cl != nullptr), P.unit_soc, h->traits.forward);
+    a.fwd_list = solve_forward_list(h->plan, h->traits, a.h_diag, P.expand_variant, a.compact, al_mode, P.B, P.Bp, plants(h) != 0, P.gl != nullptr,
+                                    mode >= 0 && h->ops->forward2[mode] != nullptr && h->ops->expand_backward_scan != nullptr,
+                                    !(env && std::atoi(env) == 0), FWD_LIST_MAX_BP) ? 1 : 0;
+  }
   TRY(ensure_solve_events(h));
   const hipEvent_t e0 = h->sev[0], e1 = h->sev[1];
   HIPCHECK(hipEventRecord(e0, h->stream));
@@ -730,6 +740,7 @@ int solve_impl(to_handle* h, to_solve_stats* st, int al_mode) {
       }
       if (h->profile) HIPCHECK(hipEventRecord(h->ev[4 * step + 2], h->stream));
       a.CW = sp.CW; a.TW = sp.TW; a.store_x = sp.store_x;
+      h->list_active = last_active;  // (list mode: the forward pass's grid)
       if (sp.two_launch) {  // launch A — one round for everybody; flags -> list; launch B — the rest of the search for the flagged ones; the accept
         const int cw0 = a.CW, tw0 = a.TW, dump0 = a.dump_wave;
         a.dump_wave = pl.ls2_dump;
