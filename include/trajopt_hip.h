@@ -23,6 +23,8 @@
  *   to_policy_rollout_mc        <- the same with process / measurement noise drawn in the kernel and one plant per sample
  *   to_mpc_advance              <- the step between two MPC re-solves: that rollout from the measured state, then set_initial_state! and
  *                                  initial_controls! with the shifted plan (src/problem.jl:255-275), without leaving the device
+ *   to_set_tracking_reference_batch / to_set_tracking_window
+ *                               <- update_trajectory!(obj, Z, start) src/objective.jl:198-212, one reference and one start per trajectory
  *   to_set_* / to_get_*         <- initial_controls!/initial_states!/set_initial_state!/states/controls
  *                                  src/problem.jl:198-310
  *
@@ -77,7 +79,10 @@ extern "C" {
  * found by symbol lookup; a library without them steps every trajectory of a handle by to_problem_desc::dt.  And for to_mpc_advance with
  * to_mpc_opts / to_mpc_result (the receding-horizon step on the device): one symbol and two structs added with TO_ABI_VERSION and
  * TO_ABI_MINOR unchanged and no existing struct changed in size, found by symbol lookup; with a library without it a host composes the step
- * from to_policy_rollout, to_set_initial_state, to_set_controls and to_rollout. */
+ * from to_policy_rollout, to_set_initial_state, to_set_controls and to_rollout.  And for to_set_tracking_reference_batch /
+ * to_set_tracking_window / to_get_tracking_window / to_clear_tracking_reference_batch / to_get_cost_linear_batch (one tracking reference and
+ * one window of it per trajectory): five symbols added with TO_ABI_VERSION and TO_ABI_MINOR unchanged and no existing struct changed, found
+ * by symbol lookup; with a library without them a host feeds each knot's terms through to_set_cost_linear_batch. */
 #define TO_ABI_VERSION 7
 #define TO_ABI_MINOR 1
 
@@ -400,6 +405,38 @@ int to_set_constraint(to_handle* h, int32_t con_id, const to_constraint_desc* co
  * then takes from the shared q). */
 int to_set_cost_linear_batch(to_handle* h, int32_t cost_id, const double* q /* [n*B] or NULL */, const double* r /* [m*B] or NULL */);
 int to_clear_cost_linear_batch(to_handle* h);
+/* One tracking REFERENCE per TRAJECTORY, windowed on the device: update_trajectory!(obj, Z, start) (src/objective.jl:198-212 —
+ * set_LQR_goal!(obj[k], x_ref[start-1+k], u_ref[start-1+k]) knot by knot) for a fleet whose members follow their own paths, or one path at
+ * their own phase.  Needs a tracking objective: cost_index gives every knot a cost of its own.  The reference — Xref[n, Nref, B], Uref[m,
+ * Nref, B] (column-major, entry fastest, then reference knot, then trajectory; Uref may be NULL) — is stored on the device once; `start`
+ * [B], 1-based, says where each trajectory's window begins (NULL: 1 for all).  The knot with 0-based index k of trajectory b tracks
+ * reference knot j = start_b - 1 + k — under TO_TRACK_END_HOLD min(j, Nref - 1) — and its cost c = costs[cost_index[k]] gets the linear
+ * terms q_b = -Q x_ref[j] and, with Uref, r_b = -R u_ref[j], computed on the device by one kernel launch: diagonal kinds -(Q_i x_i);
+ * QUADRATIC acc = Q[i,0] x_0, acc = acc + Q[i,j] x_j for ascending j, then -acc; every product and sum rounded on its own — bit for bit what
+ * N calls of to_set_cost_linear_batch with those values store, and they write the same storage.  With Uref == NULL the r terms are not
+ * touched (the one-argument set_LQR_goal!).  Q, R, H, c and a DiagonalQuatCost's q_ref stay the descriptor's.
+ * to_set_tracking_window moves every trajectory's window: 4 B bytes go to the device and all N knots are lowered again from the stored
+ * reference and the CURRENT descriptors.  In between, to_set_cost and to_set_cost_linear_batch act on a cost as they always do (it starts
+ * over, or takes the given terms, until the next window call); to_clear_cost_linear_batch returns the costs to their descriptors and keeps
+ * the stored reference; to_clear_tracking_reference_batch frees the reference and clears the terms — a solve after it is bit-identical to
+ * the same solve on a fresh handle.  to_get_tracking_window reports Nref (0 while no reference is set), the end mode and every start.
+ * to_get_cost_linear_batch returns the linear terms cost `cost_id` evaluates for every trajectory, c.q[i] + the stored difference (the
+ * descriptor's values repeated B times while nothing is set), q[n, B] / r[m, B].
+ * Errors.  TO_ERR_NULL: Xref NULL; start NULL in to_set_tracking_window.  TO_ERR_ARGUMENT: Nref < 1; an unknown end_mode; a reference
+ * value that is not finite (the message names the first trajectory and knot); start_b < 1; start_b > Nref under HOLD; start_b - 1 + N >
+ * Nref under REFUSE; a window call while no reference is set; a cost_index that gives two knots one cost ("needs a tracking objective (a
+ * distinct cost per knot)"); a solve in flight.  TO_ERR_UNSUPPORTED: a knot whose cost is ERROR_QUADRATIC; TO_MODEL_HYBRID_DOUBLE_INTEGRATOR,
+ * TO_MODEL_VECTOR, TO_MODEL_INFEASIBLE, with the model's name.  A refused call changes nothing.  Not announced by TO_ABI_MINOR: look the
+ * symbols up (ABI history above). */
+#define TO_TRACK_END_REFUSE 0   /* update_trajectory!'s BoundsError: start_b - 1 + N <= Nref for every b, else TO_ERR_ARGUMENT */
+#define TO_TRACK_END_HOLD   1   /* knots past the end of the reference track its last knot */
+int to_set_tracking_reference_batch(to_handle* h, int32_t Nref, const double* Xref /* [n, Nref, B] */,
+                                    const double* Uref /* [m, Nref, B] or NULL */, const int32_t* start /* [B], 1-based, or NULL = 1 for all */,
+                                    int32_t end_mode);
+int to_set_tracking_window(to_handle* h, const int32_t* start /* [B], 1-based */);
+int to_get_tracking_window(to_handle* h, int32_t* Nref, int32_t* end_mode, int32_t* start /* [B]; any may be NULL */);
+int to_clear_tracking_reference_batch(to_handle* h);
+int to_get_cost_linear_batch(to_handle* h, int32_t cost_id, double* q /* [n*B] or NULL */, double* r /* [m*B] or NULL */);
 /* One constraint-parameter set per TRAJECTORY (round 6): set_goal_state!(prob, xf; constraint = true) updates the GoalConstraints too
  * (src/problem.jl:303-309, src/constraints.jl:22-87) — here for every trajectory of the batch at once.  con_id names a GOAL constraint,
  * params[p, B] (column-major) = xf_b[inds], the target of trajectory b — or a LINEAR constraint (src/constraints.jl:103-150), params[p, B] =

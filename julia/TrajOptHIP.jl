@@ -901,6 +901,57 @@ function clear_time_steps_batch!(p::BatchProblem)
     check(ccall((:to_clear_time_steps_batch, lib), Cint, (Ptr{Cvoid},), p.handle))
     nothing
 end
+"""
+    update_trajectory!(p, Xref, Uref, start = 1; hold = false)   # Xref :: (n, Nref, B), Uref :: (m, Nref, B) or nothing, start :: Int or (B,)
+One tracking reference per trajectory, windowed on the device (`to_set_tracking_reference_batch`): knot `k` of trajectory `b` tracks
+reference knot `start[b] + k - 1` — `update_trajectory!(obj, Z, start)` (src/objective.jl:198-212) for a fleet whose members follow their
+own paths.  Only `q` and `r` of the costs change; with `Uref === nothing` the `r` terms are not touched.  `hold = true`: knots past the end
+track the last reference knot (otherwise such a window is an error).  `set_tracking_window!(p, start)` moves the windows without touching
+the reference, `tracking_window(p)` reports them, `clear_tracking_reference_batch!(p)` frees the reference and returns the costs to their
+descriptors, `cost_linear_batch(p, i)` returns the linear terms cost `i` (1-based) evaluates.  Added without raising `TO_ABI_MINOR`: a
+library that lacks them is detected by symbol lookup (`has_tracking_reference_batch()`).
+"""
+has_tracking_reference_batch() = Libdl.dlsym(Libdl.dlopen(lib), :to_set_tracking_reference_batch; throw_error = false) !== nothing
+const TO_TRACK_END_REFUSE = Int32(0)
+const TO_TRACK_END_HOLD = Int32(1)
+tracking_starts(p::BatchProblem, start::Integer) = fill(Int32(start), p.B)
+function tracking_starts(p::BatchProblem, start::AbstractVector{<:Integer})
+    length(start) == p.B || throw(DimensionMismatch("start must be an integer or (B,)"))
+    Vector{Int32}(start)
+end
+function TO.update_trajectory!(p::BatchProblem, Xref::Array{Float64,3}, Uref::Union{Nothing,Array{Float64,3}}, start = 1; hold::Bool = false)
+    has_tracking_reference_batch() || error("libtrajopt_hip.so does not export to_set_tracking_reference_batch")
+    Nref = size(Xref, 2)
+    size(Xref) == (p.n, Nref, p.B) || throw(DimensionMismatch("Xref must be (n, Nref, B)"))
+    Uref === nothing || size(Uref) == (p.m, Nref, p.B) || throw(DimensionMismatch("Uref must be (m, Nref, B)"))
+    s = tracking_starts(p, start)
+    check(ccall((:to_set_tracking_reference_batch, lib), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Int32),
+                p.handle, Nref, Xref, Uref === nothing ? C_NULL : Uref, s, hold ? TO_TRACK_END_HOLD : TO_TRACK_END_REFUSE))
+    p
+end
+function set_tracking_window!(p::BatchProblem, start)
+    has_tracking_reference_batch() || error("libtrajopt_hip.so does not export to_set_tracking_window")
+    s = tracking_starts(p, start)
+    check(ccall((:to_set_tracking_window, lib), Cint, (Ptr{Cvoid}, Ptr{Int32}), p.handle, s))
+    p
+end
+function tracking_window(p::BatchProblem)
+    has_tracking_reference_batch() || error("libtrajopt_hip.so does not export to_get_tracking_window")
+    Nref, mode, s = Ref{Int32}(0), Ref{Int32}(0), zeros(Int32, p.B)
+    check(ccall((:to_get_tracking_window, lib), Cint, (Ptr{Cvoid}, Ref{Int32}, Ref{Int32}, Ptr{Int32}), p.handle, Nref, mode, s))
+    (Nref = Int(Nref[]), hold = mode[] == TO_TRACK_END_HOLD, start = s)
+end
+function clear_tracking_reference_batch!(p::BatchProblem)
+    has_tracking_reference_batch() || error("libtrajopt_hip.so does not export to_clear_tracking_reference_batch")
+    check(ccall((:to_clear_tracking_reference_batch, lib), Cint, (Ptr{Cvoid},), p.handle))
+    nothing
+end
+function cost_linear_batch(p::BatchProblem, i::Integer)
+    has_tracking_reference_batch() || error("libtrajopt_hip.so does not export to_get_cost_linear_batch")
+    q, r = zeros(p.n, p.B), zeros(p.m, p.B)
+    check(ccall((:to_get_cost_linear_batch, lib), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}), p.handle, i - 1, q, r))
+    (q = q, r = r)
+end
 function clear_goal_state_batch!(p::BatchProblem)
     check(ccall((:to_clear_cost_linear_batch, lib), Cint, (Ptr{Cvoid},), p.handle))
     check(ccall((:to_clear_constraint_params_batch, lib), Cint, (Ptr{Cvoid},), p.handle))
@@ -1054,7 +1105,7 @@ function profile(p::BatchProblem)
     (kernel_ms = ms, launches = launches)
 end
 
-export LinearMap, MassDoubleIntegrator, BatchProblem, set_model_params_batch!, model_params_batch, clear_model_params_batch!, has_model_params_batch, set_constraint_limits_batch!, get_constraint_limits_batch, clear_constraint_limits_batch!, has_constraint_limits_batch, set_time_steps_batch!, set_final_times_batch!, time_steps_batch, clear_time_steps_batch!, has_time_steps_batch, policy_rollout, PolicyOpts, PolicyResult, policy_rollout_mc, policy_noise_draws, PolicyNoise, mpc_advance!, has_mpc_advance, MpcOpts, MpcResult, abi_minor, SolverOpts, solver_options, default_options, solve_ilqr!, solve_al!, solve_pn!, solve_altro!, solve_async!, wait_solve!, dynamics_defect, expand!, backwardpass!, forwardpass!,
+export LinearMap, MassDoubleIntegrator, BatchProblem, set_model_params_batch!, model_params_batch, clear_model_params_batch!, has_model_params_batch, set_constraint_limits_batch!, get_constraint_limits_batch, clear_constraint_limits_batch!, has_constraint_limits_batch, set_time_steps_batch!, set_final_times_batch!, time_steps_batch, clear_time_steps_batch!, has_time_steps_batch, policy_rollout, PolicyOpts, PolicyResult, policy_rollout_mc, policy_noise_draws, PolicyNoise, mpc_advance!, has_mpc_advance, MpcOpts, MpcResult, set_tracking_window!, tracking_window, clear_tracking_reference_batch!, cost_linear_batch, has_tracking_reference_batch, abi_minor, SolverOpts, solver_options, default_options, solve_ilqr!, solve_al!, solve_pn!, solve_altro!, solve_async!, wait_solve!, dynamics_defect, expand!, backwardpass!, forwardpass!,
     stage_costs, al_cost, dynamics_jacobians, cost_expansion, gains, cost_gradient_hessian, discrete_jacobian, duals, set_duals!,
     reset_duals!, dual_update!, comm_unique_id, comm_init_rank!, allgather!, allgather_stats, comm_shards, comm_destroy!, solver_path, knot_dims, device_count, build_id
 

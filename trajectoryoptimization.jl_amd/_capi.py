@@ -180,6 +180,7 @@ class MpcResult(C.Structure):
 
 MPC_GUESS_CLOSED_LOOP, MPC_GUESS_NOMINAL = 0, 1
 MPC_TAIL_HOLD, MPC_TAIL_FILL = 0, 1
+TRACK_END_REFUSE, TRACK_END_HOLD = 0, 1
 
 _H = C.c_void_p
 _PD = C.POINTER(C.c_double)
@@ -281,13 +282,21 @@ HIP_ONLY = {
     "clear_time_steps_batch": [_H],
     # the receding-horizon step on the device (OPTIONAL_HIP below)
     "mpc_advance": [_H, _PD, C.POINTER(MpcOpts), C.POINTER(PolicyOpts), C.POINTER(PolicyNoise), C.POINTER(MpcResult)],
+    # one tracking reference and one window of it per trajectory (OPTIONAL_HIP below)
+    "set_tracking_reference_batch": [_H, C.c_int32, _PD, _PD, _PI, C.c_int32],
+    "set_tracking_window": [_H, _PI],
+    "get_tracking_window": [_H, _PI, _PI, _PI],
+    "clear_tracking_reference_batch": [_H],
+    "get_cost_linear_batch": [_H, C.c_int32, _PD, _PD],
 }
 # Entry points added without raising TO_ABI_MINOR (include/trajopt_hip.h, ABI history): detected by symbol lookup.  A library that does
 # not export them still loads; the names are then absent from Library._fn and the wrappers in api.py raise UnsupportedError.
 OPTIONAL_HIP = ("set_model_params_batch", "get_model_params_batch", "clear_model_params_batch",
                 "set_constraint_limits_batch", "get_constraint_limits_batch", "clear_constraint_limits_batch",
                 "set_time_steps_batch", "get_time_steps_batch", "clear_time_steps_batch",
-                "mpc_advance")
+                "mpc_advance",
+                "set_tracking_reference_batch", "set_tracking_window", "get_tracking_window", "clear_tracking_reference_batch",
+                "get_cost_linear_batch")
 
 
 class Library:

@@ -45,7 +45,8 @@ __all__ = [
     "ConstraintList", "add_constraint", "num_constraints", "constraint_hessians",
     "KnotPoint", "Problem", "rollout", "policy_rollout", "PolicyRollout", "PolicyNoise", "policy_noise_draws", "mpc_advance", "MpcAdvance", "mpc_run", "MpcRun", "set_model_params", "model_params", "clear_model_params",
     "set_time_steps_batch", "set_final_times_batch", "time_steps", "clear_time_steps_batch", "cost", "states", "controls", "initial_controls", "initial_states",
-    "set_initial_state", "set_goal_state", "update_trajectory", "get_constraints", "get_objective", "get_model",
+    "set_initial_state", "set_goal_state", "update_trajectory", "set_tracking_reference_batch", "set_tracking_window", "get_tracking_window",
+    "clear_tracking_reference_batch", "get_cost_linear_batch", "get_constraints", "get_objective", "get_model",
     "get_initial_state", "get_final_state", "get_trajectory", "gettimes",
     "SolverOptions", "iLQRSolver", "ALSolver", "ALTROSolver", "ProjectedNewtonSolver", "dynamics_defect", "solve", "SolvePipeline", "iterations", "status", "max_violation",
     "evaluate_constraints", "constraint_jacobians", "sense", "upper_bound", "lower_bound", "is_bound",
@@ -1559,12 +1560,31 @@ class MpcRun:
         self.X_cl, self.U_cl, self.iterations, self.status, self.advance_status, self.k_limit = X_cl, U_cl, iterations, status, advance_status, k_limit
 
 
-def mpc_run(solver, steps, shift=1, x_true=None, plant=None, noise=None, before_solve=None, **advance_kw):
+def _advance_tracking_window(prob, moved, s, t):
+    """mpc_run's bookkeeping of a stored tracking reference: the windows of the trajectories that moved follow the plan ``s`` knots."""
+    tr = prob._tracking
+    start = tr["start"].astype(np.int64) + np.where(moved, s, 0)
+    if tr["end"] == "refuse":
+        over = np.flatnonzero(start - 1 + prob.N > tr["Nref"])
+        if over.size:
+            b = int(over[0])
+            raise ArgumentError(f"mpc_run: after period {t} the tracking window of trajectory {b} (start {int(start[b])}, N = {prob.N}) runs off the end of "
+                                f"its reference (Nref = {tr['Nref']}); store a longer reference or use end=\"hold\"")
+    else:
+        start = np.minimum(start, tr["Nref"])  # every knot of such a window already tracks the last reference knot
+    set_tracking_window(prob, start.astype(np.int32))
+
+
+def mpc_run(solver, steps, shift=1, x_true=None, plant=None, noise=None, before_solve=None, advance_reference=True, **advance_kw):
     """The closed loop: ``steps`` periods of solve -> ``mpc_advance`` -> solve ... on ``solver.prob``; the true state never leaves the device
     between periods.  ``x_true`` ([B, n] or [n]): where the plant starts (None: the problem's x0).  ``plant`` / ``noise``: the plant that is
     simulated and its noise; period ``t`` draws with ``sample_offset = noise.sample_offset + t``, so the draws of period t, knot k are
     (trajectory, t, k) and ``policy_noise_draws`` reproduces them.  ``before_solve(prob, t)`` runs before the solve of period t (the hook for
-    ``update_trajectory`` / ``set_goal_state``).  Other keywords go to ``mpc_advance``.  Returns an ``MpcRun``."""
+    ``update_trajectory`` / ``set_goal_state``).  ``advance_reference``: when the problem carries a per-trajectory tracking reference
+    (``set_tracking_reference_batch``), after every advance the window starts of the trajectories that moved (advance status 0) grow by
+    ``shift`` and ``set_tracking_window`` is called, so the next solve tracks the reference from where the plan now begins; a trajectory that
+    left the limits keeps its window.  Under ``end="refuse"`` a window that would run off the end raises before the call.  Other keywords go
+    to ``mpc_advance``.  Returns an ``MpcRun``."""
     prob = solver.prob
     _need_mpc_advance(prob)
     steps, s = int(steps), int(shift)
@@ -1587,6 +1607,8 @@ def mpc_run(solver, steps, shift=1, x_true=None, plant=None, noise=None, before_
             X_cl[:, 0] = r.X[:, 0]
         X_cl[:, t * s + 1:(t + 1) * s + 1], U_cl[:, t * s:(t + 1) * s] = r.X[:, 1:], r.U
         adv[t], klim[t] = r.status, r.k_limit
+        if advance_reference and getattr(prob, "_tracking", None) is not None:
+            _advance_tracking_window(prob, r.status == 0, s, t)
     return MpcRun(X_cl, U_cl, its, sts, adv, klim)
 
 
@@ -1870,10 +1892,101 @@ def clear_goal_state_batch(prob):
     prob.xf_batch = None
 
 
+_TRACK_END = {"refuse": capi.TRACK_END_REFUSE, "hold": capi.TRACK_END_HOLD}
+
+
+def _need_tracking_reference(prob, name="set_tracking_reference_batch"):
+    if name not in prob._lib._fn:
+        raise UnsupportedError(f"per-trajectory tracking references need a HIP library that exports to_{name} "
+                               "(the CPU oracle retargets every trajectory with the same update_trajectory)")
+
+
+def _tracking_starts(prob, start):
+    """``start`` (an int, or [B] ints; 1-based) -> contiguous int32 [B].  Shape and type only: the library checks the values."""
+    s = np.asarray(start)
+    if s.dtype == bool or not np.issubdtype(s.dtype, np.integer):
+        raise ArgumentError(f"start must be an integer or [B={prob.B}] integers (1-based); got {s.dtype}")
+    if s.ndim == 0:
+        s = np.full(prob.B, int(s))
+    elif s.shape != (prob.B,):
+        raise DimensionMismatch(f"start must be an integer or [B={prob.B}]; got {s.shape}")
+    if s.size and (s.min() < np.iinfo(np.int32).min or s.max() > np.iinfo(np.int32).max):
+        raise ArgumentError("start does not fit 32 bits")
+    return np.ascontiguousarray(s, dtype=np.int32)
+
+
+def set_tracking_reference_batch(prob, Xref, Uref=None, start=1, end="refuse"):
+    """One tracking reference per TRAJECTORY, windowed on the device (to_set_tracking_reference_batch): ``update_trajectory`` for a fleet
+    whose members follow their own paths, or one path at their own phase.  ``Xref`` is [B, Nref, n] (the layout of ``states`` with Nref
+    for N), ``Uref`` [B, Nref, m] or [B, Nref-1, m] (padded with a zero knot, as ``update_trajectory`` treats a short U) or None (the r
+    terms are then not touched), ``start`` an int or [B] ints, 1-based: knot k (0-based) of trajectory b tracks reference knot
+    ``start[b] - 1 + k``; under ``end="hold"`` knots past the end track the last knot, under ``end="refuse"`` such a window is an error.
+    Needs a tracking objective (a distinct cost per knot).  Only q and r of the costs change, as with ``set_LQR_goal!``; the terms are what
+    N ``set_cost_linear_batch`` calls with q_b = -Q x_ref, r_b = -R u_ref store, bit for bit.  ``set_tracking_window`` moves the windows."""
+    _need_tracking_reference(prob)
+    B, N, n, m = prob.B, prob.N, prob.n, prob.m
+    if end not in _TRACK_END:
+        raise ArgumentError(f"end must be one of {sorted(_TRACK_END)}; got {end!r}")
+    X = np.asarray(Xref, dtype=np.float64)
+    if X.ndim != 3 or X.shape[0] != B or X.shape[2] != n or X.shape[1] < 1:
+        raise DimensionMismatch(f"Xref must be [B={B}, Nref, n={n}]; got {X.shape}")
+    Nref = X.shape[1]
+    U = None
+    if Uref is not None:
+        U = np.asarray(Uref, dtype=np.float64)
+        if U.ndim != 3 or U.shape[0] != B or U.shape[2] != m or U.shape[1] not in (Nref, Nref - 1):
+            raise DimensionMismatch(f"Uref must be [B={B}, Nref={Nref}, m={m}] or [B, Nref-1, m]; got {U.shape}")
+        if U.shape[1] == Nref - 1:
+            U = np.concatenate([U, np.zeros((B, 1, m))], axis=1)
+        U = np.ascontiguousarray(U)
+    s = _tracking_starts(prob, start)
+    X = np.ascontiguousarray(X)
+    prob._call("set_tracking_reference_batch", Nref, prob._pd(X), prob._pd(U) if U is not None else None, prob._pi(s), _TRACK_END[end])
+    prob._tracking = dict(Nref=Nref, end=end, start=s.copy())
+
+
+def set_tracking_window(prob, start):
+    """Move every trajectory's window of the stored reference (to_set_tracking_window): ``start`` an int or [B] ints, 1-based.  4 B bytes go
+    to the device; all N knots are lowered again from the stored reference and the current cost descriptors."""
+    _need_tracking_reference(prob, "set_tracking_window")
+    s = _tracking_starts(prob, start)
+    prob._call("set_tracking_window", prob._pi(s))
+    if getattr(prob, "_tracking", None) is not None:
+        prob._tracking["start"] = s.copy()
+
+
+def get_tracking_window(prob):
+    """(Nref, end, start [B]) of the stored tracking reference (to_get_tracking_window); Nref = 0 while none is set."""
+    _need_tracking_reference(prob, "get_tracking_window")
+    Nref, mode, s = C.c_int32(0), C.c_int32(0), np.empty(prob.B, np.int32)
+    prob._call("get_tracking_window", C.byref(Nref), C.byref(mode), prob._pi(s))
+    return Nref.value, {v: k for k, v in _TRACK_END.items()}[mode.value], s
+
+
+def clear_tracking_reference_batch(prob):
+    """Free the stored reference and return every cost to its descriptor (to_clear_tracking_reference_batch): a solve after it equals the
+    same solve on a fresh problem bit for bit.  (``clear_goal_state_batch`` returns the costs to their descriptors and KEEPS the reference.)"""
+    _need_tracking_reference(prob, "clear_tracking_reference_batch")
+    prob._call("clear_tracking_reference_batch")
+    prob._tracking = None
+
+
+def get_cost_linear_batch(prob, cost_id):
+    """(q [B, n], r [B, m]): the linear terms cost ``cost_id`` (0-based position among the problem's distinct costs) evaluates for every
+    trajectory (to_get_cost_linear_batch) — the descriptor's, repeated, while no per-trajectory terms are set."""
+    _need_tracking_reference(prob, "get_cost_linear_batch")
+    q, r = np.empty((prob.B, prob.n)), np.empty((prob.B, prob.m))
+    prob._call("get_cost_linear_batch", int(cost_id), prob._pd(q), prob._pd(r))
+    return q, r
+
+
 def update_trajectory(prob, X, U, start=1):
     """update_trajectory!(obj, Z, start)  (src/objective.jl:198-212): retarget a tracking objective (one cost per knot,
     see TrackingObjective) to knots start..start+N-1 of the reference (X [n, Nref], U [m, >=Nref-1]); like
-    set_LQR_goal! it changes only q and r, never the constant c (src/cost_functions.jl:249-258)."""
+    set_LQR_goal! it changes only q and r, never the constant c (src/cost_functions.jl:249-258).  A 3-D ``X`` ([B, Nref, n], with ``U``
+    [B, Nref, m], [B, Nref-1, m] or None and ``start`` an int or [B]) is one reference per trajectory: ``set_tracking_reference_batch``."""
+    if np.ndim(X) == 3:
+        return set_tracking_reference_batch(prob, X, U, start)
     if getattr(prob, "hybrid", False):
         raise UnsupportedError("update_trajectory on a hybrid model vector: the knots have different dimensions; rebuild the problem")
     X = np.asarray(X, dtype=np.float64)

@@ -258,6 +258,83 @@ inline void shared_constraint_limits(const DevCon& ci, int q, double* out) {
   for (int i = 0; i < q; ++i) out[i] = ci.soff[q == 1 && ci.d.kind == TO_CON_NORM ? ci.p - 1 : i];
 }
 
+// One tracking reference per trajectory (to_set_tracking_reference_batch / to_set_tracking_window): every refusal of the two entry points,
+// decided from what the host knows of the handle before any device call.  TrackFacts: those facts (model_key as in handle.h ModelOps: 7 the
+// hybrid double integrator, 8 model vectors, 9 .. 11 InfeasibleModel; Nref_set = 0 while no reference is stored).
+struct TrackFacts {
+  int model_key; const char* model_name;
+  int n, m, N, B;
+  const to_cost_desc* costs; int n_costs; const int* cost_index /* [N] */;
+  bool in_flight;
+  int Nref_set, end_mode_set;
+};
+// the window itself: start[B] (NULL: 1 for all) against a reference of Nref knots
+inline int validate_tracking_starts(const char* who, int N, int B, int Nref, int end_mode, const int32_t* start) {
+  for (int b = 0; b < B; ++b) {
+    const long long s = start ? start[b] : 1;
+    if (s < 1) return fail(TO_ERR_ARGUMENT, std::string(who) + ": start of trajectory " + std::to_string(b) + " is " + std::to_string(s) + " (1-based: must be >= 1)");
+    if (end_mode == TO_TRACK_END_HOLD && s > Nref)
+      return fail(TO_ERR_ARGUMENT, std::string(who) + ": start of trajectory " + std::to_string(b) + " is " + std::to_string(s) + ", behind the reference (Nref = " +
+                                       std::to_string(Nref) + ")");
+    if (end_mode == TO_TRACK_END_REFUSE && s - 1 + N > Nref)  // update_trajectory!'s BoundsError (src/objective.jl:198-212)
+      return fail(TO_ERR_ARGUMENT, std::string(who) + ": reference trajectory too short for trajectory " + std::to_string(b) + ": start " + std::to_string(s) +
+                                       " - 1 + N = " + std::to_string(s - 1 + N) + " > Nref = " + std::to_string(Nref) + " (TO_TRACK_END_HOLD tracks the last knot instead)");
+  }
+  return TO_OK;
+}
+// what both entry points ask of the handle: idle, a model whose knots share one state, a cost of its own on every knot, no ErrorQuadratic
+inline int validate_tracking_target(const char* who, const TrackFacts& f) {
+  if (f.in_flight) return fail(TO_ERR_ARGUMENT, "an asynchronous solve is in flight on this handle (call to_solve_wait first)");
+  if (f.model_key >= 7)
+    return fail(TO_ERR_UNSUPPORTED, std::string(who) + ": not available for the " + f.model_name +
+                                        " (TO_MODEL_HYBRID_DOUBLE_INTEGRATOR, TO_MODEL_VECTOR and TO_MODEL_INFEASIBLE have no per-trajectory tracking reference)");
+  for (int k = 0; k < f.N; ++k)
+    for (int l = k + 1; l < f.N; ++l)
+      if (f.cost_index[k] == f.cost_index[l])
+        return fail(TO_ERR_ARGUMENT, std::string(who) + " needs a tracking objective (a distinct cost per knot): knots " + std::to_string(k + 1) + " and " +
+                                         std::to_string(l + 1) + " share cost " + std::to_string(f.cost_index[k]));
+  for (int k = 0; k < f.N; ++k)
+    if (f.costs[f.cost_index[k]].kind == TO_COST_ERROR_QUADRATIC)
+      return fail(TO_ERR_UNSUPPORTED, std::string(who) + ": the cost of knot " + std::to_string(k + 1) + " is ErrorQuadratic (its q slot carries x_ref)");
+  return TO_OK;
+}
+inline int validate_tracking_reference(const TrackFacts& f, int Nref, const double* Xref, const double* Uref, const int32_t* start, int end_mode) {
+  const char* who = "to_set_tracking_reference_batch";
+  if (f.in_flight) return validate_tracking_target(who, f);
+  if (!Xref) return fail(TO_ERR_NULL, std::string(who) + ": Xref is NULL");
+  if (int r = validate_tracking_target(who, f)) return r;
+  if (Nref < 1) return fail(TO_ERR_ARGUMENT, std::string(who) + ": Nref must be >= 1; got " + std::to_string(Nref));
+  if (end_mode != TO_TRACK_END_REFUSE && end_mode != TO_TRACK_END_HOLD)
+    return fail(TO_ERR_ARGUMENT, std::string(who) + ": end_mode must be TO_TRACK_END_REFUSE (0) or TO_TRACK_END_HOLD (1)");
+  for (int b = 0; b < f.B; ++b)
+    for (int j = 0; j < Nref; ++j) {
+      bool ok = true;
+      for (int i = 0; i < f.n; ++i) ok = ok && std::isfinite(Xref[i + (size_t)f.n * (j + (size_t)Nref * b)]);
+      for (int i = 0; Uref && i < f.m; ++i) ok = ok && std::isfinite(Uref[i + (size_t)f.m * (j + (size_t)Nref * b)]);
+      if (!ok) return fail(TO_ERR_ARGUMENT, std::string(who) + ": the reference of trajectory " + std::to_string(b) + " is not finite at knot " + std::to_string(j + 1));
+    }
+  return validate_tracking_starts(who, f.N, f.B, Nref, end_mode, start);
+}
+inline int validate_tracking_window(const TrackFacts& f, const int32_t* start) {
+  const char* who = "to_set_tracking_window";
+  if (f.in_flight) return validate_tracking_target(who, f);
+  if (!start) return fail(TO_ERR_NULL, std::string(who) + ": start is NULL");
+  if (f.Nref_set < 1) return fail(TO_ERR_ARGUMENT, std::string(who) + ": no tracking reference is set (to_set_tracking_reference_batch first)");
+  if (int r = validate_tracking_target(who, f)) return r;
+  return validate_tracking_starts(who, f.N, f.B, f.Nref_set, f.end_mode_set, start);
+}
+// the reference in the layout upload_vec takes: rows [x_ref[j]; u_ref[j]] (u rows zero without Uref), [(n+m) Nref, B]
+inline void pack_tracking_reference(int n, int m, int B, int Nref, const double* Xref, const double* Uref, std::vector<double>* out) {
+  const int nz = n + m;
+  out->assign((size_t)nz * Nref * B, 0.0);
+  for (int b = 0; b < B; ++b)
+    for (int j = 0; j < Nref; ++j) {
+      double* z = out->data() + (size_t)nz * (j + (size_t)Nref * b);
+      for (int i = 0; i < n; ++i) z[i] = Xref[i + (size_t)n * (j + (size_t)Nref * b)];
+      for (int i = 0; Uref && i < m; ++i) z[n + i] = Uref[i + (size_t)m * (j + (size_t)Nref * b)];
+    }
+}
+
 // Per-trajectory time steps (to_set_time_steps_batch): dt[(N-1), B], knot fastest, column b read exactly like to_problem_desc::dt.
 // lower_time_steps checks every value — finite and > 0, the check the descriptor's own steps get at to_create; there is NO "must sum to
 // tf - t0" check: trajectory b ends at its own tf_b = t0 + sum_k dt_b[k] — and tiles them the way DevProblem::dtb is read: step k of

@@ -80,6 +80,12 @@ struct to_handle_s {
   int* d_crow = nullptr;    // [64] compact_row table of the model (tangent-matrix getters)
   std::vector<char> gl_set; // [n_costs] cost i carries per-trajectory linear terms (all clear: DevProblem::gl goes back to null)
   double* d_gl = nullptr;   // per-trajectory linear cost terms (DevProblem::gl), tiled, L = n_costs * (n + m); allocated on first use
+  // one tracking reference per trajectory (to_set_tracking_reference_batch; k_track.h lowers a window of it into d_gl)
+  double* d_track_ref = nullptr;      // tiled, L = track_Nref * (n + m): rows [x_ref[j]; u_ref[j]] (u rows zero while track_u is false)
+  int* d_track_start = nullptr;       // [B] 1-based window starts, re-uploaded by every window call
+  std::vector<int32_t> track_start;   // host copy of the starts (to_get_tracking_window)
+  int track_Nref = 0, track_end = 0;  // knots of the stored reference (0: none) and its end mode (TO_TRACK_END_*)
+  bool track_u = false;               // the reference carries controls
   double* d_pm = nullptr;   // per-trajectory model parameters (DevProblem::pm), tiled, L = 16, one spare tile; allocated on first use
   std::vector<double> pm_host;  // [16, B] host copy of what DevProblem::pm holds: what to_set_model_params_batch was given, or — pm_own false, the handle
                                 // carries per-trajectory time steps only — the shared parameters repeated (empty: DevProblem::pm is null)

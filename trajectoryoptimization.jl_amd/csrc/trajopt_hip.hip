@@ -21,6 +21,7 @@
 #include "handle.h"
 #include "k_generic.h"
 #include "k_mpc.h"
+#include "k_track.h"
 
 using namespace to;
 
@@ -1857,6 +1858,89 @@ int to_mpc_advance(to_handle* h, const double* x_meas, const to_mpc_opts* mpc, c
   TRY(launch_rollout(h));  // the state to_set_initial_state + to_set_controls + to_rollout would have left
   HIPCHECK(hipStreamSynchronize(h->stream));
   return check_guards(h, "to_mpc_advance");
+}
+// ---- one tracking reference per trajectory, windowed on the device (k_track.h) --------------------------------------------------------
+static TrackFacts track_facts(const to_handle* h) {
+  const DevProblem& P = h->a.P;
+  return TrackFacts{h->model_key, model_key_name(h->model_key), P.n, P.m, P.N, P.B, h->costs.data(), (int)h->costs.size(), h->cost_index.data(),
+                    h->inflight.load(), h->track_Nref, h->track_end};
+}
+// the stored starts -> the device, then all N knots of every trajectory into d_gl from the current descriptors (one launch)
+static int track_lower(to_handle* h, const char* who) {
+  DevProblem& P = h->a.P;
+  const int nz = P.n + P.m, L = (int)h->costs.size() * nz;
+  if (!h->d_gl) {  // zero-filled: every cost starts with its descriptor's terms (as in to_set_cost_linear_batch)
+    TRY(dev_alloc(h, &h->d_gl, (size_t)L * P.Bp));
+    h->gl_set.assign(h->costs.size(), 0);
+  }
+  HIPCHECK(hipMemcpyAsync(h->d_track_start, h->track_start.data(), sizeof(int32_t) * P.B, hipMemcpyHostToDevice, h->stream));
+  TrackArgs ta;
+  ta.n = P.n; ta.m = P.m; ta.N = P.N; ta.B = P.B; ta.Nref = h->track_Nref; ta.with_u = h->track_u ? 1 : 0; ta.n_costs = (int)h->costs.size();
+  ta.ref = h->d_track_ref; ta.start = h->d_track_start; ta.cost_index = P.cost_index; ta.costs = P.costs; ta.gl = h->d_gl;
+  const int rows = P.N * (h->track_u ? nz : P.n);
+  TRY(launch(k_track_lower, dim3((unsigned)(P.Bp / 64), (unsigned)std::min(rows, 32)), dim3(BLOCK), 0, h->stream, ta));
+  HIPCHECK(hipStreamSynchronize(h->stream));
+  P.gl = h->d_gl;
+  for (int k = 0; k < P.N; ++k) h->gl_set[h->cost_index[k]] = 1;
+  return check_guards(h, who);
+}
+int to_set_tracking_reference_batch(to_handle* h, int32_t Nref, const double* Xref, const double* Uref, const int32_t* start, int32_t end_mode) {
+  CHECK_H(h);
+  TRY(validate_tracking_reference(track_facts(h), Nref, Xref, Uref, start, end_mode));  // every refusal, before any device call
+  TRY(use_device(h));
+  const DevProblem& P = h->a.P;
+  const int nz = P.n + P.m, B = P.B;
+  std::vector<double> packed;
+  pack_tracking_reference(P.n, P.m, B, Nref, Xref, Uref, &packed);
+  dev_release(h, &h->d_track_ref);  // (a reference of another length replaces the stored one)
+  h->track_Nref = 0;
+  TRY(dev_alloc(h, &h->d_track_ref, (size_t)Nref * nz * P.Bp));
+  if (!h->d_track_start) TRY(dev_alloc(h, &h->d_track_start, (size_t)P.Bp));
+  TRY(upload_vec(h, packed.data(), h->d_track_ref, Nref * nz));
+  h->track_start.assign(B, 1);
+  if (start) std::copy(start, start + B, h->track_start.begin());
+  h->track_Nref = Nref; h->track_end = end_mode; h->track_u = Uref != nullptr;
+  return track_lower(h, "to_set_tracking_reference_batch");
+}
+int to_set_tracking_window(to_handle* h, const int32_t* start) {
+  CHECK_H(h);
+  TRY(validate_tracking_window(track_facts(h), start));
+  TRY(use_device(h));
+  std::copy(start, start + h->a.P.B, h->track_start.begin());
+  return track_lower(h, "to_set_tracking_window");
+}
+int to_get_tracking_window(to_handle* h, int32_t* Nref, int32_t* end_mode, int32_t* start) {
+  CHECK_H(h);
+  if (Nref) *Nref = h->track_Nref;
+  if (end_mode) *end_mode = h->track_Nref ? h->track_end : TO_TRACK_END_REFUSE;
+  if (start) for (int b = 0; b < h->a.P.B; ++b) start[b] = h->track_Nref ? h->track_start[b] : 1;
+  return TO_OK;
+}
+int to_clear_tracking_reference_batch(to_handle* h) {
+  CHECK_H(h); CHECK_IDLE(h); TRY(use_device(h));
+  dev_release(h, &h->d_track_ref);
+  dev_release(h, &h->d_track_start);
+  h->track_start.clear();
+  h->track_Nref = 0; h->track_end = 0; h->track_u = false;
+  return to_clear_cost_linear_batch(h);
+}
+int to_get_cost_linear_batch(to_handle* h, int32_t id, double* q, double* r) {
+  CHECK_H(h); CHECK_IDLE(h); TRY(use_device(h));
+  if (id < 0 || id >= (int)h->costs.size()) return fail(TO_ERR_ARGUMENT, "cost id out of range");
+  if (!q && !r) return fail(TO_ERR_NULL, "null pointer");
+  const to_cost_desc& c = h->costs[id];
+  const DevProblem& P = h->a.P;
+  const int n = P.n, m = P.m, nz = n + m, L = (int)h->costs.size() * nz, B = P.B;
+  // what the kernels evaluate: the descriptor's term plus the stored difference (zero while nothing is set)
+  if (q) {
+    if (h->d_gl) TRY(download_vec(h, q, h->d_gl, n, L, id * nz));
+    for (int b = 0; b < B; ++b) for (int i = 0; i < n; ++i) q[i + (size_t)n * b] = h->d_gl ? c.q[i] + q[i + (size_t)n * b] : c.q[i];
+  }
+  if (r) {
+    if (h->d_gl) TRY(download_vec(h, r, h->d_gl, m, L, id * nz + n));
+    for (int b = 0; b < B; ++b) for (int j = 0; j < m; ++j) r[j + (size_t)m * b] = h->d_gl ? c.r[j] + r[j + (size_t)m * b] : c.r[j];
+  }
+  return TO_OK;
 }
 // the generator alone (k_policy_noise_draws), so that a parity failure of the stochastic rollout can be localised to it or to the loop
 int to_policy_noise_draws(int device, uint64_t seed, uint32_t traj, uint32_t sample, uint32_t k, uint32_t kind, int32_t pairs, double* z) {
