@@ -82,7 +82,10 @@ extern "C" {
  * from to_policy_rollout, to_set_initial_state, to_set_controls and to_rollout.  And for to_set_tracking_reference_batch /
  * to_set_tracking_window / to_get_tracking_window / to_clear_tracking_reference_batch / to_get_cost_linear_batch (one tracking reference and
  * one window of it per trajectory): five symbols added with TO_ABI_VERSION and TO_ABI_MINOR unchanged and no existing struct changed, found
- * by symbol lookup; with a library without them a host feeds each knot's terms through to_set_cost_linear_batch. */
+ * by symbol lookup; with a library without them a host feeds each knot's terms through to_set_cost_linear_batch.  And for
+ * to_set_cost_weights_batch / to_get_cost_weights_batch / to_clear_cost_weights_batch (one diagonal Q / R per trajectory): three symbols added
+ * with TO_ABI_VERSION and TO_ABI_MINOR unchanged and no existing struct changed, found by symbol lookup; a library without them shares the
+ * weights of every cost among the trajectories of a handle. */
 #define TO_ABI_VERSION 7
 #define TO_ABI_MINOR 1
 
@@ -437,6 +440,28 @@ int to_set_tracking_window(to_handle* h, const int32_t* start /* [B], 1-based */
 int to_get_tracking_window(to_handle* h, int32_t* Nref, int32_t* end_mode, int32_t* start /* [B]; any may be NULL */);
 int to_clear_tracking_reference_batch(to_handle* h);
 int to_get_cost_linear_batch(to_handle* h, int32_t cost_id, double* q /* [n*B] or NULL */, double* r /* [m*B] or NULL */);
+/* One set of cost WEIGHTS per TRAJECTORY: a weight sweep, a cost auto-tuning loop, a fleet whose members trade tracking error against effort
+ * differently, a robustness study over Qf — on one handle.  Cost cost_id (the position among the problem's distinct costs, as in to_set_cost) of
+ * trajectory b is the descriptor's cost with its diagonal Q replaced by Q[:, b] (Q is [n, B], n fastest), its diagonal R by R[:, b] ([m, B]), or
+ * both; a NULL argument leaves that block as it is.  q, r, c, w, q_ref and terminal stay the descriptor's, and the per-trajectory linear terms
+ * of to_set_cost_linear_batch still add to q and r (they are NOT recomputed: a goal -Q_b xf_b is the caller's to set).  Accepted kinds:
+ * TO_COST_DIAGONAL and TO_COST_DIAGONAL_QUAT (its w stays shared); TO_COST_QUADRATIC and TO_COST_ERROR_QUADRATIC — TO_ERR_UNSUPPORTED, by
+ * name.  Refused before anything changes: a cost_id out of range, Q and R both NULL, a solve in flight, a value that is not finite (naming the
+ * first offending trajectory and entry) — TO_ERR_ARGUMENT; the values are otherwise held to what to_set_cost asks of a descriptor's Q and R,
+ * no more (the reference only warns about definiteness, src/cost_functions.jl:337-343); the hybrid double integrator, model vectors and
+ * InfeasibleModel, and a handle that holds a tracking reference (to_set_tracking_reference_batch lowers -Q x_ref from the descriptors; it in
+ * turn refuses a handle with weights) — TO_ERR_UNSUPPORTED.  Everything that evaluates the cost — to_cost, to_stage_costs, to_al_cost, the
+ * line search, the expansion, to_cost_expansion, the projected-Newton polish's metric, J of to_policy_rollout and to_mpc_advance — then reads
+ * trajectory b's own weights: the expression a single-trajectory problem built with them evaluates.  The solves run the general kernel
+ * variants while weights are set (as with to_set_constraint_limits_batch: no scan, fused cooperative or packed kernel, no forward-list mode,
+ * no preloaded stage cost).  The setter leaves X, U, duals and gains as they are.  to_get_... returns what every trajectory is evaluated
+ * with: what was set, or the descriptor's diagonal repeated B times (either pointer may be NULL, not both).  to_set_cost on a cost restarts
+ * THAT cost's weights from the new descriptor; to_clear_... returns every cost to its descriptor and the handle to the kernel variants it ran
+ * before — a solve after it is bit-identical to the same solve on a fresh handle.  Not announced by TO_ABI_MINOR: look the symbols up (ABI
+ * history above). */
+int to_set_cost_weights_batch(to_handle* h, int32_t cost_id, const double* Q /* [n*B] or NULL */, const double* R /* [m*B] or NULL */);
+int to_get_cost_weights_batch(to_handle* h, int32_t cost_id, double* Q /* [n*B] or NULL */, double* R /* [m*B] or NULL */);
+int to_clear_cost_weights_batch(to_handle* h);
 /* One constraint-parameter set per TRAJECTORY (round 6): set_goal_state!(prob, xf; constraint = true) updates the GoalConstraints too
  * (src/problem.jl:303-309, src/constraints.jl:22-87) — here for every trajectory of the batch at once.  con_id names a GOAL constraint,
  * params[p, B] (column-major) = xf_b[inds], the target of trajectory b — or a LINEAR constraint (src/constraints.jl:103-150), params[p, B] =

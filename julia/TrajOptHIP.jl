@@ -952,6 +952,33 @@ function cost_linear_batch(p::BatchProblem, i::Integer)
     check(ccall((:to_get_cost_linear_batch, lib), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}), p.handle, i - 1, q, r))
     (q = q, r = r)
 end
+"""
+    set_cost_weights_batch!(p, i; Q = nothing, R = nothing)     # Q :: (n, B), R :: (m, B); cost i is 1-based
+One diagonal `Q` / `R` per trajectory for cost `i` (`to_set_cost_weights_batch`): trajectory `b` evaluates the cost with `Q[:, b]` and
+`R[:, b]` in place of the descriptor's diagonals; `q`, `r`, `c`, `w` stay the descriptor's.  `DiagonalCost` and `DiagonalQuatCost` only.
+`cost_weights_batch(p, i)` returns what every trajectory is evaluated with (the descriptor's diagonal repeated if nothing is set),
+`clear_cost_weights_batch!(p)` returns every cost to its descriptor.  Added without raising `TO_ABI_MINOR`: a library that lacks them is
+detected by symbol lookup (`has_cost_weights_batch()`).
+"""
+has_cost_weights_batch() = Libdl.dlsym(Libdl.dlopen(lib), :to_set_cost_weights_batch; throw_error = false) !== nothing
+function set_cost_weights_batch!(p::BatchProblem, i::Integer; Q::Union{Nothing, Matrix{Float64}} = nothing, R::Union{Nothing, Matrix{Float64}} = nothing)
+    has_cost_weights_batch() || error("libtrajopt_hip.so does not export to_set_cost_weights_batch")
+    Q === nothing || size(Q) == (p.n, p.B) || throw(DimensionMismatch("Q must be (n, B)"))
+    R === nothing || size(R) == (p.m, p.B) || throw(DimensionMismatch("R must be (m, B)"))
+    check(ccall((:to_set_cost_weights_batch, lib), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}), p.handle, i - 1, Q === nothing ? C_NULL : Q, R === nothing ? C_NULL : R))
+    nothing
+end
+function cost_weights_batch(p::BatchProblem, i::Integer)
+    has_cost_weights_batch() || error("libtrajopt_hip.so does not export to_get_cost_weights_batch")
+    Q, R = zeros(p.n, p.B), zeros(p.m, p.B)
+    check(ccall((:to_get_cost_weights_batch, lib), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}), p.handle, i - 1, Q, R))
+    (Q = Q, R = R)
+end
+function clear_cost_weights_batch!(p::BatchProblem)
+    has_cost_weights_batch() || error("libtrajopt_hip.so does not export to_clear_cost_weights_batch")
+    check(ccall((:to_clear_cost_weights_batch, lib), Cint, (Ptr{Cvoid},), p.handle))
+    nothing
+end
 function clear_goal_state_batch!(p::BatchProblem)
     check(ccall((:to_clear_cost_linear_batch, lib), Cint, (Ptr{Cvoid},), p.handle))
     check(ccall((:to_clear_constraint_params_batch, lib), Cint, (Ptr{Cvoid},), p.handle))
@@ -1105,7 +1132,7 @@ function profile(p::BatchProblem)
     (kernel_ms = ms, launches = launches)
 end
 
-export LinearMap, MassDoubleIntegrator, BatchProblem, set_model_params_batch!, model_params_batch, clear_model_params_batch!, has_model_params_batch, set_constraint_limits_batch!, get_constraint_limits_batch, clear_constraint_limits_batch!, has_constraint_limits_batch, set_time_steps_batch!, set_final_times_batch!, time_steps_batch, clear_time_steps_batch!, has_time_steps_batch, policy_rollout, PolicyOpts, PolicyResult, policy_rollout_mc, policy_noise_draws, PolicyNoise, mpc_advance!, has_mpc_advance, MpcOpts, MpcResult, set_tracking_window!, tracking_window, clear_tracking_reference_batch!, cost_linear_batch, has_tracking_reference_batch, abi_minor, SolverOpts, solver_options, default_options, solve_ilqr!, solve_al!, solve_pn!, solve_altro!, solve_async!, wait_solve!, dynamics_defect, expand!, backwardpass!, forwardpass!,
+export LinearMap, MassDoubleIntegrator, BatchProblem, set_model_params_batch!, model_params_batch, clear_model_params_batch!, has_model_params_batch, set_constraint_limits_batch!, get_constraint_limits_batch, clear_constraint_limits_batch!, has_constraint_limits_batch, set_time_steps_batch!, set_final_times_batch!, time_steps_batch, clear_time_steps_batch!, has_time_steps_batch, policy_rollout, PolicyOpts, PolicyResult, policy_rollout_mc, policy_noise_draws, PolicyNoise, mpc_advance!, has_mpc_advance, MpcOpts, MpcResult, set_tracking_window!, tracking_window, clear_tracking_reference_batch!, cost_linear_batch, has_tracking_reference_batch, set_cost_weights_batch!, cost_weights_batch, clear_cost_weights_batch!, has_cost_weights_batch, abi_minor, SolverOpts, solver_options, default_options, solve_ilqr!, solve_al!, solve_pn!, solve_altro!, solve_async!, wait_solve!, dynamics_defect, expand!, backwardpass!, forwardpass!,
     stage_costs, al_cost, dynamics_jacobians, cost_expansion, gains, cost_gradient_hessian, discrete_jacobian, duals, set_duals!,
     reset_duals!, dual_update!, comm_unique_id, comm_init_rank!, allgather!, allgather_stats, comm_shards, comm_destroy!, solver_path, knot_dims, device_count, build_id
 

@@ -288,6 +288,10 @@ HIP_ONLY = {
     "get_tracking_window": [_H, _PI, _PI, _PI],
     "clear_tracking_reference_batch": [_H],
     "get_cost_linear_batch": [_H, C.c_int32, _PD, _PD],
+    # one diagonal Q / R per trajectory (OPTIONAL_HIP below)
+    "set_cost_weights_batch": [_H, C.c_int32, _PD, _PD],
+    "get_cost_weights_batch": [_H, C.c_int32, _PD, _PD],
+    "clear_cost_weights_batch": [_H],
 }
 # Entry points added without raising TO_ABI_MINOR (include/trajopt_hip.h, ABI history): detected by symbol lookup.  A library that does
 # not export them still loads; the names are then absent from Library._fn and the wrappers in api.py raise UnsupportedError.
@@ -296,7 +300,8 @@ OPTIONAL_HIP = ("set_model_params_batch", "get_model_params_batch", "clear_model
                 "set_time_steps_batch", "get_time_steps_batch", "clear_time_steps_batch",
                 "mpc_advance",
                 "set_tracking_reference_batch", "set_tracking_window", "get_tracking_window", "clear_tracking_reference_batch",
-                "get_cost_linear_batch")
+                "get_cost_linear_batch",
+                "set_cost_weights_batch", "get_cost_weights_batch", "clear_cost_weights_batch")
 
 
 class Library:

@@ -46,7 +46,8 @@ __all__ = [
     "KnotPoint", "Problem", "rollout", "policy_rollout", "PolicyRollout", "PolicyNoise", "policy_noise_draws", "mpc_advance", "MpcAdvance", "mpc_run", "MpcRun", "set_model_params", "model_params", "clear_model_params",
     "set_time_steps_batch", "set_final_times_batch", "time_steps", "clear_time_steps_batch", "cost", "states", "controls", "initial_controls", "initial_states",
     "set_initial_state", "set_goal_state", "update_trajectory", "set_tracking_reference_batch", "set_tracking_window", "get_tracking_window",
-    "clear_tracking_reference_batch", "get_cost_linear_batch", "get_constraints", "get_objective", "get_model",
+    "clear_tracking_reference_batch", "get_cost_linear_batch", "set_cost_weights_batch", "get_cost_weights_batch", "clear_cost_weights_batch",
+    "set_LQR_weights_batch", "get_constraints", "get_objective", "get_model",
     "get_initial_state", "get_final_state", "get_trajectory", "gettimes",
     "SolverOptions", "iLQRSolver", "ALSolver", "ALTROSolver", "ProjectedNewtonSolver", "dynamics_defect", "solve", "SolvePipeline", "iterations", "status", "max_violation",
     "evaluate_constraints", "constraint_jacobians", "sense", "upper_bound", "lower_bound", "is_bound",
@@ -1978,6 +1979,82 @@ def get_cost_linear_batch(prob, cost_id):
     q, r = np.empty((prob.B, prob.n)), np.empty((prob.B, prob.m))
     prob._call("get_cost_linear_batch", int(cost_id), prob._pd(q), prob._pd(r))
     return q, r
+
+
+def _need_cost_weights_batch(prob):
+    if "set_cost_weights_batch" not in prob._lib._fn:
+        raise UnsupportedError("per-trajectory cost weights need a HIP library that exports to_set_cost_weights_batch "
+                               "(the CPU oracle shares the weights of every cost among the trajectories of a problem)")
+
+
+def _weights_arg(prob, a, k, name):
+    """``a`` ([B, k], or None) -> contiguous [B, k] doubles == column-major (k, B), or None."""
+    if a is None:
+        return None
+    a = np.asarray(a, dtype=np.float64)
+    if a.shape != (prob.B, k):
+        raise DimensionMismatch(f"{name} must be [B, {'n' if name == 'Q' else 'm'}] = {(prob.B, k)}; got {a.shape}")
+    return np.ascontiguousarray(a)
+
+
+def set_cost_weights_batch(prob, cost_id, Q=None, R=None):
+    """One diagonal Q / R per TRAJECTORY for cost ``cost_id`` (0-based position among the problem's distinct costs, as in
+    ``get_cost_linear_batch``; to_set_cost_weights_batch): ``Q`` [B, n], ``R`` [B, m]; one left out keeps that block as it is.  DiagonalCost
+    and DiagonalQuatCost only (w stays shared).  q, r, c stay the descriptor's — a goal's q_b = -Q_b xf_b is ``set_LQR_weights_batch``'s
+    business.  X, U, duals and gains stay as they are."""
+    _need_cost_weights_batch(prob)
+    if Q is None and R is None:
+        raise ArgumentError("set_cost_weights_batch: give Q, R or both")
+    Qa, Ra = _weights_arg(prob, Q, prob.n, "Q"), _weights_arg(prob, R, prob.m, "R")
+    prob._call("set_cost_weights_batch", int(cost_id), prob._pd(Qa) if Qa is not None else None, prob._pd(Ra) if Ra is not None else None)
+
+
+def get_cost_weights_batch(prob, cost_id):
+    """(Q [B, n], R [B, m]): the diagonal weights cost ``cost_id`` evaluates for every trajectory (to_get_cost_weights_batch) — the
+    descriptor's, repeated, while none are set."""
+    _need_cost_weights_batch(prob)
+    Q, R = np.empty((prob.B, prob.n)), np.empty((prob.B, prob.m))
+    prob._call("get_cost_weights_batch", int(cost_id), prob._pd(Q), prob._pd(R))
+    return Q, R
+
+
+def clear_cost_weights_batch(prob):
+    """Every cost back to the weights of its descriptor (to_clear_cost_weights_batch): a solve after it equals the same solve on a fresh
+    problem bit for bit.  (Per-trajectory linear terms, ``set_goal_state`` with a matrix, are ``clear_goal_state_batch``'s.)"""
+    _need_cost_weights_batch(prob)
+    prob._call("clear_cost_weights_batch")
+
+
+def set_LQR_weights_batch(prob, Q, R, Qf=None, xf=None, uf=None):
+    """An LQR objective per TRAJECTORY: every stage cost gets ``Q`` [B, n], ``R`` [B, m]; every terminal cost ``Qf`` [B, n] (left alone
+    when None) and the same R.  With goals — ``xf`` ([n] or [B, n]; default: the problem's own ``xf_batch`` / ``xf`` when it has one) and
+    ``uf`` ([m] or [B, m]; default 0 when a state goal is in play) — the linear terms follow: q_b = -Q_b xf_b, r_b = -R_b uf_b through
+    to_set_cost_linear_batch, exactly what ``set_LQR_goal!`` would store for a cost with those weights (src/cost_functions.jl:249-258).
+    The constant ``c`` stays the descriptor's, as ``set_LQR_goal!`` leaves it: costs differ from those of a problem built with
+    ``LQRObjective(Q_b, R_b, Qf_b, xf_b)`` by a constant per trajectory, the solutions do not."""
+    _need_cost_weights_batch(prob)
+    B, n, m = prob.B, prob.n, prob.m
+    Qa, Ra, Qfa = _weights_arg(prob, Q, n, "Q"), _weights_arg(prob, R, m, "R"), _weights_arg(prob, Qf, n, "Q")
+    if Qa is None or Ra is None:
+        raise ArgumentError("set_LQR_weights_batch: Q and R are both needed")
+    if xf is None:
+        xf = getattr(prob, "xf_batch", None)
+    if xf is None and not np.isnan(prob.xf).any():
+        xf = prob.xf
+    Xf = Uf = None
+    if xf is not None or uf is not None:
+        Xf = np.zeros((B, n)) if xf is None else np.broadcast_to(np.asarray(xf, dtype=np.float64), (B, n))
+        Uf = np.zeros((B, m)) if uf is None else np.broadcast_to(np.asarray(uf, dtype=np.float64), (B, m))
+    for i, c in enumerate(prob._cost_objs):
+        Qi = Qfa if c.terminal else Qa
+        if Qi is None:
+            continue
+        prob._call("set_cost_weights_batch", i, prob._pd(Qi), prob._pd(Ra))
+        if Xf is not None:
+            q, r = np.ascontiguousarray(-(Qi * Xf)), np.ascontiguousarray(-(Ra * Uf))
+            prob._call("set_cost_linear_batch", i, prob._pd(q), prob._pd(r))
+    if xf is not None and np.asarray(xf).ndim == 2:
+        prob.xf_batch = np.array(Xf)
 
 
 def update_trajectory(prob, X, U, start=1):

@@ -135,13 +135,16 @@ __device__ __forceinline__ double* slot_ptr(double* nominal, double* cand, const
 // gl0: this lane's pointer into DevProblem::gl (per-trajectory linear cost terms; nullptr: none)
 // cp0 / cl0: this lane's pointers into DevProblem::cp / cl (per-trajectory constraint parameters / limits; general variants only)
 // dt0: dt_lane of this lane's trajectory (per-trajectory time steps, problem_dev.h step_dt), or nothing: the shared steps, read as ever
-template <class M, bool GEN = true, class D = std::nullptr_t>
+// gw0: this lane's pointer to entry 0 of DevProblem::gw (per-trajectory cost weights, problem_dev.h cost_wq), or nothing: the descriptors' weights
+template <int nz> __device__ __forceinline__ std::nullptr_t cost_block(std::nullptr_t, int) { return nullptr; }
+template <int nz> __device__ __forceinline__ const double* cost_block(const double* gw0, int ci) { return gw0 + (size_t)ci * nz * 64; }
+template <class M, bool GEN = true, class D = std::nullptr_t, class W = std::nullptr_t>
 __device__ __forceinline__ double knot_cost(const DevProblem& P, int k, const double* x, const double* u, const double* lam0,
                                             const double* mu0, bool with_al, const double* gl0 = nullptr, const double* cp0 = nullptr,
-                                            const double* cl0 = nullptr, D dt0 = nullptr) {
+                                            const double* cl0 = nullptr, D dt0 = nullptr, W gw0 = nullptr) {
   constexpr int n = M::n, m = M::m, nz = n + m;
   const int cidx = P.cost_index[k];
-  double Jk = cost_eval<n, m, GEN>(P.costs[cidx], x, u);
+  double Jk = cost_eval<n, m, GEN>(P.costs[cidx], x, u, cost_block<nz>(gw0, cidx));
   if constexpr (GEN) {
     if (P.gl) Jk += goal_lin_cost<n, m>(gl0, cidx, x, u);  // (P.gl: wave-uniform; gl0 is only meaningful with it)
   }
@@ -242,7 +245,8 @@ __device__ __forceinline__ double knot_violation(const DevProblem& P, int k, con
 }
 
 // whole-trajectory pass over the NOMINAL trajectory: cost (with or without AL), max violation, optional dual update
-template <class M>
+// GW: the instance a handle with per-trajectory cost weights runs (DevProblem::gw set; picked by the launcher)
+template <class M, bool GW = false>
 __device__ __forceinline__ void trajectory_pass(const KArgs& a, int tile, int lane, bool with_al, bool do_dual_update, double* J_out,
                                                 double* cmax_out, int c = 0) {
   constexpr int n = M::n, m = M::m, nz = n + m;
@@ -280,6 +284,8 @@ __device__ __forceinline__ void trajectory_pass(const KArgs& a, int tile, int la
       }
     }
     if (cmax_out && P.n_cons > 0) { const double v = knot_violation<M>(P, k, x, u, cp0, cl0); if (!(v <= cmax)) cmax = v; }
+    if constexpr (GW) { if (J_out) J += knot_cost<M>(P, k, x, u, lam0, mu0, with_al, TILE_PTR(P.gl, P.n_costs * nz), cp0, cl0, dt0, TILE_PTR(P.gw, P.n_costs * nz)); }
+    else
     if (J_out) J += knot_cost<M>(P, k, x, u, lam0, mu0, with_al, TILE_PTR(P.gl, P.n_costs * nz), cp0, cl0, dt0);
   }
   if (J_out) *J_out = J;

@@ -267,6 +267,7 @@ struct TrackFacts {
   const to_cost_desc* costs; int n_costs; const int* cost_index /* [N] */;
   bool in_flight;
   int Nref_set, end_mode_set;
+  bool cost_weights = false;  // DevProblem::gw is set (to_set_cost_weights_batch): k_track_lower forms -Q x_ref from the DESCRIPTOR's Q
 };
 // the window itself: start[B] (NULL: 1 for all) against a reference of Nref knots
 inline int validate_tracking_starts(const char* who, int N, int B, int Nref, int end_mode, const int32_t* start) {
@@ -288,6 +289,9 @@ inline int validate_tracking_target(const char* who, const TrackFacts& f) {
   if (f.model_key >= 7)
     return fail(TO_ERR_UNSUPPORTED, std::string(who) + ": not available for the " + f.model_name +
                                         " (TO_MODEL_HYBRID_DOUBLE_INTEGRATOR, TO_MODEL_VECTOR and TO_MODEL_INFEASIBLE have no per-trajectory tracking reference)");
+  if (f.cost_weights)
+    return fail(TO_ERR_UNSUPPORTED, std::string(who) + ": the handle carries per-trajectory cost weights (to_set_cost_weights_batch); the reference is lowered "
+                                        "with the descriptors' Q and R (to_clear_cost_weights_batch first)");
   for (int k = 0; k < f.N; ++k)
     for (int l = k + 1; l < f.N; ++l)
       if (f.cost_index[k] == f.cost_index[l])
@@ -359,6 +363,106 @@ inline int lower_time_steps(int N, int B, int Bp, const double* dt, const double
         (*tiled)[(t * L + k) * 64 + l] = b < (size_t)B ? dt[k + (size_t)L * b] : shared[k];
       }
   return TO_OK;
+}
+
+// Per-trajectory cost weights (to_set_cost_weights_batch / to_get_... / to_clear_...): every refusal of the three entry points, decided from what
+// the host knows of the handle before any device call.  CostWeightFacts: those facts (model_key as in TrackFacts; NULL facts: a NULL handle).
+// The VALUES are held to what to_set_cost asks of a descriptor's Q and R and to being finite, nothing more: the reference only warns about
+// definiteness (src/cost_functions.jl:337-343), and a weight of zero or below is the caller's business here as it is in a descriptor.
+struct CostWeightFacts {
+  int model_key; const char* model_name;
+  int n, m, B;
+  const to_cost_desc* costs; int n_costs;
+  bool in_flight;
+  int Nref_set;  // knots of a stored tracking reference (0: none)
+};
+inline const char* cost_kind_name(int kind) {
+  return kind == TO_COST_DIAGONAL ? "DiagonalCost" : kind == TO_COST_QUADRATIC ? "QuadraticCost" : kind == TO_COST_DIAGONAL_QUAT ? "DiagonalQuatCost"
+         : kind == TO_COST_ERROR_QUADRATIC ? "ErrorQuadratic" : "unknown cost kind";
+}
+// the handle as a target (all three entry points; cost_id < 0 with any = true: the clear call, which names no cost)
+inline int validate_cost_weights_target(const char* who, const CostWeightFacts* f, int32_t cost_id, bool any = false) {
+  if (!f) return fail(TO_ERR_NULL, "null handle");
+  if (f->in_flight) return fail(TO_ERR_ARGUMENT, "an asynchronous solve is in flight on this handle (call to_solve_wait first)");
+  if (f->model_key >= 7)
+    return fail(TO_ERR_UNSUPPORTED, std::string(who) + ": per-trajectory cost weights are not available for the " + f->model_name +
+                                        " (TO_MODEL_HYBRID_DOUBLE_INTEGRATOR, TO_MODEL_VECTOR and TO_MODEL_INFEASIBLE share their weights)");
+  if (any) return TO_OK;
+  if (cost_id < 0 || cost_id >= f->n_costs) return fail(TO_ERR_ARGUMENT, "cost id out of range");
+  return TO_OK;
+}
+inline int validate_cost_weights_kind(const char* who, const CostWeightFacts& f, int32_t cost_id) {
+  const int kind = f.costs[cost_id].kind;
+  if (kind != TO_COST_DIAGONAL && kind != TO_COST_DIAGONAL_QUAT)
+    return fail(TO_ERR_UNSUPPORTED, std::string(who) + ": cost " + std::to_string(cost_id) + " is of kind " + cost_kind_name(kind) +
+                                        "; per-trajectory weights are the diagonal Q and R of DiagonalCost and DiagonalQuatCost only");
+  return TO_OK;
+}
+inline int validate_cost_weights(const CostWeightFacts* f, int32_t cost_id, const double* Q /* [n, B] or NULL */, const double* R /* [m, B] or NULL */) {
+  const char* who = "to_set_cost_weights_batch";
+  if (int r = validate_cost_weights_target(who, f, cost_id)) return r;
+  if (!Q && !R) return fail(TO_ERR_ARGUMENT, std::string(who) + ": Q and R are both NULL");
+  if (int r = validate_cost_weights_kind(who, *f, cost_id)) return r;
+  if (f->Nref_set > 0)
+    return fail(TO_ERR_UNSUPPORTED, std::string(who) + ": the handle holds a tracking reference (to_set_tracking_reference_batch), which is lowered with the "
+                                        "descriptors' Q and R (to_clear_tracking_reference_batch first)");
+  for (int b = 0; b < f->B; ++b) {
+    for (int i = 0; Q && i < f->n; ++i)
+      if (!std::isfinite(Q[i + (size_t)f->n * b]))
+        return fail(TO_ERR_ARGUMENT, std::string(who) + ": Q[" + std::to_string(i) + "] of trajectory " + std::to_string(b) + " is not finite");
+    for (int j = 0; R && j < f->m; ++j)
+      if (!std::isfinite(R[j + (size_t)f->m * b]))
+        return fail(TO_ERR_ARGUMENT, std::string(who) + ": R[" + std::to_string(j) + "] of trajectory " + std::to_string(b) + " is not finite");
+  }
+  return TO_OK;
+}
+inline int validate_cost_weights_get(const CostWeightFacts* f, int32_t cost_id, const double* Q, const double* R) {
+  const char* who = "to_get_cost_weights_batch";
+  if (int r = validate_cost_weights_target(who, f, cost_id)) return r;
+  if (!Q && !R) return fail(TO_ERR_ARGUMENT, std::string(who) + ": Q and R are both NULL");
+  return validate_cost_weights_kind(who, *f, cost_id);
+}
+// The host copy behind DevProblem::gw: values[L, B] with L = n_costs (n + m), row ci (n + m) + i of column b = Q_i (i < n) / R_{i-n} of cost ci
+// as trajectory b is evaluated with it.  cost_weights_fill: every cost's descriptor values (first use; cost_weights_restart: one cost's rows
+// again, behind to_set_cost); cost_weights_store: the setter's Q / R into one cost's rows; cost_weights_tile: the device layout — entry e of
+// trajectory b at tiled[((b >> 6) L + e) 64 + (b & 63)], Bp / 64 tiles and one spare; the lanes behind the batch carry the descriptors' values
+// (idle lanes compute along on valid data).  A dense cost's rows are never read; they hold the leading entries of its arrays.
+inline void cost_weights_restart(int n, int m, int B, const to_cost_desc* costs, int n_costs, int ci, std::vector<double>* values) {
+  const int nz = n + m;
+  const size_t L = (size_t)n_costs * nz;
+  for (int b = 0; b < B; ++b) {
+    double* v = values->data() + L * b + (size_t)ci * nz;
+    for (int i = 0; i < n; ++i) v[i] = costs[ci].Q[i];
+    for (int j = 0; j < m; ++j) v[n + j] = costs[ci].R[j];
+  }
+}
+inline void cost_weights_fill(int n, int m, int B, const to_cost_desc* costs, int n_costs, std::vector<double>* values) {
+  values->assign((size_t)n_costs * (n + m) * B, 0.0);
+  for (int ci = 0; ci < n_costs; ++ci) cost_weights_restart(n, m, B, costs, n_costs, ci, values);
+}
+inline void cost_weights_store(int n, int m, int B, int n_costs, int ci, const double* Q, const double* R, std::vector<double>* values) {
+  const int nz = n + m;
+  const size_t L = (size_t)n_costs * nz;
+  for (int b = 0; b < B; ++b) {
+    double* v = values->data() + L * b + (size_t)ci * nz;
+    for (int i = 0; Q && i < n; ++i) v[i] = Q[i + (size_t)n * b];
+    for (int j = 0; R && j < m; ++j) v[n + j] = R[j + (size_t)m * b];
+  }
+}
+inline size_t cost_weights_tiled_len(int n, int m, int n_costs, int Bp) { return ((size_t)Bp / 64 + 1) * (size_t)n_costs * (n + m) * 64; }
+inline void cost_weights_tile(int n, int m, int B, int Bp, const to_cost_desc* costs, int n_costs, const std::vector<double>& values, std::vector<double>* tiled) {
+  const int nz = n + m;
+  const size_t L = (size_t)n_costs * nz, tiles = (size_t)Bp / 64 + 1;
+  tiled->assign(cost_weights_tiled_len(n, m, n_costs, Bp), 0.0);
+  for (size_t t = 0; t < tiles; ++t)
+    for (size_t e = 0; e < L; ++e) {
+      const int ci = (int)(e / nz), i = (int)(e % nz);
+      const double shared = i < n ? costs[ci].Q[i] : costs[ci].R[i - n];
+      for (int l = 0; l < 64; ++l) {
+        const size_t b = t * 64 + l;
+        (*tiled)[(t * L + e) * 64 + l] = b < (size_t)B ? values[L * b + e] : shared;
+      }
+    }
 }
 
 // rot: attitude representation of the model's state (to_rotation), -1 for vector-space models

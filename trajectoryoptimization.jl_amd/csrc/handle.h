@@ -96,6 +96,8 @@ struct to_handle_s {
   double* d_cl = nullptr;   // per-trajectory constraint limits (DevProblem::cl), tiled, L = n_cl = summed p of the constraints, one spare tile; allocated on first use
   std::vector<int> cl_base;                 // [n_cons] first row of constraint i's block in d_cl
   std::vector<std::vector<double>> cl_host; // [n_cons] limits[q, B] as to_set_constraint_limits_batch was given them (empty: shared limits)
+  double* d_gw = nullptr;   // per-trajectory cost weights (DevProblem::gw), tiled, L = n_costs * (n + m), one spare tile; allocated on first use
+  std::vector<double> gw_host;  // [L, B] the diagonal Q / R every trajectory's costs are evaluated with (desc_lower.h cost_weights_fill; empty: DevProblem::gw is null)
   double* d_tmp = nullptr;  // [Bp] scratch for reductions / outputs
   double* d_tmp2 = nullptr;
   // multi-GPU: RCCL communicator of the batch shards (to_comm_*; librccl is dlopen'ed on first use)
@@ -259,6 +261,22 @@ template <class M, bool PM, class F>
 int with_time_steps(const to_handle* h, F&& body) {
   if constexpr (PM && TimeStepsModel<M>::value) {
     if (h->a.P.dtb != nullptr) return body(std::true_type{});
+  }
+  return body(std::false_type{});
+}
+
+// Per-trajectory cost weights (DevProblem::gw, to_set_cost_weights_batch): body(bool_constant<GW>) with GW = the handle carries them.  The kernels
+// that read a cost's diagonal outside the forward passes exist twice, and a handle without weights launches the instance it always did
+// (problem_dev.h cost_wq); the expansion kernels carry the same choice as bit 3 of their variant (ops.h with_variant).  The models the setter
+// refuses (desc_lower.h validate_cost_weights_target) have no second instance.
+template <class M> struct CostWeightsModel : std::true_type {};
+template <> struct CostWeightsModel<HybridDoubleIntegratorModel> : std::false_type {};
+template <> struct CostWeightsModel<ModelVectorModel> : std::false_type {};
+template <class Base> struct CostWeightsModel<InfeasibleModel<Base>> : std::false_type {};
+template <class M, class F>
+int with_weights(const to_handle* h, F&& body) {
+  if constexpr (CostWeightsModel<M>::value) {
+    if (h->a.P.gw != nullptr) return body(std::true_type{});
   }
   return body(std::false_type{});
 }

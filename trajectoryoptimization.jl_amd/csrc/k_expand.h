@@ -107,6 +107,9 @@ __device__ __forceinline__ void expand_knot(const KArgs& a, int gtile, int lane,
 #pragma unroll
     for (int i = 0; i < n; ++i) v[i] = (jc >= 0 && i == sc) ? 1.0 : v[i];
   }
+  // VAR bit 3 (the general variant of a handle with per-trajectory cost weights, ops.h with_variant): diagonal Q / R from DevProblem::gw
+  if constexpr ((VAR & 8) != 0) cost_grad_hvp<n, m, (VAR & 1) != 0>(P.costs[P.cost_index[k]], x, u, terminal, v, gr, y, cost_weights<nz>(P, tile, lane64, P.cost_index[k]));
+  else
   cost_grad_hvp<n, m, (VAR & 1) != 0>(P.costs[P.cost_index[k]], x, u, terminal, v, gr, y);
   if (P.gl) goal_lin_grad<n, m>(P.gl + ((size_t)tile * (size_t)(P.n_costs * nz)) * 64 + lane64, P.cost_index[k], terminal, gr);  // per-trajectory q, r
   if (P.opts.cost_dt_scaling && !terminal) {
@@ -467,6 +470,8 @@ __device__ __forceinline__ void expand_lane_knot(const KArgs& a, int tile, int l
     double v[nz], gr[nz], y[nz];
 #pragma unroll
     for (int i = 0; i < nz; ++i) v[i] = (i == (j < ne ? j : n + (j - ne))) ? 1.0 : 0.0;
+    if constexpr ((VAR & 8) != 0) cost_grad_hvp<n, m, (VAR & 1) != 0>(P.costs[P.cost_index[k]], x, u, terminal, v, gr, y, cost_weights<nz>(P, tile, lane, P.cost_index[k]));  // (VAR bit 3: as in expand_knot)
+    else
     cost_grad_hvp<n, m, (VAR & 1) != 0>(P.costs[P.cost_index[k]], x, u, terminal, v, gr, y);
     if (P.gl) goal_lin_grad<n, m>(P.gl + ((size_t)tile * (size_t)(P.n_costs * nz)) * 64 + lane, P.cost_index[k], terminal, gr);  // per-trajectory q, r
     if (P.opts.cost_dt_scaling && !terminal) {

@@ -112,6 +112,10 @@ __device__ __forceinline__ void forward_candidate(const KArgs& a, int tile, int 
   const double* gl0 = TILE_PTR(P.gl, P.n_costs * (n + m));
   const double* cp0 = TILE_PTR(P.cp, P.n_cp);  // per-trajectory constraint parameters (general variants)
   const double* cl0 = TILE_PTR(P.cl, P.n_cl);  // ... and limits
+  // per-trajectory cost weights (general variants): wave-uniform like has_gl.  This translation unit is compiled with -ffp-contract=on — fused
+  // operations are formed per source expression — so the side a handle without weights takes computes the bits it always did
+  const bool has_gw = GEN && P.gw != nullptr;
+  const double* gw0 = TILE_PTR(P.gw, P.n_costs * (n + m));
   const int ci0 = P.cost_index[0];
   const double* dt0 = dt_lane_of<(MODE & 64) != 0>(P, b);  // bit6: the trajectory's own time steps (DevProblem::dtb; with bit5, picked by the launcher)
   double h0 = 0.0;
@@ -190,7 +194,9 @@ __device__ __forceinline__ void forward_candidate(const KArgs& a, int tile, int 
     pUo += m * 64;
     gsum += gk;
     const double h = SIMPLE ? h0 : step_dt_of<(MODE & 64) != 0>(P, k, dt0);
-    double Jk = SIMPLE ? sc.eval(xb, ub) : cost_eval<n, m, GEN>(P.costs[P.cost_index[k]], xb, ub);
+    double Jk;
+    if (has_gw) { const int ck = P.cost_index[k]; Jk = cost_eval<n, m, GEN>(P.costs[ck], xb, ub, cost_block<n + m>(gw0, ck)); }  // (never a preloaded shared weight)
+    else Jk = SIMPLE ? sc.eval(xb, ub) : cost_eval<n, m, GEN>(P.costs[P.cost_index[k]], xb, ub);
     if constexpr (GEN) {  // per-trajectory q, r: in the general variants only (launch_forward picks one when DevProblem::gl is set), so that
       if (has_gl) Jk += goal_lin_cost<n, m>(gl0, SIMPLE ? ci0 : (int)P.cost_index[k], xb, ub);  // the default kernels keep their loops as they were
     }
@@ -223,7 +229,8 @@ __device__ __forceinline__ void forward_candidate(const KArgs& a, int tile, int 
     double u0[m];
 #pragma unroll
     for (int j = 0; j < m; ++j) u0[j] = 0.0;
-    J += knot_cost<M, GEN>(P, N - 1, xb, u0, lam0, mu0, true, gl0, cp0, cl0);
+    if (has_gw) J += knot_cost<M, GEN>(P, N - 1, xb, u0, lam0, mu0, true, gl0, cp0, cl0, nullptr, gw0);
+    else J += knot_cost<M, GEN>(P, N - 1, xb, u0, lam0, mu0, true, gl0, cp0, cl0);
   }
   if constexpr (KLDS) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // no DMA may still be in flight when the next pass refills the buffers
   J_out = J; g_out = gsum / (N - 1); ok_out = ok;
@@ -749,6 +756,10 @@ __device__ __forceinline__ void fwd2_account(const KArgs& a, int tile, int lane,
   const double* gl0 = TILE_PTR(P.gl, P.n_costs * (n + m));
   const double* cp0 = TILE_PTR(P.cp, P.n_cp);  // per-trajectory constraint parameters (general variants)
   const double* cl0 = TILE_PTR(P.cl, P.n_cl);  // ... and limits
+  // per-trajectory cost weights (general variants): wave-uniform like has_gl.  This translation unit is compiled with -ffp-contract=on — fused
+  // operations are formed per source expression — so the side a handle without weights takes computes the bits it always did
+  const bool has_gw = GEN && P.gw != nullptr;
+  const double* gw0 = TILE_PTR(P.gw, P.n_costs * (n + m));
   const int ci0 = P.cost_index[0];
   double h0 = 0.0;
   if constexpr (SIMPLE) {
@@ -800,7 +811,9 @@ __device__ __forceinline__ void fwd2_account(const KArgs& a, int tile, int lane,
     for (int j = 0; j < m; ++j) gk = fmax(gk, fabs(dk[j]) * rcp_fast(fabs(ub[j]) + 1.0));
     gsum += gk;
     const double h = SIMPLE ? h0 : P.dt[k];
-    double Jk = SIMPLE ? sc.eval(xb, ub) : cost_eval<n, m, GEN>(P.costs[P.cost_index[k]], xb, ub);
+    double Jk;
+    if (has_gw) { const int ck = P.cost_index[k]; Jk = cost_eval<n, m, GEN>(P.costs[ck], xb, ub, cost_block<n + m>(gw0, ck)); }  // (never a preloaded shared weight)
+    else Jk = SIMPLE ? sc.eval(xb, ub) : cost_eval<n, m, GEN>(P.costs[P.cost_index[k]], xb, ub);
     if constexpr (GEN) {  // per-trajectory q, r: in the general variants only (launch_forward picks one when DevProblem::gl is set), so that
       if (has_gl) Jk += goal_lin_cost<n, m>(gl0, SIMPLE ? ci0 : (int)P.cost_index[k], xb, ub);  // the default kernels keep their loops as they were
     }
@@ -839,7 +852,8 @@ __device__ __forceinline__ void fwd2_account(const KArgs& a, int tile, int lane,
     double u0[m];
 #pragma unroll
     for (int j = 0; j < m; ++j) u0[j] = 0.0;
-    J += knot_cost<M, GEN>(P, N - 1, xb, u0, lam0, mu0, true, gl0, cp0, cl0);
+    if (has_gw) J += knot_cost<M, GEN>(P, N - 1, xb, u0, lam0, mu0, true, gl0, cp0, cl0, nullptr, gw0);
+    else J += knot_cost<M, GEN>(P, N - 1, xb, u0, lam0, mu0, true, gl0, cp0, cl0);
   }
   J_out = J; g_out = gsum / (N - 1); ok_out = ok;
 }

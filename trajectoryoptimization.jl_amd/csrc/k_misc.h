@@ -48,7 +48,8 @@ __global__ void __launch_bounds__(64) k_rollout(KArgs a) {  // src/problem.jl:33
 
 // ------------------------------------------------------------------------------------------------ cost
 // out[b] = total (AL) cost, or — when Jk is given — per-knot objective values in a tiled array with L = N
-template <class M>
+// GW (here and in k_outer_update, k_cost_derivs): the instance of a handle with per-trajectory cost weights (DevProblem::gw set, ops.h with_weights)
+template <class M, bool GW = false>
 __global__ void __launch_bounds__(64) k_cost(KArgs a, int with_al, double* out, double* Jk) {
   constexpr int n = M::n, m = M::m;
   TILE_LANE();
@@ -67,12 +68,14 @@ __global__ void __launch_bounds__(64) k_cost(KArgs a, int with_al, double* out, 
       for (int i = 0; i < n; ++i) x[i] = EL(X, k * n + i);
 #pragma unroll
       for (int i = 0; i < m; ++i) u[i] = (k < N - 1) ? EL(U, k * m + i) : 0.0;
+      if constexpr (GW) EL(o, k) = knot_cost<M>(P, k, x, u, nullptr, nullptr, false, TILE_PTR(P.gl, P.n_costs * (n + m)), nullptr, nullptr, dt0, TILE_PTR(P.gw, P.n_costs * (n + m)));
+      else
       EL(o, k) = knot_cost<M>(P, k, x, u, nullptr, nullptr, false, TILE_PTR(P.gl, P.n_costs * (n + m)), nullptr, nullptr, dt0);
     }
     return;
   }
   double J;
-  trajectory_pass<M>(a, tile, lane, with_al != 0, false, &J, nullptr);
+  trajectory_pass<M, GW>(a, tile, lane, with_al != 0, false, &J, nullptr);
   out[b] = J;
 }
 
@@ -160,7 +163,7 @@ __global__ void __launch_bounds__(64) k_outer_decide(KArgs a) {
   for (int ci = 0; ci < P.n_cons; ++ci) EL(mn0, ci) = fmin(EL(mu0, ci) * o.penalty_scaling, o.penalty_max);
 }
 
-template <class M>
+template <class M, bool GW = false>
 __global__ void __launch_bounds__(64) k_outer_update(KArgs a) {
   constexpr int n = M::n, m = M::m, nz = n + m;
   OUTER_LANE(2);
@@ -188,6 +191,10 @@ __global__ void __launch_bounds__(64) k_outer_update(KArgs a) {
     con_shift<nz>(P, K, TILE_PTR(P.cp, P.n_cp), zc);
     con_dual_update<nz>(K, zc, lam, (size_t)64, EL(mu0, ci), P.opts.dual_max, TILE_PTR(P.cl, P.n_cl));
   }
+  if constexpr (GW)
+    EL(TILE_PTR(a.knotbuf, N), k) = knot_cost<M>(P, k, x, u, lam0, mn0, true, TILE_PTR(P.gl, P.n_costs * nz), TILE_PTR(P.cp, P.n_cp), TILE_PTR(P.cl, P.n_cl), dt_lane(P, b),
+                                                 TILE_PTR(P.gw, P.n_costs * nz));
+  else
   EL(TILE_PTR(a.knotbuf, N), k) = knot_cost<M>(P, k, x, u, lam0, mn0, true, TILE_PTR(P.gl, P.n_costs * nz), TILE_PTR(P.cp, P.n_cp), TILE_PTR(P.cl, P.n_cl), dt_lane(P, b));
 }
 
@@ -218,7 +225,7 @@ __global__ void __launch_bounds__(64) k_outer_finish(KArgs a) {
 // ------------------------------------------------------------------------------------------------ per-knot API kernels
 // RD.gradient!/RD.hessian! of the objective on the full state (no AL, no error-state projection):
 // grad[(n+m), N, B], hess[(n+m),(n+m),N,B] column-major host layout, written directly.
-template <class M>
+template <class M, bool GW = false>
 __global__ void __launch_bounds__(64) k_cost_derivs(KArgs a, double* grad, double* hess) {
   constexpr int n = M::n, m = M::m, nz = n + m;
   TILE_LANE();
@@ -239,6 +246,8 @@ __global__ void __launch_bounds__(64) k_cost_derivs(KArgs a, double* grad, doubl
     double v[nz], g[nz], y[nz];
 #pragma unroll
     for (int i = 0; i < nz; ++i) v[i] = (i == j) ? 1.0 : 0.0;
+    if constexpr (GW) cost_grad_hvp<n, m>(P.costs[P.cost_index[k]], x, u, terminal, v, g, y, cost_weights<nz>(P, tile, lane, P.cost_index[k]));
+    else
     cost_grad_hvp<n, m>(P.costs[P.cost_index[k]], x, u, terminal, v, g, y);
     if (P.gl) goal_lin_grad<n, m>(TILE_PTR(P.gl, P.n_costs * nz), P.cost_index[k], terminal, g);
     const double sc = (P.opts.cost_dt_scaling && !terminal) ? step_dt(P, k, dt_lane(P, b)) : 1.0;

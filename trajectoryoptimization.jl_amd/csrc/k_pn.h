@@ -345,8 +345,9 @@ PN_FN double pn_eval(const PnArgs& q, double* w, const PnLds& L, const double* x
 
 // inverse metric of knot k, entry j of nc: 1 / (max(diag of the error-state OBJECTIVE Hessian, 0) + rho_primal)
 // (DT: dt0 = the polished trajectory's own time steps, DevProblem::dtb; problem_dev.h step_dt_of)
-template <class M, bool DT = false>
-PN_FN double pn_metric_dir(const DevProblem& P, int k, const double* z, bool terminal, int j, const double* dt0 = nullptr) {
+// (GW: b = the polished trajectory, whose own diagonal weights the Hessian is built from, DevProblem::gw; problem_dev.h cost_wq)
+template <class M, bool DT = false, bool GW = false>
+PN_FN double pn_metric_dir(const DevProblem& P, int k, const double* z, bool terminal, int j, const double* dt0 = nullptr, [[maybe_unused]] int b = 0) {
   constexpr int n = M::n, m = M::m, ne = M::ne, nz = n + m;
   CostC& C = P.costs[P.cost_index[k]];
   const double sc = (P.opts.cost_dt_scaling && !terminal) ? step_dt_of<DT>(P, k, dt0) : 1.0;
@@ -354,6 +355,8 @@ PN_FN double pn_metric_dir(const DevProblem& P, int k, const double* z, bool ter
   errstate_col<M>(z, j < ne ? j : 0, v);
   for (int i = 0; i < n; ++i) v[i] = (j < ne) ? v[i] : 0.0;
   for (int i = n; i < nz; ++i) v[i] = (i == n + j - ne) ? 1.0 : 0.0;
+  if constexpr (GW) cost_grad_hvp<n, m, true>(C, z, z + n, terminal, v, g, y, cost_weights<nz>(P, b >> 6, b & 63, P.cost_index[k]));
+  else
   cost_grad_hvp<n, m, true>(C, z, z + n, terminal, v, g, y);
   double dj = 0.0;
   for (int i = 0; i < nz; ++i) dj += v[i] * y[i];
@@ -980,14 +983,15 @@ __global__ void __launch_bounds__(64) k_pn_lin_col(PnArgs q) {
 // branches (with a lane per knot the dense-cost branches of lanes on differently-costed knots diverged around the register-hungry
 // ErrorQuadratic duals, exactly where hipcc's spill placement is unsafe: DESIGN.md §6).  Lane j < nc owns metric entry j; the
 // active rows are built by every lane alike (same values to the same addresses).
-template <class M, bool DT = false>
+template <class M, bool DT = false, bool GW = false>
 __global__ void __launch_bounds__(64) k_pn_lin_knot(PnArgs q) {
   constexpr int nc = M::ne + M::m;
   double* w = q.ws + (size_t)blockIdx.x * (size_t)q.koff[q.a.P.N];
   if (w[PN_H_STATE] != (double)PN_ACTIVE) return;
   const int k = blockIdx.y, j = min((int)threadIdx.x, nc - 1);
   const PnRec<M> R = pn_rec<M>(q, w, k);
-  R.W[j] = pn_metric_dir<M, DT>(q.a.P, k, R.Z, k == q.a.P.N - 1, j, dt_lane_of<DT>(q.a.P, DT ? q.list[q.base + blockIdx.x] : 0));
+  R.W[j] = pn_metric_dir<M, DT, GW>(q.a.P, k, R.Z, k == q.a.P.N - 1, j, dt_lane_of<DT>(q.a.P, DT ? q.list[q.base + blockIdx.x] : 0),
+                                    GW ? q.list[q.base + blockIdx.x] : 0);
   pn_lin_rows<M>(q, w, k);
 }
 

@@ -53,16 +53,21 @@ struct PolicyKnot {
 };
 
 // objective value of one stage knot; DT (a handle with per-trajectory time steps, DevProblem::dtb): scaled by the trajectory's own step
-template <class M, bool DT>
+// GW (a handle with per-trajectory cost weights, DevProblem::gw): the weights of sample c's trajectory b; gw0 = its pointer to entry 0
+template <class M, bool DT, bool GW = false>
 __device__ __forceinline__ double policy_knot_cost(const DevProblem& P, int k, const double* x, const double* u, const double* gl0, const double* cp0,
-                                                   [[maybe_unused]] const double* dt0) {
+                                                   [[maybe_unused]] const double* dt0, [[maybe_unused]] const double* gw0 = nullptr) {
+  if constexpr (GW) {
+    if constexpr (DT) return knot_cost<M, true>(P, k, x, u, nullptr, nullptr, false, gl0, cp0, nullptr, dt0, gw0);
+    else return knot_cost<M, true>(P, k, x, u, nullptr, nullptr, false, gl0, cp0, nullptr, nullptr, gw0);
+  } else
   if constexpr (DT) return knot_cost<M, true>(P, k, x, u, nullptr, nullptr, false, gl0, cp0, nullptr, dt0);
   else return knot_cost<M, true>(P, k, x, u, nullptr, nullptr, false, gl0, cp0);
 }
 
 // DT: sample c steps by the time steps of ITS trajectory b (DevProblem::dtb).  A handle with per-trajectory steps always runs a one-plant-per-
 // sample instance (NZ bit 2), and its launcher picks DT = true (ops.h; problem_dev.h step_dt_of)
-template <class M, bool UNIFORM, int FI, int NZ = 0, bool DT = false>
+template <class M, bool UNIFORM, int FI, int NZ = 0, bool DT = false, bool GW = false>
 __global__ void __launch_bounds__(64) k_policy_rollout(KArgs a, PolicyArgs pa) {
   constexpr bool NOISE_W = (NZ & 1) != 0, NOISE_V = (NZ & 2) != 0, LANE_PLANT = (NZ & 4) != 0;
   constexpr int n = M::n, m = M::m, ne = M::ne, RSK = Gains<M>::RSK;
@@ -92,6 +97,7 @@ __global__ void __launch_bounds__(64) k_policy_rollout(KArgs a, PolicyArgs pa) {
   const double* cp0 = TILE_PTR(P.cp, P.n_cp);
   const double* cl0 = TILE_PTR(P.cl, P.n_cl);
   const double* dt0 = dt_lane_of<DT>(P, b);
+  [[maybe_unused]] const double* gw0 = GW ? TILE_PTR(P.gw, P.n_costs * (n + m)) : nullptr;  // (by the trajectory b, like gl0)
   double mp[16];  // the PLANT's parameters; the law's x̄, ū, K, d are the planning model's
   if constexpr (LANE_PLANT) {
     const double* pp = pa.plants + c * 16;
@@ -165,7 +171,7 @@ __global__ void __launch_bounds__(64) k_policy_rollout(KArgs a, PolicyArgs pa) {
       if (store) EL(pUo, j) = uj;
     }
     pUo += m * 64;
-    J += policy_knot_cost<M, DT>(P, k, xb, ub, gl0, cp0, dt0);
+    J += policy_knot_cost<M, DT, GW>(P, k, xb, ub, gl0, cp0, dt0, gw0);
     if (has_cons) { const double v = knot_violation<M>(P, k, xb, ub, cp0, cl0); if (!(v <= cm)) cm = v; }
     model_step<M, double, FI>(mp, integrator, k, xb, ub, step_dt_of<DT>(P, k, dt0), xn);
     if constexpr (NOISE_W) {  // x_{k+1} = state_add(f(x_k, u_k), w_k): no dt scaling; the limit test below sees the noisy state
@@ -202,6 +208,8 @@ __global__ void __launch_bounds__(64) k_policy_rollout(KArgs a, PolicyArgs pa) {
     for (int i = 0; i < ne; ++i) { const double v = fabs(dx[i]); if (!(v <= dxm)) dxm = v; }
 #pragma unroll
     for (int j = 0; j < m; ++j) u0[j] = 0.0;
+    if constexpr (GW) J += knot_cost<M, true>(P, N - 1, xb, u0, nullptr, nullptr, false, gl0, cp0, nullptr, nullptr, gw0);
+    else
     J += knot_cost<M, true>(P, N - 1, xb, u0, nullptr, nullptr, false, gl0, cp0);
     if (has_cons) { const double v = knot_violation<M>(P, N - 1, xb, u0, cp0, cl0); if (!(v <= cm)) cm = v; }
   }

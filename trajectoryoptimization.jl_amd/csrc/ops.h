@@ -40,13 +40,17 @@ int with_integrator(const to_handle* h, F&& body) {
   return body(std::integral_constant<int, -1>{});
 }
 // THE expansion-variant ladder: body(v) with v = std::integral_constant<int, VAR> of the handle's problem — 0 = diagonal-kind costs, no
-// constraints; 2 = + selector / SOC-selector constraints; 7 = everything.  SPECIAL = false: the general variant only (the flagged instances
-// of one plant per trajectory).  A body that has no instance of a variant guards it with `if constexpr`.
-template <bool SPECIAL = true, class F>
+// constraints; 2 = + selector / SOC-selector constraints; 7 = everything; 15 = everything, with the diagonal weights of the costs read per
+// trajectory (DevProblem::gw set: bit 3, k_expand.h; WEIGHTS = false, the models the setter refuses: no such instance).  SPECIAL = false: the
+// general variants only (the flagged instances of one plant per trajectory).  A body that has no instance of a variant guards it with `if constexpr`.
+template <bool SPECIAL = true, bool WEIGHTS = true, class F>
 int with_variant(const to_handle* h, F&& body) {
   if constexpr (SPECIAL) {
     if (h->a.P.expand_variant == 0) return body(std::integral_constant<int, 0>{});
     if (h->a.P.expand_variant == 2) return body(std::integral_constant<int, 2>{});
+  }
+  if constexpr (WEIGHTS) {
+    if (h->a.P.gw != nullptr) return body(std::integral_constant<int, 15>{});
   }
   return body(std::integral_constant<int, 7>{});
 }
@@ -60,7 +64,7 @@ int op_rollout(to_handle* h) {
 }
 template <class M>
 int op_cost(to_handle* h, int with_al, double* out, double* Jk) {
-  return launch(k_cost<M>, grid_b(h), dim3(BLOCK), 0, h->stream, h->a, with_al, out, Jk);
+  return with_weights<M>(h, [&](auto gw) { return launch(k_cost<M, decltype(gw)::value>, grid_b(h), dim3(BLOCK), 0, h->stream, h->a, with_al, out, Jk); });
 }
 template <class M>
 int op_violation(to_handle* h, double* out) {
@@ -76,12 +80,12 @@ int op_outer(to_handle* h) {
   const int N = h->a.P.N;
   enqueue(k_outer_violation<M>, grid_b(h, N), dim3(BLOCK), 0, h->stream, h->a);
   enqueue(k_outer_decide<M>, grid_b(h), dim3(BLOCK), 0, h->stream, h->a);
-  enqueue(k_outer_update<M>, grid_b(h, N), dim3(BLOCK), 0, h->stream, h->a);
+  with_weights<M>(h, [&](auto gw) { enqueue(k_outer_update<M, decltype(gw)::value>, grid_b(h, N), dim3(BLOCK), 0, h->stream, h->a); return TO_OK; });
   return launch(k_outer_finish<M>, grid_b(h), dim3(BLOCK), 0, h->stream, h->a);
 }
 template <class M>
 int op_cost_derivs(to_handle* h, double* dg, double* dh) {
-  return launch(k_cost_derivs<M>, grid_b(h, h->a.P.N), dim3(BLOCK), 0, h->stream, h->a, dg, dh);
+  return with_weights<M>(h, [&](auto gw) { return launch(k_cost_derivs<M, decltype(gw)::value>, grid_b(h, h->a.P.N), dim3(BLOCK), 0, h->stream, h->a, dg, dh); });
 }
 template <class M, bool PM = false>
 int op_discrete_jacobian(to_handle* h, double* F) {
@@ -113,17 +117,17 @@ int op_expand(to_handle* h) {
   // lane layout: one lane per (trajectory, knot), all columns at once (k_expand_lane; instantiated in the lane translation units, ops_lane.h)
   if (lay == 3 && h->plan.expand_lane && h->ops->expand_lane_k[0]) return h->ops->expand_lane_k[0](h);
   return with_integrator<M>(h, [&](auto fi) {
-    return with_variant(h, [&](auto v) {
+    return with_variant<true, CostWeightsModel<M>::value>(h, [&](auto v) {
       constexpr int FI = decltype(fi)::value, V = decltype(v)::value;
       constexpr int kc = expand_kc<M, V == 0 ? 0 : 2>();
       const dim3 grid((P.B + h->G - 1) / h->G, (P.N + kc - 1) / kc);
-      if constexpr (M::mfma_backward && ExpandPack<M>::ok && V != 7) {  // compact cost block of the quaternion rigid body: the packed expansion (k_expand.h)
+      if constexpr (M::mfma_backward && ExpandPack<M>::ok && (V & 4) == 0) {  // compact cost block of the quaternion rigid body: the packed expansion (k_expand.h)
         if (lay == 2 && h->plan.expand_pack)
           return launch(k_expand<M, FI, V, 2, true>, dim3((P.B + EXPAND_PACK_G - 1) / EXPAND_PACK_G, (P.N + kc - 1) / kc), dim3(BLOCK), 0, h->stream, h->a);
       }
       if constexpr (M::mfma_backward) {
         if (lay == 1) return launch(k_expand<M, FI, V, 1>, grid, dim3(BLOCK), 0, h->stream, h->a);
-        if constexpr (V != 7) {
+        if constexpr ((V & 4) == 0) {
           if (lay == 2) return launch(k_expand<M, FI, V, 2>, grid, dim3(BLOCK), 0, h->stream, h->a);
         }
       }
@@ -146,16 +150,18 @@ int op_expand_pm(to_handle* h) {
   const dim3 grid((P.B + h->G - 1) / h->G, (P.N + kc - 1) / kc);
   if (h->a.bwd_lane || h->a.h_compact) return fail(TO_ERR_UNSUPPORTED, "per-trajectory model parameters: expansion layout without a flagged instance");
   return with_integrator<M>(h, [&](auto fi) {
-    return with_time_steps<M, true>(h, [&](auto dt) {
-      constexpr int FI = decltype(fi)::value;
-      constexpr bool DT = decltype(dt)::value;
-      if constexpr (M::mfma_backward) {
-        if (h->a.bwd_mfma) return launch(k_expand<M, FI, 7, 1, false, true, DT>, grid, dim3(BLOCK), 0, h->stream, h->a);
-      }
-      if constexpr (!M::mfma_backward || M::coop_backward) {
-        if (!h->a.bwd_mfma) return launch(k_expand<M, FI, 7, 0, false, true, DT>, grid, dim3(BLOCK), 0, h->stream, h->a);
-      }
-      return fail(TO_ERR_UNSUPPORTED, "per-trajectory model parameters: expansion not compiled for this model and layout");
+    return with_variant<false, CostWeightsModel<M>::value>(h, [&](auto v) {  // (7, or 15 with per-trajectory cost weights)
+      return with_time_steps<M, true>(h, [&](auto dt) {
+        constexpr int FI = decltype(fi)::value, V = decltype(v)::value;
+        constexpr bool DT = decltype(dt)::value;
+        if constexpr (M::mfma_backward) {
+          if (h->a.bwd_mfma) return launch(k_expand<M, FI, V, 1, false, true, DT>, grid, dim3(BLOCK), 0, h->stream, h->a);
+        }
+        if constexpr (!M::mfma_backward || M::coop_backward) {
+          if (!h->a.bwd_mfma) return launch(k_expand<M, FI, V, 0, false, true, DT>, grid, dim3(BLOCK), 0, h->stream, h->a);
+        }
+        return fail(TO_ERR_UNSUPPORTED, "per-trajectory model parameters: expansion not compiled for this model and layout");
+      });
     });
   });
 }
@@ -191,7 +197,7 @@ int op_expand_backward_coop(to_handle* h) {
     return with_integrator<M>(h, [&](auto fi) {
       return with_variant(h, [&](auto v) {
         constexpr int FI = decltype(fi)::value, V = decltype(v)::value;
-        if constexpr (V != 7) {
+        if constexpr ((V & 4) == 0) {
           if (h->a.coop_merge != 0) return launch(k_expand_backward_coop<M, FI, V, true>, grid, dim3(128), 0, h->stream, h->a);
           return launch(k_expand_backward_coop<M, FI, V, false>, grid, dim3(128), 0, h->stream, h->a);
         }
@@ -248,10 +254,12 @@ int op_policy_rollout(to_handle* h, const PolicyArgs& pa, int waves) {
   const size_t lds = M::lds_gains ? sizeof(double) * 2 * gains_lds_doubles<M>(uniform ? 1 : pa.TPW) : 0;  // two gains buffers
   return with_integrator<M>(h, [&](auto fi) {
     return with_time_steps<M, (NZ & 4) != 0>(h, [&](auto dt) {  // (a handle with per-trajectory time steps runs a one-plant-per-sample instance)
-      constexpr int FI = decltype(fi)::value;
-      constexpr bool DT = decltype(dt)::value;
-      if (uniform) return launch(k_policy_rollout<M, true, FI, NZ, DT>, dim3(waves), dim3(BLOCK), lds, h->stream, h->a, pa);
-      return launch(k_policy_rollout<M, false, FI, NZ, DT>, dim3(waves), dim3(BLOCK), lds, h->stream, h->a, pa);
+      return with_weights<M>(h, [&](auto gw) {  // (... and one with per-trajectory cost weights the instance that reads them for J)
+        constexpr int FI = decltype(fi)::value;
+        constexpr bool DT = decltype(dt)::value, GW = decltype(gw)::value;
+        if (uniform) return launch(k_policy_rollout<M, true, FI, NZ, DT, GW>, dim3(waves), dim3(BLOCK), lds, h->stream, h->a, pa);
+        return launch(k_policy_rollout<M, false, FI, NZ, DT, GW>, dim3(waves), dim3(BLOCK), lds, h->stream, h->a, pa);
+      });
     });
   });
 }

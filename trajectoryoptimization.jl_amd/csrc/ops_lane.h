@@ -14,7 +14,7 @@ int op_expand_lane(to_handle* h) {
   if constexpr (M::lane_backward && !M::lie) {
     const dim3 lgrid(h->a.P.Bp / BLOCK, h->a.P.N);
     return with_integrator<M>(h, [&](auto fi) {
-      return with_variant<!PM>(h, [&](auto v) {
+      return with_variant<!PM, CostWeightsModel<M>::value>(h, [&](auto v) {
         return with_time_steps<M, PM>(h, [&](auto dt) {
           return launch(k_expand_lane<M, decltype(fi)::value, decltype(v)::value, PM, decltype(dt)::value>, lgrid, dim3(BLOCK), 0, h->stream, h->a);
         });
@@ -30,7 +30,7 @@ int op_expand_backward(to_handle* h) {
   if constexpr (M::lane_backward && !M::lie) {
     const dim3 grid(h->a.P.Bp / BLOCK);
     return with_integrator<M>(h, [&](auto fi) {
-      return with_variant(h, [&](auto v) { return launch(k_expand_backward_lane<M, decltype(fi)::value, decltype(v)::value>, grid, dim3(BLOCK), 0, h->stream, h->a); });
+      return with_variant<true, CostWeightsModel<M>::value>(h, [&](auto v) { return launch(k_expand_backward_lane<M, decltype(fi)::value, decltype(v)::value>, grid, dim3(BLOCK), 0, h->stream, h->a); });
     });
   }
   return fail(TO_ERR_UNSUPPORTED, "fused lane expansion + backward pass not compiled for this model");

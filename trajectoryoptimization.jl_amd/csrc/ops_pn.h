@@ -25,7 +25,7 @@ int op_pn_launch(to_handle* h, int slot0, int count, hipStream_t stream, const t
     for (int round = 0; round <= opts->n_steps; ++round) {  // (n_steps >= 0: desc_lower.h) n_steps + 2 rounds, the last one its begin only
       enqueue(k_pn_begin<M, PM, DT>, dim3(count), dim3(64), lds, stream, q, round);
       enqueue(k_pn_lin_col<M, PM, DT>, dim3(count, col_blocks), dim3(64), 0, stream, q);
-      enqueue(k_pn_lin_knot<M, DT>, dim3(count, knot_blocks), dim3(64), 0, stream, q);
+      with_weights<M>(h, [&](auto gw) { enqueue(k_pn_lin_knot<M, DT, decltype(gw)::value>, dim3(count, knot_blocks), dim3(64), 0, stream, q); return TO_OK; });
       enqueue(k_pn_project<M, PM, DT>, dim3(count), dim3(64), lds, stream, q);
     }
     return launch(k_pn_begin<M, PM, DT>, dim3(count), dim3(64), lds, stream, q, opts->n_steps + 1);

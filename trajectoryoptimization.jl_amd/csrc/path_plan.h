@@ -229,10 +229,11 @@ inline StepPlan plan_step(const PathPlan& p, const PathTraits& t, int h_diag, in
 // it.  So the mode is decided once per solve: on only when EVERY step plans the scan kernel and the two-wave forward pass whatever active
 // count the host has seen (last_active <= B), on an iLQR solve without the k_compact list.
 //   forward2_compiled: the forward variant of this solve has a two-wave instance (launch_forward falls back to k_forward otherwise);
-//   linear_terms: DevProblem::gl is set (cp / cl / plants rule the scan out through expand_variant); enabled: the TRAJOPT_FWD_LIST switch.
+//   linear_terms: DevProblem::gl is set (cp / cl / plants rule the scan out through expand_variant); enabled: the TRAJOPT_FWD_LIST switch;
+//   cost_weights: DevProblem::gw is set (its expand_variant has bit 2 forced as well; stated here so that the mode does not hang on that alone).
 inline bool solve_forward_list(const PathPlan& p, const PathTraits& t, int h_diag, int expand_variant, int compact_armed, int al_mode, int B, int Bp,
-                               bool plants, bool linear_terms, bool forward2_compiled, bool enabled, int max_bp) {
-  if (!enabled || al_mode || compact_armed || plants || linear_terms || !forward2_compiled || !t.write_through || Bp > max_bp) return false;
+                               bool plants, bool linear_terms, bool forward2_compiled, bool enabled, int max_bp, bool cost_weights = false) {
+  if (!enabled || al_mode || compact_armed || plants || linear_terms || cost_weights || !forward2_compiled || !t.write_through || Bp > max_bp) return false;
   const StepPlan full = plan_step(p, t, h_diag, expand_variant, compact_armed, B, B, plants);  // the plan is monotone in last_active: the full batch is its worst case
   if (full.kind != STEP_SCAN || !full.store_x || full.two_launch) return false;
   return full.two_wave || p.fwd2 == 1;
@@ -259,19 +260,25 @@ inline void path_report(const PathPlan& p, const PathTraits& t, int h_diag, int 
 // Per-trajectory TIME STEPS (time_steps: DevProblem::dtb set, to_set_time_steps_batch) ride on the flagged instances that load one plant per
 // trajectory — only they read the step per trajectory — so such a handle IS a `plants` handle to every predicate above (routed_as_plants),
 // whether or not the caller also gave each trajectory its own plant.
+// Per-trajectory COST WEIGHTS (cost_weights: DevProblem::gw set, to_set_cost_weights_batch) route a handle exactly as con_limits does — bit 2
+// forced, forward `mode | 8` — and, beyond that, keep the forward pass off the variants that preload ONE stage cost for the whole wave
+// (forward_simple): a trajectory's weights are its own.
 struct TableFlags {
   bool dense_costs = false, cons = false, non_selector = false;  // from the descriptors
   bool con_params = false, con_limits = false, plants = false;   // a constraint flagged for cp / for cl; DevProblem::pm set
   bool time_steps = false;                                       // DevProblem::dtb set
+  bool cost_weights = false;                                     // DevProblem::gw set
 };
 inline bool routed_as_plants(bool plants /* pm */, bool time_steps /* dtb */) { return plants || time_steps; }
 inline bool routed_as_plants(const TableFlags& f) { return routed_as_plants(f.plants, f.time_steps); }
 inline int expand_variant_of(const TableFlags& f) {
-  return (f.dense_costs ? 1 : 0) | (f.cons ? 2 : 0) | ((f.non_selector || f.con_params || f.con_limits || routed_as_plants(f)) ? 4 : 0);
+  return (f.dense_costs ? 1 : 0) | (f.cons ? 2 : 0) | ((f.non_selector || f.con_params || f.con_limits || f.cost_weights || routed_as_plants(f)) ? 4 : 0);
 }
-inline bool forward_general(int expand_variant, bool cost_terms /* gl */, bool con_params /* cp */, bool con_limits /* cl */) {
-  return (expand_variant & 5) != 0 || cost_terms || con_params || con_limits;
+inline bool forward_general(int expand_variant, bool cost_terms /* gl */, bool con_params /* cp */, bool con_limits /* cl */, bool cost_weights /* gw */ = false) {
+  return (expand_variant & 5) != 0 || cost_terms || con_params || con_limits || cost_weights;
 }
+// forward_mode's `simple_stage`: DevProblem::simple_stage, except with per-trajectory cost weights (no preloaded shared stage cost)
+inline bool forward_simple(bool simple_stage, bool cost_weights /* gw */ = false) { return simple_stage && !cost_weights; }
 // Forward-pass kernel variant (k_forward.h MODE bits): bit0 simple stage cost, bit1 constraints, bit2 compile-time RK4 (models that
 // pin it), bit3 dense costs / generic constraints / per-trajectory terms, bit4 unit-SOC; `mask` holds the compiled ones.  -1: none fits.
 inline int forward_mode(bool simple_stage, bool has_cons, bool rk4, bool general, bool unit_soc, uint32_t mask) {

@@ -79,6 +79,13 @@ struct DevProblem {
   // trajectory steps by dt.  While it is set pm is set too (the shared plant repeated when the caller gave none): the time step rides on the
   // flagged (PM) kernel instances, and on a wave-uniform branch in the cost kernels that have no such instance.
   const double* dtb;
+  // Per-trajectory cost weights (to_set_cost_weights_batch: one diagonal Q / R per trajectory): tiled like gl, L = n_costs * (n + m); entry
+  // ci*(n+m) + i of trajectory b sits at gw[((b >> 6) * L + ci*(n+m) + i) * 64 + (b & 63)] and holds the VALUE of cost ci's Q_i (i < n) /
+  // R_{i-n} — not a difference: trajectory b evaluates the expression a single-trajectory problem built with those weights evaluates.  Filled with
+  // every cost's descriptor values on first use; while it is set every diagonal-kind site reads it, whichever cost the setter named.  NULL (the
+  // default): every trajectory shares the descriptors.  Read by the GW instances of the general kernel variants only (cost_weights below,
+  // DESIGN.md §1e).
+  const double* gw;
 };
 
 // The 16 model parameters of trajectory b into registers (the flagged kernel instances, once, ahead of their knot loops): indexed by the
@@ -265,10 +272,30 @@ __device__ __forceinline__ void errquad_grad(CostC& C, const T* x, T* g /*n*/) {
   }
 }
 
+// ------------------------------------------------------------------------------------------------ per-trajectory cost weights
+// Diagonal Q_i / R_j of cost C as this lane's trajectory sees them.  w: the lane's pointer to entry 0 of the cost's block in DevProblem::gw
+// (cost_weights) — indexed by the TRAJECTORY, like load_plant; the loads have wave-uniform offsets from that per-lane base — or nothing: the
+// callers that pass no pointer (every kernel instance a handle without weights runs) compile to the descriptor read they always had.  Which
+// of the two a kernel does is a COMPILE-TIME property of its instance outside the forward passes (the GW template arguments; the expansion
+// carries it as bit 3 of VAR): a run-time branch inside a knot loop splits basic blocks, hipcc's default contraction then pairs other
+// products with other sums, and a handle without weights must keep its bits (tests/test_gpu_cost_weights_unflagged.py).  The forward
+// translation units are compiled with -ffp-contract=on, which fuses per source expression whatever the blocks look like: there the general
+// variants pick between the two calls on DevProblem::gw, a kernel argument (k_forward.h).
+__device__ __forceinline__ double cost_wq(CostC& C, int i, std::nullptr_t) { return C.Q[i]; }
+__device__ __forceinline__ double cost_wq(CostC&, int i, const double* w) { return w[(size_t)i * 64]; }
+template <int n> __device__ __forceinline__ double cost_wr(CostC& C, int j, std::nullptr_t) { return C.R[j]; }
+template <int n> __device__ __forceinline__ double cost_wr(CostC&, int j, const double* w) { return w[(size_t)(n + j) * 64]; }
+// the lane's pointer to the block of cost ci (tile, lane: of the trajectory; nz = n + m)
+template <int nz>
+__device__ __forceinline__ const double* cost_weights(const DevProblem& P, int tile, int lane, int ci) {
+  return P.gw + ((size_t)tile * (size_t)(P.n_costs * nz) + (size_t)ci * nz) * 64 + lane;
+}
+
 // ------------------------------------------------------------------------------------------------ costs
 // J = ½x'Qx + q'x + c (+ ½u'Ru + r'u whenever u is given) (+ u'Hx) (+ w·min(1±dq))
-template <int n, int m, bool DENSE = true>
-__device__ __forceinline__ double cost_eval(CostC& C, const double* x, const double* u) {
+// gw (here and in cost_grad_hvp): see cost_wq — the diagonal kinds read their Q and R through it; the dense kinds have no per-trajectory weights
+template <int n, int m, bool DENSE = true, class W = std::nullptr_t>
+__device__ __forceinline__ double cost_eval(CostC& C, const double* x, const double* u, W gw = nullptr) {
   double J;
   if constexpr (DENSE && (n == 13 || n == 12)) {
     if (C.kind == TO_COST_ERROR_QUADRATIC) {
@@ -291,7 +318,7 @@ __device__ __forceinline__ double cost_eval(CostC& C, const double* x, const dou
   } else {
     double xQx = 0.0;
 #pragma unroll
-    for (int i = 0; i < n; ++i) xQx += x[i] * C.Q[i] * x[i];
+    for (int i = 0; i < n; ++i) xQx += x[i] * cost_wq(C, i, gw) * x[i];
     J = 0.5 * xQx;
   }
   double qx = 0.0;
@@ -310,7 +337,7 @@ __device__ __forceinline__ double cost_eval(CostC& C, const double* x, const dou
       }
     } else {
 #pragma unroll
-      for (int i = 0; i < m; ++i) uRu += u[i] * C.R[i] * u[i];
+      for (int i = 0; i < m; ++i) uRu += u[i] * cost_wr<n>(C, i, gw) * u[i];
     }
 #pragma unroll
     for (int i = 0; i < m; ++i) ru += C.r[i] * u[i];
@@ -429,9 +456,9 @@ struct StageCostLds {
 
 // gradient g (n+m) and Hessian-vector product y = H v (n+m) of the cost at (x,u); u-parts zero if terminal
 // DENSE = false compiles the QuadraticCost (full Q, R, H) branches out.
-template <int n, int m, bool DENSE = true>
+template <int n, int m, bool DENSE = true, class W = std::nullptr_t>
 __device__ __forceinline__ void cost_grad_hvp(CostC& C, const double* x, const double* u, bool terminal,
-                                              const double* v, double* g, double* y) {
+                                              const double* v, double* g, double* y, W gw = nullptr) {
   if constexpr (DENSE && (n == 13 || n == 12)) {
     if (C.kind == TO_COST_ERROR_QUADRATIC) {
       Dual xd[n], gd[n];
@@ -458,7 +485,7 @@ __device__ __forceinline__ void cost_grad_hvp(CostC& C, const double* x, const d
     }
   } else {
 #pragma unroll
-    for (int i = 0; i < n; ++i) { g[i] = C.Q[i] * x[i] + C.q[i]; y[i] = C.Q[i] * v[i]; }
+    for (int i = 0; i < n; ++i) { g[i] = cost_wq(C, i, gw) * x[i] + C.q[i]; y[i] = cost_wq(C, i, gw) * v[i]; }
   }
   if (C.kind == TO_COST_DIAGONAL_QUAT) {  // the intended gradient src/lie_costs.jl:82-90
     const double qr[4] = {C.q_ref[0], C.q_ref[1], C.q_ref[2], C.q_ref[3]};
@@ -497,7 +524,7 @@ __device__ __forceinline__ void cost_grad_hvp(CostC& C, const double* x, const d
         }
     } else {
 #pragma unroll
-      for (int i = 0; i < m; ++i) { g[n + i] = C.R[i] * u[i] + C.r[i]; y[n + i] = C.R[i] * v[n + i]; }
+      for (int i = 0; i < m; ++i) { g[n + i] = cost_wr<n>(C, i, gw) * u[i] + C.r[i]; y[n + i] = cost_wr<n>(C, i, gw) * v[n + i]; }
     }
   }
 }

@@ -8,9 +8,12 @@
 
 namespace to {
 
-// One carried array: kind 0 / 3 a tiled double array with L rows per trajectory (3: never copied home), 1 a double and 2 an int
-// per trajectory.
+// One carried array: kind 0 / 3 / 4 a tiled double array with L rows per trajectory (3, 4: never copied home; 4: the per-trajectory cost
+// weights, DevProblem::gw — a kind of their own because their row length is that of the per-trajectory cost terms, so that a set sized
+// with them is told from one sized without), 1 a double and 2 an int per trajectory.
 struct RpSlot { int kind; int L; };
+inline bool rp_tiled(int kind) { return kind == 0 || kind == 3 || kind == 4; }
+inline int rp_device_kind(int kind) { return kind == 4 ? 3 : kind; }  // what the repack kernels see (k_generic.h RpArgs::kind)
 
 // What the buffers of one working set were sized for (cap = 0: nothing allocated).
 struct RpSized {
@@ -19,7 +22,7 @@ struct RpSized {
 };
 
 inline size_t rp_slot_bytes(const RpSlot& s, int Bp) {
-  return (s.kind == 0 || s.kind == 3) ? sizeof(double) * (size_t)s.L * (size_t)Bp : (s.kind == 1 ? sizeof(double) : sizeof(int)) * (size_t)Bp;
+  return rp_tiled(s.kind) ? sizeof(double) * (size_t)s.L * (size_t)Bp : (s.kind == 1 ? sizeof(double) : sizeof(int)) * (size_t)Bp;
 }
 inline size_t rp_map_bytes(int Bp) { return sizeof(int) * (size_t)Bp; }
 

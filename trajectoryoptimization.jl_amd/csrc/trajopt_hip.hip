@@ -242,6 +242,7 @@ int upload_tables(to_handle* h) {
     }
     tf.plants = P.pm != nullptr;  // ... and per-trajectory model parameters by the flagged instances of the general variants only
     tf.time_steps = P.dtb != nullptr;  // ... on which per-trajectory time steps ride
+    tf.cost_weights = P.gw != nullptr;  // per-trajectory cost weights are read by the general variants only (their GW instances)
     P.expand_variant = expand_variant_of(tf);  // (path_plan.h)
     // unit-SOC forward-pass variants (problem_dev.h unit_soc_desc): at least one control-block constraint, and all of them unit
     bool any_ctrl = false, all_unit = true;
@@ -305,7 +306,8 @@ int launch_forward(to_handle* h, bool accept = true, bool two_wave = false) {
     if (accept) TRY(launch_accept(h));
     return TO_OK;
   }
-  const int mode = forward_mode(P.simple_stage, P.n_cons > 0, P.integrator == INTEG_RK4, forward_general(P.expand_variant, P.gl != nullptr, P.cp != nullptr, P.cl != nullptr), P.unit_soc, h->traits.forward);
+  const int mode = forward_mode(forward_simple(P.simple_stage, P.gw != nullptr), P.n_cons > 0, P.integrator == INTEG_RK4,
+                                forward_general(P.expand_variant, P.gl != nullptr, P.cp != nullptr, P.cl != nullptr, P.gw != nullptr), P.unit_soc, h->traits.forward);
   if (mode < 0) return fail(TO_ERR_UNSUPPORTED, "forward-pass variant not compiled for this model");
   if ((two_wave || h->plan.fwd2 == 1) && h->ops->forward2[mode]) TRY(h->ops->forward2[mode](h));
   else TRY(h->ops->forward[0][mode](h));
@@ -390,6 +392,7 @@ int rp_setup(to_handle* h) {
   if (P.n_cons > 0) { add(&a.lam, 3, (int)P.n_duals); add(&a.mu, 3, P.n_cons); }
   if (a.P.cp) add(&a.P.cp, 3, P.n_cp);
   if (a.P.cl) add(&a.P.cl, 3, P.n_cl);  // per-trajectory constraint limits travel with their trajectories, like cp
+  if (a.P.gw) add(&a.P.gw, 4, P.n_costs * (P.n + P.m));  // ... and so do per-trajectory cost weights (rp_plan.h: a kind of their own for the re-use rule)
   for (double** f : {&a.J, &a.dJ, &a.grad, &a.rho, &a.drho, &a.cmax}) add(f, 1, 1);
   for (int** f : {&a.status, &a.iterations, &a.it_inner, &a.outer, &a.dJzero, &a.ls_index, &a.active, &a.budget, &a.bpfail, &a.acc, &a.accp}) add(f, 2, 1);
   if ((int)h->rp_arr.size() > RP_MAX) return fail(TO_ERR_UNSUPPORTED, "repack table too long");
@@ -429,7 +432,7 @@ int rp_move(to_handle* h, int count) {
   RpArgs mv, hm;
   mv.n = hm.n = (int)h->rp_arr.size();
   for (int i = 0; i < mv.n; ++i) {
-    mv.kind[i] = hm.kind[i] = h->rp_arr[i].kind; mv.L[i] = hm.L[i] = h->rp_arr[i].L;
+    mv.kind[i] = hm.kind[i] = rp_device_kind(h->rp_arr[i].kind); mv.L[i] = hm.L[i] = h->rp_arr[i].L;
     mv.src[i] = rp_field(h, h->rp_arr[i].off); mv.dst[i] = h->rp_work[w][i];
     hm.src[i] = rp_field(h, h->rp_arr[i].off); hm.dst[i] = h->rp_home[i];
     HIPCHECK(hipMemsetAsync(h->rp_work[w][i], 0, rp_bytes(h->rp_arr[i], Bp_new), h->stream));  // the padding lanes hold valid (zero) data, active = 0
@@ -464,7 +467,7 @@ int rp_finish(to_handle* h, bool copy) {
   if (copy) {
     RpArgs hm;
     hm.n = (int)h->rp_arr.size();
-    for (int i = 0; i < hm.n; ++i) { hm.kind[i] = h->rp_arr[i].kind; hm.L[i] = h->rp_arr[i].L; hm.src[i] = rp_field(h, h->rp_arr[i].off); hm.dst[i] = h->rp_home[i]; }
+    for (int i = 0; i < hm.n; ++i) { hm.kind[i] = rp_device_kind(h->rp_arr[i].kind); hm.L[i] = h->rp_arr[i].L; hm.src[i] = rp_field(h, h->rp_arr[i].off); hm.dst[i] = h->rp_home[i]; }
     if (launch(k_repack_home, dim3((a.P.B + 63) / 64, hm.n), dim3(64), 0, h->stream, hm, a.active, a.P.B, h->rp_map[w], 1) != TO_OK)
       rc = fail(TO_ERR_HIP, "k_repack_home launch failed");
   }
@@ -691,11 +694,11 @@ int solve_impl(to_handle* h, to_solve_stats* st, int al_mode) {
   HIPCHECK(hipMemsetAsync(a.counter - 1, 0, sizeof(int) * (max_steps + 1), h->stream));
   {  // list mode (path_plan.h solve_forward_list), for this whole solve or not at all; TRAJOPT_FWD_LIST=0 keeps the forward pass's fixed map
     const char* env = std::getenv("TRAJOPT_FWD_LIST");
-    const int mode = forward_mode(P.simple_stage, P.n_cons > 0, P.integrator == INTEG_RK4,
-                                  forward_general(P.expand_variant, P.gl != nullptr, P.cp != nullptr, P.cl != nullptr), P.unit_soc, h->traits.forward);
+    const int mode = forward_mode(forward_simple(P.simple_stage, P.gw != nullptr), P.n_cons > 0, P.integrator == INTEG_RK4,
+                                  forward_general(P.expand_variant, P.gl != nullptr, P.cp != nullptr, P.cl != nullptr, P.gw != nullptr), P.unit_soc, h->traits.forward);
     a.fwd_list = solve_forward_list(h->plan, h->traits, a.h_diag, P.expand_variant, a.compact, al_mode, P.B, P.Bp, plants(h) != 0, P.gl != nullptr,
                                     mode >= 0 && h->ops->forward2[mode] != nullptr && h->ops->expand_backward_scan != nullptr,
-                                    !(env && std::atoi(env) == 0), FWD_LIST_MAX_BP) ? 1 : 0;
+                                    !(env && std::atoi(env) == 0), FWD_LIST_MAX_BP, P.gw != nullptr) ? 1 : 0;
   }
   TRY(ensure_solve_events(h));
   const hipEvent_t e0 = h->sev[0], e1 = h->sev[1];
@@ -1221,6 +1224,16 @@ int to_get_controls_device(to_handle* h, void* dU) {
   CHECK_H(h); CHECK_IDLE(h); CHECK_P(dU); TRY(use_device(h));
   return download_nominal(h, nullptr, h->a.Us, h->a.P.m * (h->a.P.N - 1), dU);
 }
+// the host copy of the per-trajectory cost weights (to_handle::gw_host) -> DevProblem::gw, tiled on the host, in one copy
+static int upload_cost_weights(to_handle* h) {
+  DevProblem& P = h->a.P;
+  std::vector<double> tiled;
+  cost_weights_tile(P.n, P.m, P.B, P.Bp, h->costs.data(), (int)h->costs.size(), h->gw_host, &tiled);
+  if (!h->d_gw) TRY(dev_alloc(h, &h->d_gw, tiled.size()));
+  HIPCHECK(hipMemcpyAsync(h->d_gw, tiled.data(), tiled.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  HIPCHECK(hipStreamSynchronize(h->stream));
+  return TO_OK;
+}
 int to_set_cost(to_handle* h, int32_t id, const to_cost_desc* c) {
   CHECK_H(h); CHECK_IDLE(h); CHECK_P(c); TRY(use_device(h));
   if (id < 0 || id >= (int)h->costs.size()) return fail(TO_ERR_ARGUMENT, "cost id out of range");
@@ -1234,6 +1247,10 @@ int to_set_cost(to_handle* h, int32_t id, const to_cost_desc* c) {
     bool any = false;
     for (char f : h->gl_set) any = any || f;
     if (!any) h->a.P.gl = nullptr;  // every cost is back on its shared descriptor: the default forward variants again
+  }
+  if (h->a.P.gw) {  // ... and so do its per-trajectory weights: the new descriptor's diagonal for every trajectory (the other costs keep theirs)
+    cost_weights_restart(h->a.P.n, h->a.P.m, h->a.P.B, h->costs.data(), (int)h->costs.size(), id, &h->gw_host);
+    TRY(upload_cost_weights(h));
   }
   return upload_tables(h);
 }
@@ -1486,6 +1503,52 @@ int to_clear_model_params_batch(to_handle* h) {
   if (h->a.P.dtb) TRY(upload_plants(h, nullptr));  // per-trajectory time steps ride on the flagged instances: pm stays, on the shared plant
   else { h->a.P.pm = nullptr; h->pm_host.clear(); }
   return upload_tables(h);
+}
+
+// One diagonal Q / R per TRAJECTORY for the cost cost_id (DevProblem::gw; desc_lower.h has every refusal, the host copy and the tiling).  The
+// array holds the weights of EVERY cost — the descriptors' values where nothing was set — and the whole of it goes up again with every call.
+// The handle is then routed like one with per-trajectory constraint limits (path_plan.h TableFlags::cost_weights) and launches the GW
+// instances of the kernels that read a cost's diagonal; X, U, duals and gains are left as they are.
+static CostWeightFacts cost_weight_facts(const to_handle* h) {
+  const DevProblem& P = h->a.P;
+  return CostWeightFacts{h->model_key, model_key_name(h->model_key), P.n, P.m, P.B, h->costs.data(), (int)h->costs.size(), h->inflight.load(), h->track_Nref};
+}
+int to_set_cost_weights_batch(to_handle* h, int32_t cost_id, const double* Q, const double* R) {
+  CostWeightFacts f;
+  if (h) f = cost_weight_facts(h);
+  TRY(validate_cost_weights(h ? &f : nullptr, cost_id, Q, R));  // every refusal, before any device call and before anything changes
+  TRY(use_device(h));
+  DevProblem& P = h->a.P;
+  if (h->gw_host.empty()) cost_weights_fill(P.n, P.m, P.B, h->costs.data(), (int)h->costs.size(), &h->gw_host);
+  cost_weights_store(P.n, P.m, P.B, (int)h->costs.size(), cost_id, Q, R, &h->gw_host);
+  TRY(upload_cost_weights(h));
+  P.gw = h->d_gw;
+  TRY(upload_tables(h));  // (expand_variant bit 2, and with it the compact cost block, follow gw)
+  return check_guards(h, "to_set_cost_weights_batch");
+}
+int to_get_cost_weights_batch(to_handle* h, int32_t cost_id, double* Q, double* R) {
+  CostWeightFacts f;
+  if (h) f = cost_weight_facts(h);
+  TRY(validate_cost_weights_get(h ? &f : nullptr, cost_id, Q, R));
+  const DevProblem& P = h->a.P;
+  const int n = P.n, m = P.m, nz = n + m, B = P.B;
+  const size_t L = h->costs.size() * (size_t)nz;
+  const to_cost_desc& c = h->costs[cost_id];
+  for (int b = 0; b < B; ++b) {  // what every trajectory is evaluated with: the stored values, or the descriptor's diagonal repeated
+    const double* v = P.gw ? h->gw_host.data() + L * b + (size_t)cost_id * nz : nullptr;
+    for (int i = 0; Q && i < n; ++i) Q[i + (size_t)n * b] = v ? v[i] : c.Q[i];
+    for (int j = 0; R && j < m; ++j) R[j + (size_t)m * b] = v ? v[n + j] : c.R[j];
+  }
+  return TO_OK;
+}
+int to_clear_cost_weights_batch(to_handle* h) {
+  CostWeightFacts f;
+  if (h) f = cost_weight_facts(h);
+  TRY(validate_cost_weights_target("to_clear_cost_weights_batch", h ? &f : nullptr, -1, true));
+  TRY(use_device(h));
+  h->a.P.gw = nullptr;
+  h->gw_host.clear();
+  return upload_tables(h);  // every cost on its descriptor, the kernel variants the handle ran before
 }
 
 // One set of time steps per TRAJECTORY (DevProblem::dtb): dt[(N-1), B], knot fastest.  Validation and tiling are host-only code
@@ -1863,7 +1926,7 @@ int to_mpc_advance(to_handle* h, const double* x_meas, const to_mpc_opts* mpc, c
 static TrackFacts track_facts(const to_handle* h) {
   const DevProblem& P = h->a.P;
   return TrackFacts{h->model_key, model_key_name(h->model_key), P.n, P.m, P.N, P.B, h->costs.data(), (int)h->costs.size(), h->cost_index.data(),
-                    h->inflight.load(), h->track_Nref, h->track_end};
+                    h->inflight.load(), h->track_Nref, h->track_end, P.gw != nullptr};
 }
 // the stored starts -> the device, then all N knots of every trajectory into d_gl from the current descriptors (one launch)
 static int track_lower(to_handle* h, const char* who) {
