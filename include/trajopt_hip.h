@@ -85,7 +85,10 @@ extern "C" {
  * by symbol lookup; with a library without them a host feeds each knot's terms through to_set_cost_linear_batch.  And for
  * to_set_cost_weights_batch / to_get_cost_weights_batch / to_clear_cost_weights_batch (one diagonal Q / R per trajectory): three symbols added
  * with TO_ABI_VERSION and TO_ABI_MINOR unchanged and no existing struct changed, found by symbol lookup; a library without them shares the
- * weights of every cost among the trajectories of a handle. */
+ * weights of every cost among the trajectories of a handle.  And for to_set_cost_attitude_batch / to_get_cost_attitude_batch /
+ * to_clear_cost_attitude_batch / to_set_tracking_attitude / to_get_tracking_attitude (one reference quaternion per trajectory for a
+ * DiagonalQuatCost, windowed with the tracking reference): five symbols added with TO_ABI_VERSION and TO_ABI_MINOR unchanged and no existing
+ * struct changed, found by symbol lookup; a library without them shares every q_ref among the trajectories of a handle. */
 #define TO_ABI_VERSION 7
 #define TO_ABI_MINOR 1
 
@@ -401,7 +404,7 @@ int to_set_constraint(to_handle* h, int32_t con_id, const to_constraint_desc* co
  * (src/cost_functions.jl:249-258 — "only changes q and r") for every trajectory of the batch at once.  q[n, B] / r[m, B] (column-major,
  * either may be NULL) REPLACE the linear terms of cost `cost_id` for trajectory b; Q, R, H, c stay the descriptor's.  The host mirrors
  * compute q_b = -Q xf_b (set_goal_state!(prob, Xf::Matrix), src/problem.jl:294-310).  Kinds DIAGONAL, QUADRATIC, DIAGONAL_QUAT (its
- * quaternion reference q_ref stays shared); TO_ERR_UNSUPPORTED for ERROR_QUADRATIC.  to_set_cost on a cost resets its per-trajectory
+ * quaternion reference q_ref stays shared by THIS call; to_set_cost_attitude_batch below gives each trajectory its own); TO_ERR_UNSUPPORTED for ERROR_QUADRATIC.  to_set_cost on a cost resets its per-trajectory
  * terms; to_clear_cost_linear_batch returns the whole handle to shared descriptors.  A GoalConstraint's target per trajectory:
  * to_set_constraint_params_batch (below).  The projected-Newton polish builds its metric from the
  * descriptors alone (per-trajectory q does not enter a Hessian except through the attitude term of quaternion states, which the polish
@@ -417,7 +420,8 @@ int to_clear_cost_linear_batch(to_handle* h);
  * terms q_b = -Q x_ref[j] and, with Uref, r_b = -R u_ref[j], computed on the device by one kernel launch: diagonal kinds -(Q_i x_i);
  * QUADRATIC acc = Q[i,0] x_0, acc = acc + Q[i,j] x_j for ascending j, then -acc; every product and sum rounded on its own — bit for bit what
  * N calls of to_set_cost_linear_batch with those values store, and they write the same storage.  With Uref == NULL the r terms are not
- * touched (the one-argument set_LQR_goal!).  Q, R, H, c and a DiagonalQuatCost's q_ref stay the descriptor's.
+ * touched (the one-argument set_LQR_goal!).  Q, R, H, c and a DiagonalQuatCost's q_ref stay the descriptor's (the q_ref unless
+ * to_set_tracking_attitude below is turned on: it then follows the reference knot's attitude).
  * to_set_tracking_window moves every trajectory's window: 4 B bytes go to the device and all N knots are lowered again from the stored
  * reference and the CURRENT descriptors.  In between, to_set_cost and to_set_cost_linear_batch act on a cost as they always do (it starts
  * over, or takes the given terms, until the next window call); to_clear_cost_linear_batch returns the costs to their descriptors and keeps
@@ -462,6 +466,39 @@ int to_get_cost_linear_batch(to_handle* h, int32_t cost_id, double* q /* [n*B] o
 int to_set_cost_weights_batch(to_handle* h, int32_t cost_id, const double* Q /* [n*B] or NULL */, const double* R /* [m*B] or NULL */);
 int to_get_cost_weights_batch(to_handle* h, int32_t cost_id, double* Q /* [n*B] or NULL */, double* R /* [m*B] or NULL */);
 int to_clear_cost_weights_batch(to_handle* h);
+/* One ATTITUDE REFERENCE per TRAJECTORY: the costs of a Quadrotor put no weight on the quaternion entries of Q (QuatLQRCost,
+ * src/lie_costs.jl:134-141), so the goal attitude lives in w min(1 +- q_ref'q) alone — and a fleet whose members fly to their own goals, or track
+ * their own paths, needs a q_ref each.  Cost cost_id (as in to_set_cost) of trajectory b is the descriptor's cost with q_ref replaced by
+ * q_ref[:, b] (q_ref is [4, B], 4 fastest, in the order of the descriptor's q_ref[0..3], i.e. of the state entries q_ind[0..3]): the expression a
+ * single-trajectory problem built with QuatLQRCost(Q, R, xf_b; w) evaluates.  The values are used as given — not normalised, as QuatLQRCost
+ * leaves xf[quat_ind]; the sign is immaterial under min(1 +- dq).  Q, R, q, r, c, w, q_ind stay the descriptor's, and to_set_cost_linear_batch
+ * terms, to_set_cost_weights_batch weights, constraint parameters and limits, plants and time steps combine on the same cost as they do
+ * without.  Refused before anything changes: a NULL handle or q_ref — TO_ERR_NULL; a cost_id out of range, a solve in flight, a value that is
+ * not finite (naming the first offending trajectory and entry) — TO_ERR_ARGUMENT; a cost that is not TO_COST_DIAGONAL_QUAT, by name (an
+ * ErrorQuadratic keeps its reference in its q slot: out of scope), and the models to_set_cost_weights_batch refuses — TO_ERR_UNSUPPORTED.
+ * Everything that evaluates the cost (the list under to_set_cost_weights_batch) then reads trajectory b's own q_ref.  The values ride on the
+ * kernel instances of per-trajectory weights: while any attitude reference is set the handle is routed and reports (to_solver_path) exactly as
+ * one with weights, its weights array holding the descriptors' diagonals unless the caller gave weights; to_get_cost_weights_batch behaves as
+ * documented in both states, and to_clear_cost_weights_batch on a handle that still holds attitude references returns the weights to the
+ * descriptors and keeps the routing.  The weights / tracking refusals look at weights the CALLER set: attitude references alone refuse
+ * neither to_set_tracking_reference_batch nor to_set_cost_weights_batch.  The setter leaves X, U, duals and gains as they are.  to_get_...
+ * returns what every trajectory is evaluated with: the set values (or those a tracking window wrote, below), or the descriptor's q_ref
+ * repeated B times.  to_set_cost on a cost restarts THAT cost's rows from the new descriptor.  to_clear_... returns every cost to its
+ * descriptor's q_ref and — if the caller set no weights and attitude tracking is off — the handle to the kernel variants it ran before: a solve
+ * after it is bit-identical to the same solve on a fresh handle.
+ * to_set_tracking_attitude(h, 1): every lowering of a window of the stored tracking reference — this call, every to_set_tracking_window, a later
+ * to_set_tracking_reference_batch — also writes, for every knot k whose cost is a DiagonalQuatCost, q_ref_b[i] = Xref[q_ind[i] - 1, j, b]: exact
+ * copies, j the reference knot of the linear terms (the TO_TRACK_END_HOLD clamp included), in the same kernel launch; costs of other kinds are
+ * untouched and the linear terms keep their bits.  Needs a stored reference — TO_ERR_ARGUMENT — and a DiagonalQuatCost among the tracked costs
+ * — TO_ERR_UNSUPPORTED.  to_set_cost_attitude_batch between two window calls acts until the next window call, as to_set_cost_linear_batch
+ * does.  to_set_tracking_attitude(h, 0) returns the tracked costs' q_ref to their descriptors; to_clear_tracking_reference_batch does the same
+ * and turns the mode off.  Off by default: a handle that never turns it on lowers what it always did.  Not announced by TO_ABI_MINOR: look the
+ * symbols up (ABI history above). */
+int to_set_cost_attitude_batch(to_handle* h, int32_t cost_id, const double* q_ref /* [4*B], 4 fastest */);
+int to_get_cost_attitude_batch(to_handle* h, int32_t cost_id, double* q_ref /* [4*B] */);
+int to_clear_cost_attitude_batch(to_handle* h);
+int to_set_tracking_attitude(to_handle* h, int32_t on);
+int to_get_tracking_attitude(to_handle* h, int32_t* on);
 /* One constraint-parameter set per TRAJECTORY (round 6): set_goal_state!(prob, xf; constraint = true) updates the GoalConstraints too
  * (src/problem.jl:303-309, src/constraints.jl:22-87) — here for every trajectory of the batch at once.  con_id names a GOAL constraint,
  * params[p, B] (column-major) = xf_b[inds], the target of trajectory b — or a LINEAR constraint (src/constraints.jl:103-150), params[p, B] =

@@ -782,15 +782,30 @@ end
 `set_LQR_goal!(cost, xf_b)` (src/cost_functions.jl:249-252: q = -Q xf, nothing else) on every cost of the objective for every
 trajectory of the batch — batched MPC / goal sweeps on one handle (SURVEY §8b) — and, with `constraint = true` (the reference's default,
 src/problem.jl:303-309), the target `xf_b[inds]` of every GoalConstraint (`to_set_constraint_params_batch`); `clear_goal_state_batch!`
-returns to the shared descriptors.
+returns to the shared descriptors.  `attitude = true`: every `DiagonalQuatCost` also gets `q_ref_b = Xf[q_ind, b]` — what rebuilding the
+objective with `QuatLQRCost(Q, R, xf_b)` gives (`to_set_cost_attitude_batch`); the default keeps the calls it always made.
 """
-function TO.set_goal_state!(p::BatchProblem, Xf::Matrix{Float64}; objective::Bool = true, constraint::Bool = true)
+function TO.set_goal_state!(p::BatchProblem, Xf::Matrix{Float64}; objective::Bool = true, constraint::Bool = true, attitude::Bool = false)
     size(Xf) == (p.n, p.B) || throw(DimensionMismatch("Xf must be (n, B)"))
-    if objective
-        costs = Any[]
-        for c in p.prob.obj.cost
-            any(x -> x === c, costs) || push!(costs, c)
+    costs = Any[]
+    for c in p.prob.obj.cost
+        any(x -> x === c, costs) || push!(costs, c)
+    end
+    if objective   # every check before anything changes
+        for c in costs
+            c isa TO.QuadraticCostFunction || throw(MethodError(TO.set_LQR_goal!, (c, Xf)))
         end
+    end
+    if attitude    # ... and the attitudes first: the one call the library may still refuse
+        has_cost_attitude_batch() || error("libtrajopt_hip.so does not export to_set_cost_attitude_batch")
+        any(c -> c isa TO.DiagonalQuatCost, costs) || throw(ArgumentError("attitude = true, but the objective has no DiagonalQuatCost"))
+        all(isfinite, Xf) || throw(ArgumentError("Xf is not finite"))
+        for (i, c) in enumerate(costs)
+            c isa TO.DiagonalQuatCost && set_cost_attitude_batch!(p, i, Xf[collect(c.q_ind), :])
+        end
+        goal_attitude_set[p] = true
+    end
+    if objective
         for (i, c) in enumerate(costs)
             c isa TO.QuadraticCostFunction || throw(MethodError(TO.set_LQR_goal!, (c, Xf)))
             q = -(c.Q * Xf)                                   # (n, B), column-major
@@ -979,9 +994,53 @@ function clear_cost_weights_batch!(p::BatchProblem)
     check(ccall((:to_clear_cost_weights_batch, lib), Cint, (Ptr{Cvoid},), p.handle))
     nothing
 end
+"""
+    set_cost_attitude_batch!(p, i, q_ref)     # q_ref :: (4, B); cost i is 1-based
+One reference quaternion per trajectory for the `DiagonalQuatCost` `i` (`to_set_cost_attitude_batch`): trajectory `b` evaluates
+`w min(1 ± q_ref[:, b]'x[q_ind])`; the values are used as given.  `cost_attitude_batch(p, i)` returns what every trajectory is evaluated
+with (the descriptor's `q_ref` repeated if nothing is set), `clear_cost_attitude_batch!(p)` returns every cost to its descriptor.
+`set_tracking_attitude!(p, on)`: while on, every window of the stored tracking reference (`update_trajectory!(p, Xref, Uref, start)`,
+`set_tracking_window!`) also hands every `DiagonalQuatCost` the attitude of its reference knot.  Added without raising `TO_ABI_MINOR`: a
+library that lacks them is detected by symbol lookup (`has_cost_attitude_batch()`).
+"""
+has_cost_attitude_batch() = Libdl.dlsym(Libdl.dlopen(lib), :to_set_cost_attitude_batch; throw_error = false) !== nothing
+function set_cost_attitude_batch!(p::BatchProblem, i::Integer, q_ref::Matrix{Float64})
+    has_cost_attitude_batch() || error("libtrajopt_hip.so does not export to_set_cost_attitude_batch")
+    size(q_ref) == (4, p.B) || throw(DimensionMismatch("q_ref must be (4, B)"))
+    check(ccall((:to_set_cost_attitude_batch, lib), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}), p.handle, i - 1, q_ref))
+    nothing
+end
+function cost_attitude_batch(p::BatchProblem, i::Integer)
+    has_cost_attitude_batch() || error("libtrajopt_hip.so does not export to_get_cost_attitude_batch")
+    q_ref = zeros(4, p.B)
+    check(ccall((:to_get_cost_attitude_batch, lib), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}), p.handle, i - 1, q_ref))
+    q_ref
+end
+function clear_cost_attitude_batch!(p::BatchProblem)
+    has_cost_attitude_batch() || error("libtrajopt_hip.so does not export to_clear_cost_attitude_batch")
+    check(ccall((:to_clear_cost_attitude_batch, lib), Cint, (Ptr{Cvoid},), p.handle))
+    nothing
+end
+function set_tracking_attitude!(p::BatchProblem, on::Bool = true)
+    has_cost_attitude_batch() || error("libtrajopt_hip.so does not export to_set_tracking_attitude")
+    check(ccall((:to_set_tracking_attitude, lib), Cint, (Ptr{Cvoid}, Int32), p.handle, on ? 1 : 0))
+    p
+end
+function tracking_attitude(p::BatchProblem)
+    has_cost_attitude_batch() || error("libtrajopt_hip.so does not export to_get_tracking_attitude")
+    on = Ref{Int32}(0)
+    check(ccall((:to_get_tracking_attitude, lib), Cint, (Ptr{Cvoid}, Ref{Int32}), p.handle, on))
+    on[] != 0
+end
+"handles whose goal attitudes were set through `set_goal_state!(p, Xf; attitude = true)`: `clear_goal_state_batch!` clears those too"
+const goal_attitude_set = WeakKeyDict{BatchProblem,Bool}()
 function clear_goal_state_batch!(p::BatchProblem)
     check(ccall((:to_clear_cost_linear_batch, lib), Cint, (Ptr{Cvoid},), p.handle))
     check(ccall((:to_clear_constraint_params_batch, lib), Cint, (Ptr{Cvoid},), p.handle))
+    if get(goal_attitude_set, p, false)
+        clear_cost_attitude_batch!(p)
+        delete!(goal_attitude_set, p)
+    end
 end
 "Cost-to-go of the last backward pass: S[ne,ne,N,B], s[ne,N,B] (S_N = Qxx_N; S_k = Qxx + K'Quu K + K'Qux + Qux'K)."
 function cost_to_go(p::BatchProblem)
@@ -1132,7 +1191,7 @@ function profile(p::BatchProblem)
     (kernel_ms = ms, launches = launches)
 end
 
-export LinearMap, MassDoubleIntegrator, BatchProblem, set_model_params_batch!, model_params_batch, clear_model_params_batch!, has_model_params_batch, set_constraint_limits_batch!, get_constraint_limits_batch, clear_constraint_limits_batch!, has_constraint_limits_batch, set_time_steps_batch!, set_final_times_batch!, time_steps_batch, clear_time_steps_batch!, has_time_steps_batch, policy_rollout, PolicyOpts, PolicyResult, policy_rollout_mc, policy_noise_draws, PolicyNoise, mpc_advance!, has_mpc_advance, MpcOpts, MpcResult, set_tracking_window!, tracking_window, clear_tracking_reference_batch!, cost_linear_batch, has_tracking_reference_batch, set_cost_weights_batch!, cost_weights_batch, clear_cost_weights_batch!, has_cost_weights_batch, abi_minor, SolverOpts, solver_options, default_options, solve_ilqr!, solve_al!, solve_pn!, solve_altro!, solve_async!, wait_solve!, dynamics_defect, expand!, backwardpass!, forwardpass!,
+export LinearMap, MassDoubleIntegrator, BatchProblem, set_model_params_batch!, model_params_batch, clear_model_params_batch!, has_model_params_batch, set_constraint_limits_batch!, get_constraint_limits_batch, clear_constraint_limits_batch!, has_constraint_limits_batch, set_time_steps_batch!, set_final_times_batch!, time_steps_batch, clear_time_steps_batch!, has_time_steps_batch, policy_rollout, PolicyOpts, PolicyResult, policy_rollout_mc, policy_noise_draws, PolicyNoise, mpc_advance!, has_mpc_advance, MpcOpts, MpcResult, set_tracking_window!, tracking_window, clear_tracking_reference_batch!, cost_linear_batch, has_tracking_reference_batch, set_cost_weights_batch!, cost_weights_batch, clear_cost_weights_batch!, has_cost_weights_batch, set_cost_attitude_batch!, cost_attitude_batch, clear_cost_attitude_batch!, set_tracking_attitude!, tracking_attitude, has_cost_attitude_batch, abi_minor, SolverOpts, solver_options, default_options, solve_ilqr!, solve_al!, solve_pn!, solve_altro!, solve_async!, wait_solve!, dynamics_defect, expand!, backwardpass!, forwardpass!,
     stage_costs, al_cost, dynamics_jacobians, cost_expansion, gains, cost_gradient_hessian, discrete_jacobian, duals, set_duals!,
     reset_duals!, dual_update!, comm_unique_id, comm_init_rank!, allgather!, allgather_stats, comm_shards, comm_destroy!, solver_path, knot_dims, device_count, build_id
 

@@ -292,6 +292,12 @@ HIP_ONLY = {
     "set_cost_weights_batch": [_H, C.c_int32, _PD, _PD],
     "get_cost_weights_batch": [_H, C.c_int32, _PD, _PD],
     "clear_cost_weights_batch": [_H],
+    # one attitude reference (a DiagonalQuatCost's q_ref) per trajectory, windowed with the tracking reference (OPTIONAL_HIP below)
+    "set_cost_attitude_batch": [_H, C.c_int32, _PD],
+    "get_cost_attitude_batch": [_H, C.c_int32, _PD],
+    "clear_cost_attitude_batch": [_H],
+    "set_tracking_attitude": [_H, C.c_int32],
+    "get_tracking_attitude": [_H, _PI],
 }
 # Entry points added without raising TO_ABI_MINOR (include/trajopt_hip.h, ABI history): detected by symbol lookup.  A library that does
 # not export them still loads; the names are then absent from Library._fn and the wrappers in api.py raise UnsupportedError.
@@ -301,7 +307,9 @@ OPTIONAL_HIP = ("set_model_params_batch", "get_model_params_batch", "clear_model
                 "mpc_advance",
                 "set_tracking_reference_batch", "set_tracking_window", "get_tracking_window", "clear_tracking_reference_batch",
                 "get_cost_linear_batch",
-                "set_cost_weights_batch", "get_cost_weights_batch", "clear_cost_weights_batch")
+                "set_cost_weights_batch", "get_cost_weights_batch", "clear_cost_weights_batch",
+                "set_cost_attitude_batch", "get_cost_attitude_batch", "clear_cost_attitude_batch", "set_tracking_attitude",
+                "get_tracking_attitude")
 
 
 class Library:

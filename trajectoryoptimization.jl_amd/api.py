@@ -47,7 +47,8 @@ __all__ = [
     "set_time_steps_batch", "set_final_times_batch", "time_steps", "clear_time_steps_batch", "cost", "states", "controls", "initial_controls", "initial_states",
     "set_initial_state", "set_goal_state", "update_trajectory", "set_tracking_reference_batch", "set_tracking_window", "get_tracking_window",
     "clear_tracking_reference_batch", "get_cost_linear_batch", "set_cost_weights_batch", "get_cost_weights_batch", "clear_cost_weights_batch",
-    "set_LQR_weights_batch", "get_constraints", "get_objective", "get_model",
+    "set_LQR_weights_batch", "set_cost_attitude_batch", "get_cost_attitude_batch", "clear_cost_attitude_batch", "set_tracking_attitude",
+    "get_tracking_attitude", "get_constraints", "get_objective", "get_model",
     "get_initial_state", "get_final_state", "get_trajectory", "gettimes",
     "SolverOptions", "iLQRSolver", "ALSolver", "ALTROSolver", "ProjectedNewtonSolver", "dynamics_defect", "solve", "SolvePipeline", "iterations", "status", "max_violation",
     "evaluate_constraints", "constraint_jacobians", "sense", "upper_bound", "lower_bound", "is_bound",
@@ -1747,12 +1748,16 @@ def gettimes(prob):
     return prob.gettimes()
 
 
-def set_goal_state(prob, xf, objective=True, constraint=True):
-    """set_goal_state!  (src/problem.jl:294-310): set_LQR_goal! on every cost, update GoalConstraints."""
+def set_goal_state(prob, xf, objective=True, constraint=True, attitude=False):
+    """set_goal_state!  (src/problem.jl:294-310): set_LQR_goal! on every cost, update GoalConstraints.  ``attitude=True`` (with one goal
+    per trajectory, ``xf`` [B, n]) also gives every DiagonalQuatCost the goal's attitude as its reference quaternion, q_ref_b =
+    xf_b[q_ind] — what rebuilding the objective with ``QuatLQRCost(Q, R, xf_b)`` gives (to_set_cost_attitude_batch)."""
     if getattr(prob, "hybrid", False):  # (the reference's set_goal_state! needs one state dimension for all knots as well)
         raise UnsupportedError("set_goal_state on a hybrid model vector: the knots have different state dimensions; rebuild the problem")
     if np.asarray(xf).ndim == 2:
-        return _set_goal_state_batch(prob, xf, objective, constraint)
+        return _set_goal_state_batch(prob, xf, objective, constraint, attitude)
+    if attitude:
+        raise ArgumentError("set_goal_state: attitude=True needs one goal per trajectory, xf [B, n] (a shared goal's q_ref is the descriptor's: rebuild the cost)")
     xf = _vec(xf, prob.n, "xf")
     if objective:
         for i, c in enumerate(prob._cost_objs):
@@ -1775,7 +1780,7 @@ def set_goal_state(prob, xf, objective=True, constraint=True):
         prob.xf_batch = None  # to_set_cost starts every cost's per-trajectory terms over: the batch goals are gone
 
 
-def _set_goal_state_batch(prob, Xf, objective=True, constraint=True):
+def _set_goal_state_batch(prob, Xf, objective=True, constraint=True, attitude=False):
     """set_goal_state!(prob, Xf) with ONE GOAL PER TRAJECTORY, Xf [B, n] (batched MPC / goal sweeps on one handle):
     set_LQR_goal!(cost, xf_b) on every cost for every trajectory — q_b = -Q xf_b, nothing else changes (src/cost_functions.jl:249-252)
     — through to_set_cost_linear_batch, and with ``constraint=True`` the target of every GoalConstraint, xf_b[inds], through
@@ -1783,6 +1788,21 @@ def _set_goal_state_batch(prob, Xf, objective=True, constraint=True):
     Xf = np.ascontiguousarray(np.asarray(Xf, dtype=np.float64))
     if Xf.shape != (prob.B, prob.n):
         raise DimensionMismatch(f"Xf must be [B, n] = {(prob.B, prob.n)}; got {Xf.shape}")
+    if objective and any(c.kind == capi.COST_ERROR_QUADRATIC for c in prob._cost_objs):
+        raise TypeError("set_LQR_goal! is only defined for QuadraticCostFunction (src/cost_functions.jl:249)")
+    if attitude:
+        # Everything that can be refused is refused before anything changes: the checks here, then the attitudes go FIRST — the library
+        # decides its own refusals (a model without per-trajectory cost data) on the first of these calls, ahead of every other change.
+        _need_cost_attitude_batch(prob)
+        if not any(c.kind == capi.COST_DIAGONAL_QUAT for c in prob._cost_objs):
+            raise ArgumentError("set_goal_state: attitude=True, but the objective has no DiagonalQuatCost (QuatLQRCost) whose q_ref could follow the goal")
+        if not np.isfinite(Xf).all():
+            b, i = np.argwhere(~np.isfinite(Xf))[0]
+            raise ArgumentError(f"set_goal_state: Xf[{int(b)}, {int(i)}] is not finite")
+        for i, c in enumerate(prob._cost_objs):  # QuatLQRCost: q_ref = xf[quat_ind], used as given (src/lie_costs.jl:134-141)
+            if c.kind == capi.COST_DIAGONAL_QUAT:
+                prob._call("set_cost_attitude_batch", i, prob._pd(np.ascontiguousarray(Xf[:, [j - 1 for j in c.q_ind]])))
+        prob._goal_attitude = True
     if constraint:  # (src/problem.jl:303-309: every GoalConstraint of the list gets the new target — here trajectory by trajectory)
         for i, con in enumerate(prob.constraints.constraints):
             if isinstance(con, GoalConstraint):
@@ -1887,9 +1907,13 @@ def set_bounds_batch(prob, con_id, x_max=None, x_min=None, u_max=None, u_min=Non
 
 
 def clear_goal_state_batch(prob):
-    """Back to the shared descriptors (to_clear_cost_linear_batch, to_clear_constraint_params_batch)."""
+    """Back to the shared descriptors (to_clear_cost_linear_batch, to_clear_constraint_params_batch — and to_clear_cost_attitude_batch when
+    ``set_goal_state(..., attitude=True)`` set goal attitudes)."""
     prob._call("clear_cost_linear_batch")
     prob._call("clear_constraint_params_batch")
+    if getattr(prob, "_goal_attitude", False):
+        prob._call("clear_cost_attitude_batch")
+        prob._goal_attitude = False
     prob.xf_batch = None
 
 
@@ -1916,15 +1940,18 @@ def _tracking_starts(prob, start):
     return np.ascontiguousarray(s, dtype=np.int32)
 
 
-def set_tracking_reference_batch(prob, Xref, Uref=None, start=1, end="refuse"):
+def set_tracking_reference_batch(prob, Xref, Uref=None, start=1, end="refuse", attitude=False):
     """One tracking reference per TRAJECTORY, windowed on the device (to_set_tracking_reference_batch): ``update_trajectory`` for a fleet
     whose members follow their own paths, or one path at their own phase.  ``Xref`` is [B, Nref, n] (the layout of ``states`` with Nref
     for N), ``Uref`` [B, Nref, m] or [B, Nref-1, m] (padded with a zero knot, as ``update_trajectory`` treats a short U) or None (the r
     terms are then not touched), ``start`` an int or [B] ints, 1-based: knot k (0-based) of trajectory b tracks reference knot
     ``start[b] - 1 + k``; under ``end="hold"`` knots past the end track the last knot, under ``end="refuse"`` such a window is an error.
     Needs a tracking objective (a distinct cost per knot).  Only q and r of the costs change, as with ``set_LQR_goal!``; the terms are what
-    N ``set_cost_linear_batch`` calls with q_b = -Q x_ref, r_b = -R u_ref store, bit for bit.  ``set_tracking_window`` moves the windows."""
+    N ``set_cost_linear_batch`` calls with q_b = -Q x_ref, r_b = -R u_ref store, bit for bit.  ``set_tracking_window`` moves the windows.
+    ``attitude=True`` turns ``set_tracking_attitude`` on as well: every DiagonalQuatCost then tracks the attitude of its reference knot."""
     _need_tracking_reference(prob)
+    if attitude:
+        _need_cost_attitude_batch(prob)
     B, N, n, m = prob.B, prob.N, prob.n, prob.m
     if end not in _TRACK_END:
         raise ArgumentError(f"end must be one of {sorted(_TRACK_END)}; got {end!r}")
@@ -1944,6 +1971,8 @@ def set_tracking_reference_batch(prob, Xref, Uref=None, start=1, end="refuse"):
     X = np.ascontiguousarray(X)
     prob._call("set_tracking_reference_batch", Nref, prob._pd(X), prob._pd(U) if U is not None else None, prob._pi(s), _TRACK_END[end])
     prob._tracking = dict(Nref=Nref, end=end, start=s.copy())
+    if attitude:
+        set_tracking_attitude(prob, True)
 
 
 def set_tracking_window(prob, start):
@@ -1970,6 +1999,57 @@ def clear_tracking_reference_batch(prob):
     _need_tracking_reference(prob, "clear_tracking_reference_batch")
     prob._call("clear_tracking_reference_batch")
     prob._tracking = None
+
+
+def _need_cost_attitude_batch(prob, name="set_cost_attitude_batch"):
+    if name not in prob._lib._fn:
+        raise UnsupportedError(f"per-trajectory attitude references need a HIP library that exports to_{name} "
+                               "(the CPU oracle shares the q_ref of every DiagonalQuatCost among the trajectories of a problem)")
+
+
+def set_tracking_attitude(prob, on=True):
+    """Attitude tracking on or off (to_set_tracking_attitude; off by default).  On: every lowering of a window of the stored tracking
+    reference — this call, ``set_tracking_window``, a later ``set_tracking_reference_batch`` — also gives every knot whose cost is a
+    DiagonalQuatCost the reference attitude of ITS knot, q_ref_b = Xref[b, j, q_ind - 1], exact copies.  Off: the tracked costs' q_ref
+    return to their descriptors.  Needs a stored reference and a DiagonalQuatCost among the tracked costs."""
+    _need_cost_attitude_batch(prob, "set_tracking_attitude")
+    prob._call("set_tracking_attitude", 1 if on else 0)
+
+
+def get_tracking_attitude(prob):
+    """Whether attitude tracking is on (to_get_tracking_attitude)."""
+    _need_cost_attitude_batch(prob, "get_tracking_attitude")
+    on = C.c_int32(0)
+    prob._call("get_tracking_attitude", C.byref(on))
+    return bool(on.value)
+
+
+def set_cost_attitude_batch(prob, cost_id, q_ref):
+    """One reference quaternion per TRAJECTORY for the DiagonalQuatCost ``cost_id`` (0-based position among the problem's distinct costs;
+    to_set_cost_attitude_batch): ``q_ref`` [B, 4], in the order of the cost's ``q_ind``, used as given (not normalised; the sign is
+    immaterial under min(1 +- q_ref'q)).  Q, R, q, r, c, w stay the descriptor's; X, U, duals and gains stay as they are."""
+    _need_cost_attitude_batch(prob)
+    a = np.asarray(q_ref, dtype=np.float64)
+    if a.shape != (prob.B, 4):
+        raise DimensionMismatch(f"q_ref must be [B, 4] = {(prob.B, 4)}; got {a.shape}")
+    prob._call("set_cost_attitude_batch", int(cost_id), prob._pd(np.ascontiguousarray(a)))
+
+
+def get_cost_attitude_batch(prob, cost_id):
+    """[B, 4]: the reference quaternion cost ``cost_id`` evaluates for every trajectory (to_get_cost_attitude_batch) — the descriptor's,
+    repeated, while none is set."""
+    _need_cost_attitude_batch(prob, "get_cost_attitude_batch")
+    a = np.empty((prob.B, 4))
+    prob._call("get_cost_attitude_batch", int(cost_id), prob._pd(a))
+    return a
+
+
+def clear_cost_attitude_batch(prob):
+    """Every cost back to the q_ref of its descriptor (to_clear_cost_attitude_batch); without per-trajectory weights a solve after it
+    equals the same solve on a fresh problem bit for bit."""
+    _need_cost_attitude_batch(prob, "clear_cost_attitude_batch")
+    prob._call("clear_cost_attitude_batch")
+    prob._goal_attitude = False
 
 
 def get_cost_linear_batch(prob, cost_id):

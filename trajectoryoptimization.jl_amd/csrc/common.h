@@ -135,9 +135,10 @@ __device__ __forceinline__ double* slot_ptr(double* nominal, double* cand, const
 // gl0: this lane's pointer into DevProblem::gl (per-trajectory linear cost terms; nullptr: none)
 // cp0 / cl0: this lane's pointers into DevProblem::cp / cl (per-trajectory constraint parameters / limits; general variants only)
 // dt0: dt_lane of this lane's trajectory (per-trajectory time steps, problem_dev.h step_dt), or nothing: the shared steps, read as ever
-// gw0: this lane's pointer to entry 0 of DevProblem::gw (per-trajectory cost weights, problem_dev.h cost_wq), or nothing: the descriptors' weights
+// gw0: this lane's pointers to entry 0 of DevProblem::gw and ga (per-trajectory cost weights and attitude references, problem_dev.h CostLane /
+// cost_lane), or nothing: the descriptors' weights and q_ref
 template <int nz> __device__ __forceinline__ std::nullptr_t cost_block(std::nullptr_t, int) { return nullptr; }
-template <int nz> __device__ __forceinline__ const double* cost_block(const double* gw0, int ci) { return gw0 + (size_t)ci * nz * 64; }
+template <int nz> __device__ __forceinline__ CostLane cost_block(CostLane gw0, int ci) { return CostLane{gw0.w + (size_t)ci * nz * 64, gw0.a + (size_t)ci * 4 * 64}; }
 template <class M, bool GEN = true, class D = std::nullptr_t, class W = std::nullptr_t>
 __device__ __forceinline__ double knot_cost(const DevProblem& P, int k, const double* x, const double* u, const double* lam0,
                                             const double* mu0, bool with_al, const double* gl0 = nullptr, const double* cp0 = nullptr,
@@ -284,7 +285,7 @@ __device__ __forceinline__ void trajectory_pass(const KArgs& a, int tile, int la
       }
     }
     if (cmax_out && P.n_cons > 0) { const double v = knot_violation<M>(P, k, x, u, cp0, cl0); if (!(v <= cmax)) cmax = v; }
-    if constexpr (GW) { if (J_out) J += knot_cost<M>(P, k, x, u, lam0, mu0, with_al, TILE_PTR(P.gl, P.n_costs * nz), cp0, cl0, dt0, TILE_PTR(P.gw, P.n_costs * nz)); }
+    if constexpr (GW) { if (J_out) J += knot_cost<M>(P, k, x, u, lam0, mu0, with_al, TILE_PTR(P.gl, P.n_costs * nz), cp0, cl0, dt0, cost_lane<nz>(P, tile, lane)); }
     else
     if (J_out) J += knot_cost<M>(P, k, x, u, lam0, mu0, with_al, TILE_PTR(P.gl, P.n_costs * nz), cp0, cl0, dt0);
   }

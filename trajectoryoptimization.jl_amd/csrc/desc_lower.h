@@ -267,7 +267,7 @@ struct TrackFacts {
   const to_cost_desc* costs; int n_costs; const int* cost_index /* [N] */;
   bool in_flight;
   int Nref_set, end_mode_set;
-  bool cost_weights = false;  // DevProblem::gw is set (to_set_cost_weights_batch): k_track_lower forms -Q x_ref from the DESCRIPTOR's Q
+  bool cost_weights = false;  // the CALLER set weights (to_set_cost_weights_batch; CostLaneState::weights): k_track_lower forms -Q x_ref from the DESCRIPTOR's Q
 };
 // the window itself: start[B] (NULL: 1 for all) against a reference of Nref knots
 inline int validate_tracking_starts(const char* who, int N, int B, int Nref, int end_mode, const int32_t* start) {
@@ -464,6 +464,80 @@ inline void cost_weights_tile(int n, int m, int B, int Bp, const to_cost_desc* c
       }
     }
 }
+
+// Per-trajectory attitude references (to_set_cost_attitude_batch / to_get_... / to_clear_..., to_set_tracking_attitude): every refusal, decided from
+// what the host knows of the handle before any device call, the image of DevProblem::ga, and the rules by which ga rides on gw.  The facts are
+// CostWeightFacts (the target rules are those of the weights: the same models are refused).  The VALUES are used as given — QuatLQRCost does
+// not normalise xf[quat_ind] either (src/lie_costs.jl:134-141), and the sign is immaterial under min(1 +- dq) — and only held to being finite.
+inline int validate_cost_attitude_kind(const char* who, const CostWeightFacts& f, int32_t cost_id) {
+  const int kind = f.costs[cost_id].kind;
+  if (kind != TO_COST_DIAGONAL_QUAT)
+    return fail(TO_ERR_UNSUPPORTED, std::string(who) + ": cost " + std::to_string(cost_id) + " is of kind " + cost_kind_name(kind) +
+                                        "; a per-trajectory attitude reference is the q_ref of a DiagonalQuatCost only" +
+                                        (kind == TO_COST_ERROR_QUADRATIC ? " (an ErrorQuadratic keeps its reference in its q slot)" : ""));
+  return TO_OK;
+}
+inline int validate_cost_attitude(const CostWeightFacts* f, int32_t cost_id, const double* q_ref /* [4, B] */) {
+  const char* who = "to_set_cost_attitude_batch";
+  if (!f) return fail(TO_ERR_NULL, "null handle");
+  if (!q_ref) return fail(TO_ERR_NULL, std::string(who) + ": q_ref is NULL");
+  if (int r = validate_cost_weights_target(who, f, cost_id)) return r;
+  if (int r = validate_cost_attitude_kind(who, *f, cost_id)) return r;
+  for (int b = 0; b < f->B; ++b)
+    for (int i = 0; i < 4; ++i)
+      if (!std::isfinite(q_ref[i + (size_t)4 * b]))
+        return fail(TO_ERR_ARGUMENT, std::string(who) + ": q_ref[" + std::to_string(i) + "] of trajectory " + std::to_string(b) + " is not finite");
+  return TO_OK;
+}
+inline int validate_cost_attitude_get(const CostWeightFacts* f, int32_t cost_id, const double* q_ref) {
+  const char* who = "to_get_cost_attitude_batch";
+  if (!f) return fail(TO_ERR_NULL, "null handle");
+  if (!q_ref) return fail(TO_ERR_NULL, std::string(who) + ": q_ref is NULL");
+  if (int r = validate_cost_weights_target(who, f, cost_id)) return r;
+  return validate_cost_attitude_kind(who, *f, cost_id);
+}
+// to_set_tracking_attitude: on needs a stored reference and a DiagonalQuatCost among the tracked costs (those of cost_index[0 .. N-1])
+inline int validate_tracking_attitude(const TrackFacts* f, int32_t on) {
+  const char* who = "to_set_tracking_attitude";
+  if (!f) return fail(TO_ERR_NULL, "null handle");
+  if (f->in_flight) return fail(TO_ERR_ARGUMENT, "an asynchronous solve is in flight on this handle (call to_solve_wait first)");
+  if (on != 0 && on != 1) return fail(TO_ERR_ARGUMENT, std::string(who) + ": on must be 0 or 1; got " + std::to_string(on));
+  if (!on) return TO_OK;
+  if (f->Nref_set < 1) return fail(TO_ERR_ARGUMENT, std::string(who) + ": no tracking reference is set (to_set_tracking_reference_batch first)");
+  for (int k = 0; k < f->N; ++k)
+    if (f->costs[f->cost_index[k]].kind == TO_COST_DIAGONAL_QUAT) return TO_OK;
+  return fail(TO_ERR_UNSUPPORTED, std::string(who) + ": none of the tracked costs is a DiagonalQuatCost (a reference attitude is the q_ref of that kind only)");
+}
+// The image of DevProblem::ga: L = 4 n_costs rows per trajectory, row 4 ci + i = q_ref[i] of cost ci (a cost of another kind carries its
+// descriptor's q_ref slot, which is never read).  cost_attitude_fill: every cost's descriptor values as a host array [L, B] (first use);
+// cost_attitude_rows: one cost's rows alone, [4, B] (to_set_cost, the clears); cost_attitude_tile: the device layout of cost_weights_tile —
+// entry e of trajectory b at tiled[((b >> 6) L + e) 64 + (b & 63)], Bp / 64 tiles and one spare, the lanes behind the batch on the descriptors'
+// values.  After the first upload the DEVICE array is the truth (k_track_lower writes it): the setter, the getter and the restarts move one
+// cost's four rows and nothing else.
+inline void cost_attitude_rows(int B, const to_cost_desc& c, std::vector<double>* rows) {
+  rows->resize((size_t)4 * B);
+  for (int b = 0; b < B; ++b)
+    for (int i = 0; i < 4; ++i) (*rows)[i + (size_t)4 * b] = c.q_ref[i];
+}
+inline void cost_attitude_fill(int B, const to_cost_desc* costs, int n_costs, std::vector<double>* values) {
+  const size_t L = (size_t)4 * n_costs;
+  values->assign(L * B, 0.0);
+  for (int b = 0; b < B; ++b)
+    for (int ci = 0; ci < n_costs; ++ci)
+      for (int i = 0; i < 4; ++i) (*values)[L * b + 4 * ci + i] = costs[ci].q_ref[i];
+}
+inline size_t cost_attitude_tiled_len(int n_costs, int Bp) { return ((size_t)Bp / 64 + 1) * (size_t)n_costs * 4 * 64; }
+inline void cost_attitude_tile(int B, int Bp, const to_cost_desc* costs, int n_costs, const std::vector<double>& values, std::vector<double>* tiled) {
+  const size_t L = (size_t)4 * n_costs, tiles = (size_t)Bp / 64 + 1;
+  tiled->assign(cost_attitude_tiled_len(n_costs, Bp), 0.0);
+  for (size_t t = 0; t < tiles; ++t)
+    for (size_t e = 0; e < L; ++e)
+      for (int l = 0; l < 64; ++l) {
+        const size_t b = t * 64 + l;
+        (*tiled)[(t * L + e) * 64 + l] = b < (size_t)B ? values[L * b + e] : costs[e / 4].q_ref[e % 4];
+      }
+}
+// (How ga rides on gw — which of the two arrays a call fills, when both are released — is path_plan.h cost_lane_step.)
 
 // rot: attitude representation of the model's state (to_rotation), -1 for vector-space models
 inline int validate_cost(int n, int rot, const to_cost_desc& c) {

@@ -98,6 +98,9 @@ struct to_handle_s {
   std::vector<std::vector<double>> cl_host; // [n_cons] limits[q, B] as to_set_constraint_limits_batch was given them (empty: shared limits)
   double* d_gw = nullptr;   // per-trajectory cost weights (DevProblem::gw), tiled, L = n_costs * (n + m), one spare tile; allocated on first use
   std::vector<double> gw_host;  // [L, B] the diagonal Q / R every trajectory's costs are evaluated with (desc_lower.h cost_weights_fill; empty: DevProblem::gw is null)
+  double* d_ga = nullptr;   // per-trajectory attitude references (DevProblem::ga), tiled, L = 4 * n_costs, one spare tile; allocated on first use.  The device
+                            // array is the truth after its first fill (k_track_lower writes it); set with d_gw and cleared with it
+  to::CostLaneState lane;     // why gw / ga are set: the caller's weights, the caller's attitudes, attitude tracking (path_plan.h cost_lane_step)
   double* d_tmp = nullptr;  // [Bp] scratch for reductions / outputs
   double* d_tmp2 = nullptr;
   // multi-GPU: RCCL communicator of the batch shards (to_comm_*; librccl is dlopen'ed on first use)

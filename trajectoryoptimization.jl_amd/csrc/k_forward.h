@@ -115,7 +115,7 @@ __device__ __forceinline__ void forward_candidate(const KArgs& a, int tile, int 
   // per-trajectory cost weights (general variants): wave-uniform like has_gl.  This translation unit is compiled with -ffp-contract=on — fused
   // operations are formed per source expression — so the side a handle without weights takes computes the bits it always did
   const bool has_gw = GEN && P.gw != nullptr;
-  const double* gw0 = TILE_PTR(P.gw, P.n_costs * (n + m));
+  const CostLane gw0 = cost_lane<n + m>(P, tile, lane);  // (with them, the per-trajectory attitude references: DevProblem::ga rides on gw)
   const int ci0 = P.cost_index[0];
   const double* dt0 = dt_lane_of<(MODE & 64) != 0>(P, b);  // bit6: the trajectory's own time steps (DevProblem::dtb; with bit5, picked by the launcher)
   double h0 = 0.0;
@@ -759,7 +759,7 @@ __device__ __forceinline__ void fwd2_account(const KArgs& a, int tile, int lane,
   // per-trajectory cost weights (general variants): wave-uniform like has_gl.  This translation unit is compiled with -ffp-contract=on — fused
   // operations are formed per source expression — so the side a handle without weights takes computes the bits it always did
   const bool has_gw = GEN && P.gw != nullptr;
-  const double* gw0 = TILE_PTR(P.gw, P.n_costs * (n + m));
+  const CostLane gw0 = cost_lane<n + m>(P, tile, lane);  // (with them, the per-trajectory attitude references: DevProblem::ga rides on gw)
   const int ci0 = P.cost_index[0];
   double h0 = 0.0;
   if constexpr (SIMPLE) {

@@ -68,7 +68,7 @@ __global__ void __launch_bounds__(64) k_cost(KArgs a, int with_al, double* out, 
       for (int i = 0; i < n; ++i) x[i] = EL(X, k * n + i);
 #pragma unroll
       for (int i = 0; i < m; ++i) u[i] = (k < N - 1) ? EL(U, k * m + i) : 0.0;
-      if constexpr (GW) EL(o, k) = knot_cost<M>(P, k, x, u, nullptr, nullptr, false, TILE_PTR(P.gl, P.n_costs * (n + m)), nullptr, nullptr, dt0, TILE_PTR(P.gw, P.n_costs * (n + m)));
+      if constexpr (GW) EL(o, k) = knot_cost<M>(P, k, x, u, nullptr, nullptr, false, TILE_PTR(P.gl, P.n_costs * (n + m)), nullptr, nullptr, dt0, cost_lane<n + m>(P, tile, lane));
       else
       EL(o, k) = knot_cost<M>(P, k, x, u, nullptr, nullptr, false, TILE_PTR(P.gl, P.n_costs * (n + m)), nullptr, nullptr, dt0);
     }
@@ -193,7 +193,7 @@ __global__ void __launch_bounds__(64) k_outer_update(KArgs a) {
   }
   if constexpr (GW)
     EL(TILE_PTR(a.knotbuf, N), k) = knot_cost<M>(P, k, x, u, lam0, mn0, true, TILE_PTR(P.gl, P.n_costs * nz), TILE_PTR(P.cp, P.n_cp), TILE_PTR(P.cl, P.n_cl), dt_lane(P, b),
-                                                 TILE_PTR(P.gw, P.n_costs * nz));
+                                                 cost_lane<nz>(P, tile, lane));
   else
   EL(TILE_PTR(a.knotbuf, N), k) = knot_cost<M>(P, k, x, u, lam0, mn0, true, TILE_PTR(P.gl, P.n_costs * nz), TILE_PTR(P.cp, P.n_cp), TILE_PTR(P.cl, P.n_cl), dt_lane(P, b));
 }

@@ -56,7 +56,7 @@ struct PolicyKnot {
 // GW (a handle with per-trajectory cost weights, DevProblem::gw): the weights of sample c's trajectory b; gw0 = its pointer to entry 0
 template <class M, bool DT, bool GW = false>
 __device__ __forceinline__ double policy_knot_cost(const DevProblem& P, int k, const double* x, const double* u, const double* gl0, const double* cp0,
-                                                   [[maybe_unused]] const double* dt0, [[maybe_unused]] const double* gw0 = nullptr) {
+                                                   [[maybe_unused]] const double* dt0, [[maybe_unused]] CostLane gw0 = CostLane{nullptr, nullptr}) {
   if constexpr (GW) {
     if constexpr (DT) return knot_cost<M, true>(P, k, x, u, nullptr, nullptr, false, gl0, cp0, nullptr, dt0, gw0);
     else return knot_cost<M, true>(P, k, x, u, nullptr, nullptr, false, gl0, cp0, nullptr, nullptr, gw0);
@@ -97,7 +97,7 @@ __global__ void __launch_bounds__(64) k_policy_rollout(KArgs a, PolicyArgs pa) {
   const double* cp0 = TILE_PTR(P.cp, P.n_cp);
   const double* cl0 = TILE_PTR(P.cl, P.n_cl);
   const double* dt0 = dt_lane_of<DT>(P, b);
-  [[maybe_unused]] const double* gw0 = GW ? TILE_PTR(P.gw, P.n_costs * (n + m)) : nullptr;  // (by the trajectory b, like gl0)
+  [[maybe_unused]] const CostLane gw0 = GW ? cost_lane<n + m>(P, tile, lane) : CostLane{nullptr, nullptr};  // (by the trajectory b, like gl0; weights and attitude references)
   double mp[16];  // the PLANT's parameters; the law's x̄, ū, K, d are the planning model's
   if constexpr (LANE_PLANT) {
     const double* pp = pa.plants + c * 16;

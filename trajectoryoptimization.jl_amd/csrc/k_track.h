@@ -16,6 +16,11 @@
 //   diagonal kinds:  delta = (-(Q_i x_i)) - c.q[i]
 //   QUADRATIC:       acc = Q[i,0] x_0;  acc = acc + Q[i,j] x_j  for ascending j;  delta = (-acc) - c.q[i]
 // and the same with R, u, c.r for the control rows, which are not written at all while the reference has no controls.
+//
+// Attitude rows (to_set_tracking_attitude; TrackArgs::ga set): behind the linear rows the same launch takes N * 4 more rows, (knot k, entry i of
+// q_ref).  Where the knot's cost is a DiagonalQuatCost, row 4 ci + i of DevProblem::ga gets x_ref[j][q_ind[i] - 1] — an exact copy, j the
+// reference knot of the linear rows (the clamp included), the row stored whole like a row of gl; costs of other kinds are not touched.  With
+// ga null the kernel has the rows it always had.
 // Non-template: included from trajopt_hip.hip only (and, through the host shim, from tests/host_shim/track_lower_harness.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -35,19 +40,33 @@ struct TrackArgs {
   IntC* cost_index;    // [N]
   CostC* costs;        // [n_costs]
   double* gl;          // tiled, L = n_costs (n + m)
+  double* ga;          // tiled, L = 4 n_costs: DevProblem::ga while attitude tracking is on, else null (no attitude rows)
 };
 
 // grid (tiles, row groups): workgroup (x, y) takes the rows y, y + gridDim.y, ... of tile x, a row being (knot k, entry i of [q; r] — of q alone
-// without controls).  Lanes behind the batch store nothing.
+// without controls), followed by the attitude rows (knot k, entry i of q_ref) while a.ga is set.  Lanes behind the batch store nothing.
 __global__ void __launch_bounds__(64) k_track_lower(TrackArgs a) {
 #pragma clang fp contract(off)
   const int lane = threadIdx.x, tile = blockIdx.x, b = tile * 64 + lane;
   if (b >= a.B) return;
   const int n = a.n, m = a.m, nz = n + m, per = a.with_u ? nz : n, rows = a.N * per, last = a.Nref - 1;
+  const int all = rows + (a.ga != nullptr ? a.N * 4 : 0);
   const int j0 = a.start[b] - 1;
   const double* ref = a.ref + ((size_t)tile * (size_t)(a.Nref * nz)) * 64 + lane;
   double* gl = a.gl + ((size_t)tile * (size_t)(a.n_costs * nz)) * 64 + lane;
-  for (int e = blockIdx.y; e < rows; e += gridDim.y) {
+  for (int e = blockIdx.y; e < all; e += gridDim.y) {
+    if (e >= rows) {  // an attitude row (wave-uniform: e is)
+      const int k = (e - rows) >> 2, i = (e - rows) & 3;
+      int j = j0 + k;
+      j = j < last ? j : last;
+      j = j > 0 ? j : 0;
+      const int ci = a.cost_index[k];
+      CostC& c = a.costs[ci];
+      if (c.kind != TO_COST_DIAGONAL_QUAT) continue;
+      const int src = c.q_ind[i] - 1;  // (1 <= q_ind <= n: desc_lower.h validate_cost)
+      (a.ga + ((size_t)tile * (size_t)(a.n_costs * 4)) * 64 + lane)[(size_t)(ci * 4 + i) * 64] = ref[((size_t)j * nz + src) * 64];
+      continue;
+    }
     const int k = e / per, i = e - k * per;
     int j = j0 + k;          // this lane's reference knot; the host has checked the window, the clamp keeps every read inside the block
     j = j < last ? j : last;

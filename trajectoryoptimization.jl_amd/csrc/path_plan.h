@@ -269,6 +269,37 @@ struct TableFlags {
   bool time_steps = false;                                       // DevProblem::dtb set
   bool cost_weights = false;                                     // DevProblem::gw set
 };
+// How ga rides on gw.  Three reasons keep the pair of arrays set: the CALLER set weights (to_set_cost_weights_batch), the caller
+// set attitudes (to_set_cost_attitude_batch), attitude tracking is on (to_set_tracking_attitude).  While any holds, DevProblem::gw AND ga are
+// set — gw on the descriptors' diagonals unless the caller gave weights, ga on the descriptors' q_ref unless attitudes were given — and the
+// handle is routed as one with weights; when the last one goes, both pointers return to null and the handle to the kernel variants it ran before.
+// The tracking / weights refusals look at `weights` alone: attitude references with gw on the descriptors refuse neither.
+struct CostLaneState {
+  bool weights = false, attitude = false, track_attitude = false;
+  bool routed() const { return weights || attitude || track_attitude; }  // DevProblem::gw / ga are set
+};
+// what a transition asks of the device arrays
+struct CostLaneAction {
+  bool fill_gw = false;   // gw (host copy and device) starts from every cost's descriptor
+  bool fill_ga = false;   // ga likewise
+  bool release = false;   // both pointers back to null
+};
+enum CostLaneEvent { LANE_SET_WEIGHTS, LANE_CLEAR_WEIGHTS, LANE_SET_ATTITUDE, LANE_CLEAR_ATTITUDE, LANE_TRACK_ON, LANE_TRACK_OFF };
+inline CostLaneAction cost_lane_step(CostLaneState* s, CostLaneEvent e) {
+  CostLaneAction a;
+  const bool was = s->routed();
+  switch (e) {
+    case LANE_SET_WEIGHTS: s->weights = true; break;
+    case LANE_SET_ATTITUDE: s->attitude = true; break;
+    case LANE_TRACK_ON: s->track_attitude = true; break;
+    case LANE_CLEAR_WEIGHTS: a.fill_gw = s->weights; s->weights = false; break;          // (what stays routed runs on the descriptors' diagonals)
+    case LANE_CLEAR_ATTITUDE: a.fill_ga = s->attitude || s->track_attitude; s->attitude = false; break;  // every cost's q_ref; a tracking lowering follows while that mode is on
+    case LANE_TRACK_OFF: s->track_attitude = false; break;                              // (the caller restarts the tracked costs' rows)
+  }
+  if (!was && s->routed()) a.fill_gw = a.fill_ga = true;   // first use: both arrays from the descriptors
+  if (was && !s->routed()) { a = CostLaneAction{}; a.release = true; }
+  return a;
+}
 inline bool routed_as_plants(bool plants /* pm */, bool time_steps /* dtb */) { return plants || time_steps; }
 inline bool routed_as_plants(const TableFlags& f) { return routed_as_plants(f.plants, f.time_steps); }
 inline int expand_variant_of(const TableFlags& f) {

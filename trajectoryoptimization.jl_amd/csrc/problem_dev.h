@@ -86,6 +86,12 @@ struct DevProblem {
   // default): every trajectory shares the descriptors.  Read by the GW instances of the general kernel variants only (cost_weights below,
   // DESIGN.md §1e).
   const double* gw;
+  // Per-trajectory attitude references (to_set_cost_attitude_batch / to_set_tracking_attitude: one q_ref per trajectory for a DiagonalQuatCost):
+  // tiled like gw, L = 4 * n_costs; row 4*ci + i of trajectory b sits at ga[((b >> 6) * L + 4*ci + i) * 64 + (b & 63)] and holds the VALUE of
+  // q_ref[i] of cost ci, in the descriptor's order (the state entries q_ind[0..3]).  Filled with every cost's descriptor values on first use.  It
+  // rides on gw (as dtb rides on pm): ga and gw are set and cleared TOGETHER — gw holding the descriptors' diagonals while the caller gave no
+  // weights — and the GW kernel instances read both (cost_qref below); no other instance looks at this pointer.
+  const double* ga;
 };
 
 // The 16 model parameters of trajectory b into registers (the flagged kernel instances, once, ahead of their knot loops): indexed by the
@@ -281,19 +287,33 @@ __device__ __forceinline__ void errquad_grad(CostC& C, const T* x, T* g /*n*/) {
 // products with other sums, and a handle without weights must keep its bits (tests/test_gpu_cost_weights_unflagged.py).  The forward
 // translation units are compiled with -ffp-contract=on, which fuses per source expression whatever the blocks look like: there the general
 // variants pick between the two calls on DevProblem::gw, a kernel argument (k_forward.h).
+// CostLane: what a GW instance hands down in w's place — the lane's pointer into gw and, next to it, the one into DevProblem::ga (the
+// per-trajectory attitude references, which ride on the same instances): both at entry 0 of the whole arrays (cost_lane) or at the block of one
+// cost (cost_block in common.h, cost_weights).  cost_qref: q_ref[i] of a DiagonalQuatCost the same way — the descriptor's for the callers that
+// pass nothing, the trajectory's own for a GW instance; there is no run-time test of either pointer inside an instance.
+struct CostLane { const double* w; const double* a; };
 __device__ __forceinline__ double cost_wq(CostC& C, int i, std::nullptr_t) { return C.Q[i]; }
-__device__ __forceinline__ double cost_wq(CostC&, int i, const double* w) { return w[(size_t)i * 64]; }
+__device__ __forceinline__ double cost_wq(CostC&, int i, CostLane l) { return l.w[(size_t)i * 64]; }
 template <int n> __device__ __forceinline__ double cost_wr(CostC& C, int j, std::nullptr_t) { return C.R[j]; }
-template <int n> __device__ __forceinline__ double cost_wr(CostC&, int j, const double* w) { return w[(size_t)(n + j) * 64]; }
-// the lane's pointer to the block of cost ci (tile, lane: of the trajectory; nz = n + m)
+template <int n> __device__ __forceinline__ double cost_wr(CostC&, int j, CostLane l) { return l.w[(size_t)(n + j) * 64]; }
+__device__ __forceinline__ double cost_qref(CostC& C, int i, std::nullptr_t) { return C.q_ref[i]; }
+__device__ __forceinline__ double cost_qref(CostC&, int i, CostLane l) { return l.a[(size_t)i * 64]; }
+// the lane's pointers to entry 0 of gw / ga (tile, lane: of the trajectory; nz = n + m) ...
 template <int nz>
-__device__ __forceinline__ const double* cost_weights(const DevProblem& P, int tile, int lane, int ci) {
-  return P.gw + ((size_t)tile * (size_t)(P.n_costs * nz) + (size_t)ci * nz) * 64 + lane;
+__device__ __forceinline__ CostLane cost_lane(const DevProblem& P, int tile, int lane) {
+  return CostLane{P.gw + ((size_t)tile * (size_t)(P.n_costs * nz)) * 64 + lane, P.ga + ((size_t)tile * (size_t)(P.n_costs * 4)) * 64 + lane};
+}
+// ... and to the blocks of cost ci
+template <int nz>
+__device__ __forceinline__ CostLane cost_weights(const DevProblem& P, int tile, int lane, int ci) {
+  const CostLane l = cost_lane<nz>(P, tile, lane);
+  return CostLane{l.w + (size_t)ci * nz * 64, l.a + (size_t)ci * 4 * 64};
 }
 
 // ------------------------------------------------------------------------------------------------ costs
 // J = ½x'Qx + q'x + c (+ ½u'Ru + r'u whenever u is given) (+ u'Hx) (+ w·min(1±dq))
-// gw (here and in cost_grad_hvp): see cost_wq — the diagonal kinds read their Q and R through it; the dense kinds have no per-trajectory weights
+// gw (here and in cost_grad_hvp): see cost_wq / cost_qref — the diagonal kinds read their Q, R and q_ref through it; the dense kinds have no
+// per-trajectory weights
 template <int n, int m, bool DENSE = true, class W = std::nullptr_t>
 __device__ __forceinline__ double cost_eval(CostC& C, const double* x, const double* u, W gw = nullptr) {
   double J;
@@ -352,7 +372,7 @@ __device__ __forceinline__ double cost_eval(CostC& C, const double* x, const dou
     }
   }
   if (C.kind == TO_COST_DIAGONAL_QUAT) {
-    const double qr[4] = {C.q_ref[0], C.q_ref[1], C.q_ref[2], C.q_ref[3]};
+    const double qr[4] = {cost_qref(C, 0, gw), cost_qref(C, 1, gw), cost_qref(C, 2, gw), cost_qref(C, 3, gw)};
     const int qi[4] = {C.q_ind[0], C.q_ind[1], C.q_ind[2], C.q_ind[3]};
     const double dq = quat_dot<n>(qr, qi, x);
     J += C.w * fmin(1 + dq, 1 - dq);
@@ -488,7 +508,7 @@ __device__ __forceinline__ void cost_grad_hvp(CostC& C, const double* x, const d
     for (int i = 0; i < n; ++i) { g[i] = cost_wq(C, i, gw) * x[i] + C.q[i]; y[i] = cost_wq(C, i, gw) * v[i]; }
   }
   if (C.kind == TO_COST_DIAGONAL_QUAT) {  // the intended gradient src/lie_costs.jl:82-90
-    const double qr[4] = {C.q_ref[0], C.q_ref[1], C.q_ref[2], C.q_ref[3]};
+    const double qr[4] = {cost_qref(C, 0, gw), cost_qref(C, 1, gw), cost_qref(C, 2, gw), cost_qref(C, 3, gw)};
     const int qi[4] = {C.q_ind[0], C.q_ind[1], C.q_ind[2], C.q_ind[3]};
     const double dq = quat_dot<n>(qr, qi, x);
     bool fast = false;

@@ -1234,6 +1234,35 @@ static int upload_cost_weights(to_handle* h) {
   HIPCHECK(hipStreamSynchronize(h->stream));
   return TO_OK;
 }
+// DevProblem::ga from every cost's descriptor, tiled on the host, in one copy (first use; the clears that keep the handle routed).  From then on the
+// device array is the truth — k_track_lower writes it — and one cost's four rows move at a time (restart_cost_attitude, the setter, the getter).
+static int upload_cost_attitudes(to_handle* h) {
+  DevProblem& P = h->a.P;
+  std::vector<double> values, tiled;
+  cost_attitude_fill(P.B, h->costs.data(), (int)h->costs.size(), &values);
+  cost_attitude_tile(P.B, P.Bp, h->costs.data(), (int)h->costs.size(), values, &tiled);
+  if (!h->d_ga) TRY(dev_alloc(h, &h->d_ga, tiled.size()));
+  HIPCHECK(hipMemcpyAsync(h->d_ga, tiled.data(), tiled.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  HIPCHECK(hipStreamSynchronize(h->stream));
+  return TO_OK;
+}
+static int restart_cost_attitude(to_handle* h, int id) {
+  std::vector<double> rows;
+  cost_attitude_rows(h->a.P.B, h->costs[id], &rows);
+  return upload_vec(h, rows.data(), h->d_ga, 4, 4 * (int)h->costs.size(), 4 * id);
+}
+// what a transition of to_handle::lane (path_plan.h cost_lane_step) asks of gw / ga; leaves both pointers as the state says
+static int cost_lane_apply(to_handle* h, const CostLaneAction& act) {
+  DevProblem& P = h->a.P;
+  if (act.release || !h->lane.routed()) { P.gw = nullptr; P.ga = nullptr; h->gw_host.clear(); return TO_OK; }
+  if (act.fill_gw) {
+    cost_weights_fill(P.n, P.m, P.B, h->costs.data(), (int)h->costs.size(), &h->gw_host);
+    TRY(upload_cost_weights(h));
+  }
+  if (act.fill_ga) TRY(upload_cost_attitudes(h));
+  P.gw = h->d_gw; P.ga = h->d_ga;
+  return TO_OK;
+}
 int to_set_cost(to_handle* h, int32_t id, const to_cost_desc* c) {
   CHECK_H(h); CHECK_IDLE(h); CHECK_P(c); TRY(use_device(h));
   if (id < 0 || id >= (int)h->costs.size()) return fail(TO_ERR_ARGUMENT, "cost id out of range");
@@ -1251,6 +1280,7 @@ int to_set_cost(to_handle* h, int32_t id, const to_cost_desc* c) {
   if (h->a.P.gw) {  // ... and so do its per-trajectory weights: the new descriptor's diagonal for every trajectory (the other costs keep theirs)
     cost_weights_restart(h->a.P.n, h->a.P.m, h->a.P.B, h->costs.data(), (int)h->costs.size(), id, &h->gw_host);
     TRY(upload_cost_weights(h));
+    TRY(restart_cost_attitude(h, id));  // ... and its per-trajectory q_ref (DevProblem::ga is set whenever gw is)
   }
   return upload_tables(h);
 }
@@ -1519,10 +1549,9 @@ int to_set_cost_weights_batch(to_handle* h, int32_t cost_id, const double* Q, co
   TRY(validate_cost_weights(h ? &f : nullptr, cost_id, Q, R));  // every refusal, before any device call and before anything changes
   TRY(use_device(h));
   DevProblem& P = h->a.P;
-  if (h->gw_host.empty()) cost_weights_fill(P.n, P.m, P.B, h->costs.data(), (int)h->costs.size(), &h->gw_host);
+  TRY(cost_lane_apply(h, cost_lane_step(&h->lane, LANE_SET_WEIGHTS)));  // first use: gw and ga from the descriptors (gw may already stand, behind attitude references)
   cost_weights_store(P.n, P.m, P.B, (int)h->costs.size(), cost_id, Q, R, &h->gw_host);
   TRY(upload_cost_weights(h));
-  P.gw = h->d_gw;
   TRY(upload_tables(h));  // (expand_variant bit 2, and with it the compact cost block, follow gw)
   return check_guards(h, "to_set_cost_weights_batch");
 }
@@ -1546,9 +1575,43 @@ int to_clear_cost_weights_batch(to_handle* h) {
   if (h) f = cost_weight_facts(h);
   TRY(validate_cost_weights_target("to_clear_cost_weights_batch", h ? &f : nullptr, -1, true));
   TRY(use_device(h));
-  h->a.P.gw = nullptr;
-  h->gw_host.clear();
-  return upload_tables(h);  // every cost on its descriptor, the kernel variants the handle ran before
+  // every cost on its descriptor's weights; the kernel variants the handle ran before unless attitude references keep it routed (gw then holds the
+  // descriptors' diagonals again)
+  TRY(cost_lane_apply(h, cost_lane_step(&h->lane, LANE_CLEAR_WEIGHTS)));
+  return upload_tables(h);
+}
+
+// One reference quaternion per TRAJECTORY for the DiagonalQuatCost cost_id (DevProblem::ga; desc_lower.h has every refusal and the image of the
+// array, path_plan.h cost_lane_step the rules by which ga rides on gw).  The setter moves the four rows of its cost and nothing else.
+int to_set_cost_attitude_batch(to_handle* h, int32_t cost_id, const double* q_ref) {
+  CostWeightFacts f;
+  if (h) f = cost_weight_facts(h);
+  TRY(validate_cost_attitude(h ? &f : nullptr, cost_id, q_ref));  // every refusal, before any device call and before anything changes
+  TRY(use_device(h));
+  TRY(cost_lane_apply(h, cost_lane_step(&h->lane, LANE_SET_ATTITUDE)));
+  TRY(upload_vec(h, q_ref, h->d_ga, 4, 4 * (int)h->costs.size(), 4 * cost_id));
+  TRY(upload_tables(h));  // (routed as a handle with weights)
+  return check_guards(h, "to_set_cost_attitude_batch");
+}
+int to_get_cost_attitude_batch(to_handle* h, int32_t cost_id, double* q_ref) {
+  CostWeightFacts f;
+  if (h) f = cost_weight_facts(h);
+  TRY(validate_cost_attitude_get(h ? &f : nullptr, cost_id, q_ref));
+  if (h->a.P.ga) {  // what every trajectory is evaluated with: the device rows (the setter's, or a tracking window's) ...
+    TRY(use_device(h));
+    return download_vec(h, q_ref, h->d_ga, 4, 4 * (int)h->costs.size(), 4 * cost_id);
+  }
+  for (int b = 0; b < h->a.P.B; ++b)  // ... or the descriptor's q_ref repeated
+    for (int i = 0; i < 4; ++i) q_ref[i + (size_t)4 * b] = h->costs[cost_id].q_ref[i];
+  return TO_OK;
+}
+int to_clear_cost_attitude_batch(to_handle* h) {
+  CostWeightFacts f;
+  if (h) f = cost_weight_facts(h);
+  TRY(validate_cost_weights_target("to_clear_cost_attitude_batch", h ? &f : nullptr, -1, true));
+  TRY(use_device(h));
+  TRY(cost_lane_apply(h, cost_lane_step(&h->lane, LANE_CLEAR_ATTITUDE)));  // (attitude tracking, while on, writes its rows again with the next lowering)
+  return upload_tables(h);
 }
 
 // One set of time steps per TRAJECTORY (DevProblem::dtb): dt[(N-1), B], knot fastest.  Validation and tiling are host-only code
@@ -1926,7 +1989,7 @@ int to_mpc_advance(to_handle* h, const double* x_meas, const to_mpc_opts* mpc, c
 static TrackFacts track_facts(const to_handle* h) {
   const DevProblem& P = h->a.P;
   return TrackFacts{h->model_key, model_key_name(h->model_key), P.n, P.m, P.N, P.B, h->costs.data(), (int)h->costs.size(), h->cost_index.data(),
-                    h->inflight.load(), h->track_Nref, h->track_end, P.gw != nullptr};
+                    h->inflight.load(), h->track_Nref, h->track_end, h->lane.weights};
 }
 // the stored starts -> the device, then all N knots of every trajectory into d_gl from the current descriptors (one launch)
 static int track_lower(to_handle* h, const char* who) {
@@ -1940,7 +2003,8 @@ static int track_lower(to_handle* h, const char* who) {
   TrackArgs ta;
   ta.n = P.n; ta.m = P.m; ta.N = P.N; ta.B = P.B; ta.Nref = h->track_Nref; ta.with_u = h->track_u ? 1 : 0; ta.n_costs = (int)h->costs.size();
   ta.ref = h->d_track_ref; ta.start = h->d_track_start; ta.cost_index = P.cost_index; ta.costs = P.costs; ta.gl = h->d_gl;
-  const int rows = P.N * (h->track_u ? nz : P.n);
+  ta.ga = h->lane.track_attitude ? h->d_ga : nullptr;  // attitude tracking: the same launch writes the q_ref rows of the DiagonalQuatCost knots
+  const int rows = P.N * (h->track_u ? nz : P.n) + (ta.ga ? P.N * 4 : 0);
   TRY(launch(k_track_lower, dim3((unsigned)(P.Bp / 64), (unsigned)std::min(rows, 32)), dim3(BLOCK), 0, h->stream, ta));
   HIPCHECK(hipStreamSynchronize(h->stream));
   P.gl = h->d_gl;
@@ -1979,8 +2043,34 @@ int to_get_tracking_window(to_handle* h, int32_t* Nref, int32_t* end_mode, int32
   if (start) for (int b = 0; b < h->a.P.B; ++b) start[b] = h->track_Nref ? h->track_start[b] : 1;
   return TO_OK;
 }
+// attitude tracking off: the tracked costs' q_ref back on their descriptors.  Without setter calls of the caller's the whole array is filled again
+// in one copy (a tracking objective has a cost per knot: every cost in use is a tracked one); next to them only the tracked DiagonalQuatCosts
+// restart, four rows at a time, and a cost outside the window keeps what the caller gave it
+static int tracking_attitude_off(to_handle* h) {
+  if (!h->lane.track_attitude) return TO_OK;
+  if (!h->lane.attitude) TRY(upload_cost_attitudes(h));
+  else for (int k = 0; k < h->a.P.N; ++k) if (h->costs[h->cost_index[k]].kind == TO_COST_DIAGONAL_QUAT) TRY(restart_cost_attitude(h, h->cost_index[k]));
+  TRY(cost_lane_apply(h, cost_lane_step(&h->lane, LANE_TRACK_OFF)));
+  return upload_tables(h);
+}
+int to_set_tracking_attitude(to_handle* h, int32_t on) {
+  TrackFacts f;
+  if (h) f = track_facts(h);
+  TRY(validate_tracking_attitude(h ? &f : nullptr, on));
+  TRY(use_device(h));
+  if (!on) return tracking_attitude_off(h);
+  TRY(cost_lane_apply(h, cost_lane_step(&h->lane, LANE_TRACK_ON)));
+  TRY(upload_tables(h));
+  return track_lower(h, "to_set_tracking_attitude");
+}
+int to_get_tracking_attitude(to_handle* h, int32_t* on) {
+  CHECK_H(h); CHECK_P(on);
+  *on = h->lane.track_attitude ? 1 : 0;
+  return TO_OK;
+}
 int to_clear_tracking_reference_batch(to_handle* h) {
   CHECK_H(h); CHECK_IDLE(h); TRY(use_device(h));
+  TRY(tracking_attitude_off(h));
   dev_release(h, &h->d_track_ref);
   dev_release(h, &h->d_track_start);
   h->track_start.clear();
