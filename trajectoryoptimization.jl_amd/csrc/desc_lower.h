@@ -4,6 +4,7 @@
 // (tests/host_shim/pn_harness.cpp).  Mirrors the reference's constructors: Problem src/problem.jl:44-72, add_constraint!
 // src/constraint_list.jl:103-134, BoundConstraint src/constraints.jl:660-687, NormConstraint :442-455.
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <string>
@@ -216,6 +217,22 @@ inline int validate_constraint(int n, int m, int N, const to_constraint_desc& d,
   return TO_OK;
 }
 
+// THE host image of the per-trajectory tables that carry a spare tile (DevProblem::pm, dtb, cl, gw, ga; handle.h names the other family).
+// values[L, B], row fastest, one column per trajectory -> entry e of trajectory b at tiled[((b >> 6) * L + e) * 64 + (b & 63)], the address every
+// kernel forms: Bp / 64 tiles and one spare tile (like the nominal states).  Every lane behind the batch, and the whole spare tile, holds the
+// SHARED value of its row, shared[L] (idle lanes compute along on valid data).  values == NULL: the shared row for every trajectory.
+inline size_t tiled_len(size_t L, int Bp) { return ((size_t)Bp / 64 + 1) * L * 64; }
+inline void tile_rows(size_t L, int B, int Bp, const double* values, const double* shared, std::vector<double>* tiled) {
+  const size_t tiles = (size_t)Bp / 64 + 1;
+  tiled->resize(tiled_len(L, Bp));
+  for (size_t t = 0; t < tiles; ++t)
+    for (size_t e = 0; e < L; ++e)
+      for (int l = 0; l < 64; ++l) {
+        const size_t b = t * 64 + l;
+        (*tiled)[(t * L + e) * 64 + l] = (values && b < (size_t)B) ? values[L * b + e] : shared[e];
+      }
+}
+
 // Per-trajectory limits of a selector constraint (to_set_constraint_limits_batch).  constraint_limits_q: the number of values per
 // trajectory — p for a BoundConstraint (one per finite row, in row order), 1 for a second-order-cone NormConstraint (the value of its last
 // row) — or the refusal for every other kind.  lower_constraint_limits: limits[q, B] -> the values of soff[r] for every row, rows[p, B]
@@ -256,6 +273,35 @@ inline int lower_constraint_limits(const DevCon& ci, int B, const double* limits
 // the descriptor's own limits in the layout of the setter's argument (what the getter reports for a constraint on shared limits)
 inline void shared_constraint_limits(const DevCon& ci, int q, double* out) {
   for (int i = 0; i < q; ++i) out[i] = ci.soff[q == 1 && ci.d.kind == TO_CON_NORM ? ci.p - 1 : i];
+}
+// The table behind DevProblem::cl holds the rows of EVERY constraint, L = n_cl = their summed p.  constraint_limits_bases: the first row of every
+// constraint's block (returns n_cl); constraint_limits_shared: the shared row, every constraint's soff[0 .. p) at its base; constraint_limits_values:
+// values[n_cl, B] for tile_rows — the block of a constraint that was given limits (given[i], [q, B], not empty) through lower_constraint_limits,
+// the block of every other one on its soff.
+inline int constraint_limits_bases(const std::vector<DevCon>& cons, std::vector<int>* base) {
+  base->assign(cons.size(), 0);
+  int L = 0;
+  for (size_t i = 0; i < cons.size(); ++i) { (*base)[i] = L; L += cons[i].p; }
+  return L;
+}
+inline void constraint_limits_shared(const std::vector<DevCon>& cons, const std::vector<int>& base, int n_cl, std::vector<double>* shared) {
+  shared->assign((size_t)n_cl, 0.0);
+  for (size_t i = 0; i < cons.size(); ++i)
+    for (int r = 0; r < cons[i].p; ++r) (*shared)[base[i] + r] = cons[i].soff[r];
+}
+inline int constraint_limits_values(const std::vector<DevCon>& cons, const std::vector<std::vector<double>>& given, const std::vector<int>& base,
+                                    const std::vector<double>& shared, int B, std::vector<double>* values) {
+  const size_t n_cl = shared.size();
+  values->resize(n_cl * B);
+  for (int b = 0; b < B; ++b) std::copy(shared.begin(), shared.end(), values->begin() + n_cl * b);
+  std::vector<double> rows;
+  for (size_t i = 0; i < cons.size(); ++i) {
+    if (given[i].empty()) continue;
+    const int p = cons[i].p;
+    if (int r = lower_constraint_limits(cons[i], B, given[i].data(), &rows)) return r;
+    for (int b = 0; b < B; ++b) std::copy(rows.begin() + (size_t)p * b, rows.begin() + (size_t)p * (b + 1), values->begin() + n_cl * b + base[i]);
+  }
+  return TO_OK;
 }
 
 // One tracking reference per trajectory (to_set_tracking_reference_batch / to_set_tracking_window): every refusal of the two entry points,
@@ -340,12 +386,10 @@ inline void pack_tracking_reference(int n, int m, int B, int Nref, const double*
 }
 
 // Per-trajectory time steps (to_set_time_steps_batch): dt[(N-1), B], knot fastest, column b read exactly like to_problem_desc::dt.
-// lower_time_steps checks every value — finite and > 0, the check the descriptor's own steps get at to_create; there is NO "must sum to
-// tf - t0" check: trajectory b ends at its own tf_b = t0 + sum_k dt_b[k] — and tiles them the way DevProblem::dtb is read: step k of
-// trajectory b at tiled[((b >> 6) * (N - 1) + k) * 64 + (b & 63)], Bp / 64 tiles and one spare tile (like the nominal states and
-// DevProblem::pm); the lanes behind the batch and the spare tile carry the SHARED steps (idle lanes compute along on valid data).
-inline size_t time_steps_tiled_len(int N, int Bp) { return ((size_t)Bp / 64 + 1) * (size_t)(N - 1) * 64; }
-inline int lower_time_steps(int N, int B, int Bp, const double* dt, const double* shared /* [N-1] */, std::vector<double>* tiled) {
+// validate_time_steps checks every value — finite and > 0, the check the descriptor's own steps get at to_create; there is NO "must sum to
+// tf - t0" check: trajectory b ends at its own tf_b = t0 + sum_k dt_b[k].  lower_time_steps: the checks, then the image of DevProblem::dtb
+// (tile_rows with L = N - 1; the shared row: the descriptor's steps); a refused call leaves the output untouched.
+inline int validate_time_steps(int N, int B, const double* dt) {
   const int L = N - 1;
   for (int b = 0; b < B; ++b)
     for (int k = 0; k < L; ++k) {
@@ -354,14 +398,12 @@ inline int lower_time_steps(int N, int B, int Bp, const double* dt, const double
         return fail(TO_ERR_ARGUMENT, "to_set_time_steps_batch: time step " + std::to_string(k) + " of trajectory " + std::to_string(b) +
                                          (std::isfinite(v) ? " is not > 0" : " is not finite"));
     }
-  const size_t tiles = (size_t)Bp / 64 + 1;
-  tiled->assign(time_steps_tiled_len(N, Bp), 0.0);
-  for (size_t t = 0; t < tiles; ++t)
-    for (int k = 0; k < L; ++k)
-      for (int l = 0; l < 64; ++l) {
-        const size_t b = t * 64 + l;
-        (*tiled)[(t * L + k) * 64 + l] = b < (size_t)B ? dt[k + (size_t)L * b] : shared[k];
-      }
+  return TO_OK;
+}
+inline size_t time_steps_tiled_len(int N, int Bp) { return tiled_len((size_t)N - 1, Bp); }
+inline int lower_time_steps(int N, int B, int Bp, const double* dt, const double* shared /* [N-1] */, std::vector<double>* tiled) {
+  if (int r = validate_time_steps(N, B, dt)) return r;
+  tile_rows((size_t)N - 1, B, Bp, dt, shared, tiled);
   return TO_OK;
 }
 
@@ -424,9 +466,9 @@ inline int validate_cost_weights_get(const CostWeightFacts* f, int32_t cost_id, 
 }
 // The host copy behind DevProblem::gw: values[L, B] with L = n_costs (n + m), row ci (n + m) + i of column b = Q_i (i < n) / R_{i-n} of cost ci
 // as trajectory b is evaluated with it.  cost_weights_fill: every cost's descriptor values (first use; cost_weights_restart: one cost's rows
-// again, behind to_set_cost); cost_weights_store: the setter's Q / R into one cost's rows; cost_weights_tile: the device layout — entry e of
-// trajectory b at tiled[((b >> 6) L + e) 64 + (b & 63)], Bp / 64 tiles and one spare; the lanes behind the batch carry the descriptors' values
-// (idle lanes compute along on valid data).  A dense cost's rows are never read; they hold the leading entries of its arrays.
+// again, behind to_set_cost); cost_weights_store: the setter's Q / R into one cost's rows; cost_weights_shared: the shared row of the device
+// image (tile_rows) — the descriptors' diagonals, one column of what cost_weights_fill writes.  A dense cost's rows are never read; they hold the
+// leading entries of its arrays.
 inline void cost_weights_restart(int n, int m, int B, const to_cost_desc* costs, int n_costs, int ci, std::vector<double>* values) {
   const int nz = n + m;
   const size_t L = (size_t)n_costs * nz;
@@ -449,20 +491,15 @@ inline void cost_weights_store(int n, int m, int B, int n_costs, int ci, const d
     for (int j = 0; R && j < m; ++j) v[n + j] = R[j + (size_t)m * b];
   }
 }
-inline size_t cost_weights_tiled_len(int n, int m, int n_costs, int Bp) { return ((size_t)Bp / 64 + 1) * (size_t)n_costs * (n + m) * 64; }
+inline void cost_weights_shared(int n, int m, const to_cost_desc* costs, int n_costs, std::vector<double>* shared) {
+  cost_weights_fill(n, m, 1, costs, n_costs, shared);
+}
+// the image as one call (what tests/host_shim/cost_weights_harness.cpp checks lane by lane): the shared row, then tile_rows
+inline size_t cost_weights_tiled_len(int n, int m, int n_costs, int Bp) { return tiled_len((size_t)n_costs * (n + m), Bp); }
 inline void cost_weights_tile(int n, int m, int B, int Bp, const to_cost_desc* costs, int n_costs, const std::vector<double>& values, std::vector<double>* tiled) {
-  const int nz = n + m;
-  const size_t L = (size_t)n_costs * nz, tiles = (size_t)Bp / 64 + 1;
-  tiled->assign(cost_weights_tiled_len(n, m, n_costs, Bp), 0.0);
-  for (size_t t = 0; t < tiles; ++t)
-    for (size_t e = 0; e < L; ++e) {
-      const int ci = (int)(e / nz), i = (int)(e % nz);
-      const double shared = i < n ? costs[ci].Q[i] : costs[ci].R[i - n];
-      for (int l = 0; l < 64; ++l) {
-        const size_t b = t * 64 + l;
-        (*tiled)[(t * L + e) * 64 + l] = b < (size_t)B ? values[L * b + e] : shared;
-      }
-    }
+  std::vector<double> shared;
+  cost_weights_shared(n, m, costs, n_costs, &shared);
+  tile_rows(shared.size(), B, Bp, values.data(), shared.data(), tiled);
 }
 
 // Per-trajectory attitude references (to_set_cost_attitude_batch / to_get_... / to_clear_..., to_set_tracking_attitude): every refusal, decided from
@@ -510,10 +547,9 @@ inline int validate_tracking_attitude(const TrackFacts* f, int32_t on) {
 }
 // The image of DevProblem::ga: L = 4 n_costs rows per trajectory, row 4 ci + i = q_ref[i] of cost ci (a cost of another kind carries its
 // descriptor's q_ref slot, which is never read).  cost_attitude_fill: every cost's descriptor values as a host array [L, B] (first use);
-// cost_attitude_rows: one cost's rows alone, [4, B] (to_set_cost, the clears); cost_attitude_tile: the device layout of cost_weights_tile —
-// entry e of trajectory b at tiled[((b >> 6) L + e) 64 + (b & 63)], Bp / 64 tiles and one spare, the lanes behind the batch on the descriptors'
-// values.  After the first upload the DEVICE array is the truth (k_track_lower writes it): the setter, the getter and the restarts move one
-// cost's four rows and nothing else.
+// cost_attitude_rows: one cost's rows alone, [4, B] (to_set_cost, the clears); cost_attitude_shared: the shared row of the device image
+// (tile_rows), one column of what cost_attitude_fill writes — the library's uploads are that row for every trajectory.  After the first upload the
+// DEVICE array is the truth (k_track_lower writes it): the setter, the getter and the restarts move one cost's four rows and nothing else.
 inline void cost_attitude_rows(int B, const to_cost_desc& c, std::vector<double>* rows) {
   rows->resize((size_t)4 * B);
   for (int b = 0; b < B; ++b)
@@ -526,16 +562,13 @@ inline void cost_attitude_fill(int B, const to_cost_desc* costs, int n_costs, st
     for (int ci = 0; ci < n_costs; ++ci)
       for (int i = 0; i < 4; ++i) (*values)[L * b + 4 * ci + i] = costs[ci].q_ref[i];
 }
-inline size_t cost_attitude_tiled_len(int n_costs, int Bp) { return ((size_t)Bp / 64 + 1) * (size_t)n_costs * 4 * 64; }
+inline void cost_attitude_shared(const to_cost_desc* costs, int n_costs, std::vector<double>* shared) { cost_attitude_fill(1, costs, n_costs, shared); }
+// the image as one call (tests/host_shim/attitude_harness.cpp): the shared row, then tile_rows
+inline size_t cost_attitude_tiled_len(int n_costs, int Bp) { return tiled_len((size_t)4 * n_costs, Bp); }
 inline void cost_attitude_tile(int B, int Bp, const to_cost_desc* costs, int n_costs, const std::vector<double>& values, std::vector<double>* tiled) {
-  const size_t L = (size_t)4 * n_costs, tiles = (size_t)Bp / 64 + 1;
-  tiled->assign(cost_attitude_tiled_len(n_costs, Bp), 0.0);
-  for (size_t t = 0; t < tiles; ++t)
-    for (size_t e = 0; e < L; ++e)
-      for (int l = 0; l < 64; ++l) {
-        const size_t b = t * 64 + l;
-        (*tiled)[(t * L + e) * 64 + l] = b < (size_t)B ? values[L * b + e] : costs[e / 4].q_ref[e % 4];
-      }
+  std::vector<double> shared;
+  cost_attitude_shared(costs, n_costs, &shared);
+  tile_rows(shared.size(), B, Bp, values.data(), shared.data(), tiled);
 }
 // (How ga rides on gw — which of the two arrays a call fills, when both are released — is path_plan.h cost_lane_step.)
 

@@ -78,29 +78,34 @@ struct to_handle_s {
   double* d_dt = nullptr;
   int* d_cost_index = nullptr;
   int* d_crow = nullptr;    // [64] compact_row table of the model (tangent-matrix getters)
-  std::vector<char> gl_set; // [n_costs] cost i carries per-trajectory linear terms (all clear: DevProblem::gl goes back to null)
-  double* d_gl = nullptr;   // per-trajectory linear cost terms (DevProblem::gl), tiled, L = n_costs * (n + m); allocated on first use
-  // one tracking reference per trajectory (to_set_tracking_reference_batch; k_track.h lowers a window of it into d_gl)
-  double* d_track_ref = nullptr;      // tiled, L = track_Nref * (n + m): rows [x_ref[j]; u_ref[j]] (u rows zero while track_u is false)
+  // Per-trajectory tables, all tiled (entry e of trajectory b at ((b >> 6) * L + e) * 64 + (b & 63)) and allocated on first use; the DevProblem
+  // pointer of the same name is set while the table is in effect.  Two families:
+  //  - zero-filled arrays of L * Bp doubles, written a block of rows at a time through upload_vec (tiled on the device): gl, cp, track_ref;
+  //  - arrays with one spare tile whose lanes behind the batch hold the SHARED value of their row, written whole through upload_tiled (tiled on
+  //    the host, desc_lower.h tile_rows): pm, dtb, cl, gw, ga.
+  double* d_gl = nullptr;    // linear cost terms (DevProblem::gl), L = n_costs * (n + m); k_track.h lowers a tracking window into it
+  std::vector<char> gl_set;  // [n_costs] cost i carries per-trajectory linear terms (all clear: DevProblem::gl goes back to null)
+  double* d_cp = nullptr;    // constraint parameters (DevProblem::cp), L = (n + m) * number of constraints
+  double* d_track_ref = nullptr;      // one tracking reference per trajectory (to_set_tracking_reference_batch), L = track_Nref * (n + m): rows
+                                      // [x_ref[j]; u_ref[j]] (u rows zero while track_u is false)
   int* d_track_start = nullptr;       // [B] 1-based window starts, re-uploaded by every window call
   std::vector<int32_t> track_start;   // host copy of the starts (to_get_tracking_window)
   int track_Nref = 0, track_end = 0;  // knots of the stored reference (0: none) and its end mode (TO_TRACK_END_*)
   bool track_u = false;               // the reference carries controls
-  double* d_pm = nullptr;   // per-trajectory model parameters (DevProblem::pm), tiled, L = 16, one spare tile; allocated on first use
-  std::vector<double> pm_host;  // [16, B] host copy of what DevProblem::pm holds: what to_set_model_params_batch was given, or — pm_own false, the handle
-                                // carries per-trajectory time steps only — the shared parameters repeated (empty: DevProblem::pm is null)
-  bool pm_own = false;      // to_set_model_params_batch is in effect (to_clear_model_params_batch / to_clear_time_steps_batch: which of the two keeps pm alive)
-  double* d_dtb = nullptr;  // per-trajectory time steps (DevProblem::dtb), tiled, L = N - 1, one spare tile; allocated on first use
+  double* d_pm = nullptr;        // model parameters (DevProblem::pm), L = 16
+  std::vector<double> pm_host;   // [16, B] host copy of what DevProblem::pm holds: what to_set_model_params_batch was given, or — pm_own false, the handle
+                                 // carries per-trajectory time steps only — the shared parameters repeated (empty: DevProblem::pm is null)
+  bool pm_own = false;           // to_set_model_params_batch is in effect (to_clear_model_params_batch / to_clear_time_steps_batch: which of the two keeps pm alive)
+  double* d_dtb = nullptr;       // time steps (DevProblem::dtb), L = N - 1
   std::vector<double> dtb_host;  // [N-1, B] what to_set_time_steps_batch was given (empty: shared steps)
-  double* d_cp = nullptr;   // per-trajectory constraint parameters (DevProblem::cp), tiled, L = (n + m) * number of constraints; allocated on first use
-  double* d_cl = nullptr;   // per-trajectory constraint limits (DevProblem::cl), tiled, L = n_cl = summed p of the constraints, one spare tile; allocated on first use
-  std::vector<int> cl_base;                 // [n_cons] first row of constraint i's block in d_cl
-  std::vector<std::vector<double>> cl_host; // [n_cons] limits[q, B] as to_set_constraint_limits_batch was given them (empty: shared limits)
-  double* d_gw = nullptr;   // per-trajectory cost weights (DevProblem::gw), tiled, L = n_costs * (n + m), one spare tile; allocated on first use
-  std::vector<double> gw_host;  // [L, B] the diagonal Q / R every trajectory's costs are evaluated with (desc_lower.h cost_weights_fill; empty: DevProblem::gw is null)
-  double* d_ga = nullptr;   // per-trajectory attitude references (DevProblem::ga), tiled, L = 4 * n_costs, one spare tile; allocated on first use.  The device
-                            // array is the truth after its first fill (k_track_lower writes it); set with d_gw and cleared with it
-  to::CostLaneState lane;     // why gw / ga are set: the caller's weights, the caller's attitudes, attitude tracking (path_plan.h cost_lane_step)
+  double* d_cl = nullptr;        // constraint limits (DevProblem::cl), L = n_cl = summed p of the constraints
+  std::vector<int> cl_base;                  // [n_cons] first row of constraint i's block in d_cl
+  std::vector<std::vector<double>> cl_host;  // [n_cons] limits[q, B] as to_set_constraint_limits_batch was given them (empty: shared limits)
+  double* d_gw = nullptr;        // cost weights (DevProblem::gw), L = n_costs * (n + m)
+  std::vector<double> gw_host;   // [L, B] the diagonal Q / R every trajectory's costs are evaluated with (desc_lower.h cost_weights_fill; empty: DevProblem::gw is null)
+  double* d_ga = nullptr;        // attitude references (DevProblem::ga), L = 4 * n_costs.  The device array is the truth after its first fill
+                                 // (k_track_lower writes it); set with d_gw and cleared with it
+  to::CostLaneState lane;        // why gw / ga are set: the caller's weights, the caller's attitudes, attitude tracking (path_plan.h cost_lane_step)
   double* d_tmp = nullptr;  // [Bp] scratch for reductions / outputs
   double* d_tmp2 = nullptr;
   // multi-GPU: RCCL communicator of the batch shards (to_comm_*; librccl is dlopen'ed on first use)

@@ -156,6 +156,30 @@ int upload_vec(to_handle* h, const double* host, double* d, int cnt, int L = -1,
   HIPCHECK(hipStreamSynchronize(h->stream));
   return TO_OK;
 }
+// host values[L, B] (NULL: the shared row for every trajectory) -> a spare-tile table (handle.h: pm, dtb, cl, gw, ga), whole: allocated on first
+// use, tiled on the host (desc_lower.h tile_rows: the lanes behind the batch and the spare tile on shared[L]), one copy
+int upload_tiled_named(to_handle* h, const char* name, double** d, size_t L, const double* values, const double* shared) {
+  if (!*d) TRY(dev_alloc_named(h, name, d, tiled_len(L, h->a.P.Bp)));
+  std::vector<double> tiled;
+  tile_rows(L, h->a.P.B, h->a.P.Bp, values, shared, &tiled);
+  HIPCHECK(hipMemcpyAsync(*d, tiled.data(), tiled.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  HIPCHECK(hipStreamSynchronize(h->stream));
+  return TO_OK;
+}
+#define upload_tiled(h, p, ...) upload_tiled_named(h, #p, p, __VA_ARGS__)
+// a DevProblem pointer goes back to null when the last flag behind it clears: the handle is back on the kernel variants it ran before
+template <class T, class C, class F>
+void null_unless_any(T** p, const C& flags, F set) {
+  if (std::none_of(flags.begin(), flags.end(), set)) *p = nullptr;
+}
+// what the host-only validators of desc_lower.h take: the facts of a handle (make: cost_weight_facts, track_facts, below), NULL for a NULL handle
+template <class F>
+struct FactsOf {
+  F f{};
+  bool have;
+  FactsOf(const to_handle* h, F (*make)(const to_handle*)) : have(h != nullptr) { if (h) f = make(h); }
+  operator const F*() const { return have ? &f : nullptr; }
+};
 int download_vec(to_handle* h, double* host, const double* d, int cnt, int L = -1, int e0 = 0) {
   if (L < 0) L = cnt;
   const size_t total = (size_t)cnt * h->a.P.B;
@@ -1226,25 +1250,16 @@ int to_get_controls_device(to_handle* h, void* dU) {
 }
 // the host copy of the per-trajectory cost weights (to_handle::gw_host) -> DevProblem::gw, tiled on the host, in one copy
 static int upload_cost_weights(to_handle* h) {
-  DevProblem& P = h->a.P;
-  std::vector<double> tiled;
-  cost_weights_tile(P.n, P.m, P.B, P.Bp, h->costs.data(), (int)h->costs.size(), h->gw_host, &tiled);
-  if (!h->d_gw) TRY(dev_alloc(h, &h->d_gw, tiled.size()));
-  HIPCHECK(hipMemcpyAsync(h->d_gw, tiled.data(), tiled.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  HIPCHECK(hipStreamSynchronize(h->stream));
-  return TO_OK;
+  std::vector<double> shared;
+  cost_weights_shared(h->a.P.n, h->a.P.m, h->costs.data(), (int)h->costs.size(), &shared);
+  return upload_tiled(h, &h->d_gw, shared.size(), h->gw_host.data(), shared.data());
 }
 // DevProblem::ga from every cost's descriptor, tiled on the host, in one copy (first use; the clears that keep the handle routed).  From then on the
 // device array is the truth — k_track_lower writes it — and one cost's four rows move at a time (restart_cost_attitude, the setter, the getter).
 static int upload_cost_attitudes(to_handle* h) {
-  DevProblem& P = h->a.P;
-  std::vector<double> values, tiled;
-  cost_attitude_fill(P.B, h->costs.data(), (int)h->costs.size(), &values);
-  cost_attitude_tile(P.B, P.Bp, h->costs.data(), (int)h->costs.size(), values, &tiled);
-  if (!h->d_ga) TRY(dev_alloc(h, &h->d_ga, tiled.size()));
-  HIPCHECK(hipMemcpyAsync(h->d_ga, tiled.data(), tiled.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  HIPCHECK(hipStreamSynchronize(h->stream));
-  return TO_OK;
+  std::vector<double> shared;
+  cost_attitude_shared(h->costs.data(), (int)h->costs.size(), &shared);
+  return upload_tiled(h, &h->d_ga, shared.size(), nullptr, shared.data());
 }
 static int restart_cost_attitude(to_handle* h, int id) {
   std::vector<double> rows;
@@ -1263,6 +1278,14 @@ static int cost_lane_apply(to_handle* h, const CostLaneAction& act) {
   P.gw = h->d_gw; P.ga = h->d_ga;
   return TO_OK;
 }
+// the array behind DevProblem::gl on first use: zero-filled — every cost starts with its descriptor's terms — with gl_set sized next to it
+// (to_set_cost indexes gl_set whenever d_gl exists, also behind a failed upload of the caller's)
+static int ensure_gl(to_handle* h) {
+  if (h->d_gl) return TO_OK;
+  TRY(dev_alloc(h, &h->d_gl, h->costs.size() * (size_t)(h->a.P.n + h->a.P.m) * h->a.P.Bp));
+  h->gl_set.assign(h->costs.size(), 0);
+  return TO_OK;
+}
 int to_set_cost(to_handle* h, int32_t id, const to_cost_desc* c) {
   CHECK_H(h); CHECK_IDLE(h); CHECK_P(c); TRY(use_device(h));
   if (id < 0 || id >= (int)h->costs.size()) return fail(TO_ERR_ARGUMENT, "cost id out of range");
@@ -1273,9 +1296,7 @@ int to_set_cost(to_handle* h, int32_t id, const to_cost_desc* c) {
     std::vector<double> zero((size_t)nz * h->a.P.B, 0.0);
     TRY(upload_vec(h, zero.data(), h->d_gl, nz, L, id * nz));
     h->gl_set[id] = 0;
-    bool any = false;
-    for (char f : h->gl_set) any = any || f;
-    if (!any) h->a.P.gl = nullptr;  // every cost is back on its shared descriptor: the default forward variants again
+    null_unless_any(&h->a.P.gl, h->gl_set, [](char f) { return f != 0; });  // every cost is back on its shared descriptor: the default forward variants again
   }
   if (h->a.P.gw) {  // ... and so do its per-trajectory weights: the new descriptor's diagonal for every trajectory (the other costs keep theirs)
     cost_weights_restart(h->a.P.n, h->a.P.m, h->a.P.B, h->costs.data(), (int)h->costs.size(), id, &h->gw_host);
@@ -1292,10 +1313,7 @@ int to_set_cost_linear_batch(to_handle* h, int32_t id, const double* q, const do
   if (c.kind == TO_COST_ERROR_QUADRATIC) return fail(TO_ERR_UNSUPPORTED, "per-trajectory linear terms: not for ErrorQuadratic (its q slot carries x_ref)");
   DevProblem& P = h->a.P;
   const int n = P.n, m = P.m, nz = n + m, L = (int)h->costs.size() * nz, B = P.B;
-  if (!h->d_gl) {  // zero-filled: every cost starts with its descriptor's terms
-    TRY(dev_alloc(h, &h->d_gl, (size_t)L * P.Bp));
-    h->gl_set.assign(h->costs.size(), 0);  // sized with the array: to_set_cost indexes it whenever d_gl exists, also behind a failed upload below
-  }
+  TRY(ensure_gl(h));
   std::vector<double> delta;
   if (q) {  // stored as the difference from the descriptor's q: the kernels ADD it to what the shared code path computes
     delta.resize((size_t)n * B);
@@ -1330,13 +1348,9 @@ int to_set_constraint(to_handle* h, int32_t id, const to_constraint_desc* c) {
   if (ci.p != old.p || ci.k1 != old.k1 || ci.k2 != old.k2) return fail(TO_ERR_DIMENSION_MISMATCH, "replacement constraint must keep p and the knot range");
   ci.dual_off = old.dual_off;
   h->cons[id] = ci;  // (cp_off = cl_off = -1: the replaced constraint starts on shared parameters and limits again)
-  bool any = false;
-  for (const DevCon& c : h->cons) any = any || c.cp_off >= 0;
-  if (!any) h->a.P.cp = nullptr;
+  null_unless_any(&h->a.P.cp, h->cons, [](const DevCon& c) { return c.cp_off >= 0; });
   if (!h->cl_host.empty()) h->cl_host[id].clear();
-  any = false;
-  for (const DevCon& c : h->cons) any = any || c.cl_off >= 0;
-  if (!any) h->a.P.cl = nullptr;
+  null_unless_any(&h->a.P.cl, h->cons, [](const DevCon& c) { return c.cl_off >= 0; });
   return upload_tables(h);
 }
 // One parameter set per TRAJECTORY for constraint con_id.  GOAL: params[p, B] = xf_b[inds]; LINEAR: params[p, B] = b_b.  Stored as the shift of
@@ -1395,28 +1409,13 @@ int to_clear_constraint_params_batch(to_handle* h) {
 }
 
 // One set of limits per TRAJECTORY for the selector constraint con_id (DevProblem::cl; desc_lower.h lower_constraint_limits has the layouts and
-// the checks).  The whole tiled array is rebuilt on the host from what every flagged constraint was given and the descriptors of the others —
-// the lanes behind the batch carry the descriptor's values: idle lanes compute along on valid data — and goes up in one copy.
+// the checks, constraint_limits_values the rows).  The whole table is rebuilt on the host from what every flagged constraint was given and the
+// descriptors of the others, and goes up in one copy.
 static int upload_constraint_limits(to_handle* h) {
-  DevProblem& P = h->a.P;
-  const int B = P.B, n_cl = P.n_cl;
-  const size_t tiles = (size_t)P.Bp / 64 + 1;  // (+ one spare tile, like the nominal states)
-  if (!h->d_cl) TRY(dev_alloc(h, &h->d_cl, tiles * n_cl * 64));
-  std::vector<double> tiled(tiles * n_cl * 64), rows;
-  for (size_t i = 0; i < h->cons.size(); ++i) {
-    const DevCon& c = h->cons[i];
-    const bool set = !h->cl_host[i].empty();
-    if (set) TRY(lower_constraint_limits(c, B, h->cl_host[i].data(), &rows));
-    for (size_t t = 0; t < tiles; ++t)
-      for (int r = 0; r < c.p; ++r)
-        for (int l = 0; l < 64; ++l) {
-          const size_t b = t * 64 + l;
-          tiled[(t * n_cl + h->cl_base[i] + r) * 64 + l] = (set && b < (size_t)B) ? rows[r + (size_t)c.p * b] : c.soff[r];
-        }
-  }
-  HIPCHECK(hipMemcpyAsync(h->d_cl, tiled.data(), tiled.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  HIPCHECK(hipStreamSynchronize(h->stream));
-  return TO_OK;
+  std::vector<double> shared, values;
+  constraint_limits_shared(h->cons, h->cl_base, h->a.P.n_cl, &shared);
+  TRY(constraint_limits_values(h->cons, h->cl_host, h->cl_base, shared, h->a.P.B, &values));
+  return upload_tiled(h, &h->d_cl, shared.size(), values.data(), shared.data());
 }
 int to_set_constraint_limits_batch(to_handle* h, int32_t id, const double* limits) {
   CHECK_H(h); CHECK_IDLE(h); CHECK_P(limits); TRY(use_device(h));
@@ -1429,10 +1428,7 @@ int to_set_constraint_limits_batch(to_handle* h, int32_t id, const double* limit
   TRY(constraint_limits_q(ci, &q));
   if (h->cl_host.empty()) {
     h->cl_host.assign(h->cons.size(), std::vector<double>());
-    h->cl_base.assign(h->cons.size(), 0);
-    int L = 0;
-    for (size_t i = 0; i < h->cons.size(); ++i) { h->cl_base[i] = L; L += h->cons[i].p; }
-    P.n_cl = L;
+    P.n_cl = constraint_limits_bases(h->cons, &h->cl_base);
   }
   h->cl_host[id].assign(limits, limits + (size_t)q * P.B);
   TRY(upload_constraint_limits(h));
@@ -1469,9 +1465,10 @@ static const char* model_key_name(int key) {
                                             "InfeasibleModel (double integrator, D = 1)", "InfeasibleModel (double integrator, D = 2)", "InfeasibleModel (Cartpole)"};
   return (key >= 0 && key < N_MODEL_KEYS) ? names[key] : "unknown model";
 }
-static int model_params_supported(const to_handle* h, const char* who) {
+// the models with flagged instances (one plant per trajectory; the time steps ride on them); what: "model parameters" / "time steps"
+static int plants_supported(const to_handle* h, const char* who, const char* what) {
   if (h->model_key > 4 || !h->ops->plants(h->a.bwd_lane != 0))
-    return fail(TO_ERR_UNSUPPORTED, std::string(who) + ": per-trajectory model parameters are not available for the " + model_key_name(h->model_key) +
+    return fail(TO_ERR_UNSUPPORTED, std::string(who) + ": per-trajectory " + what + " are not available for the " + model_key_name(h->model_key) +
                                         " (double integrator, Cartpole and quaternion Quadrotor only)");
   return TO_OK;
 }
@@ -1479,18 +1476,7 @@ static int model_params_supported(const to_handle* h, const char* who) {
 static int upload_plants(to_handle* h, const double* params) {
   DevProblem& P = h->a.P;
   const int B = P.B;
-  const size_t tiles = (size_t)P.Bp / 64 + 1;  // (+ one spare tile, like the nominal states)
-  if (!h->d_pm) TRY(dev_alloc(h, &h->d_pm, tiles * 16 * 64));
-  // tiled on the host; lanes behind the batch carry the shared parameters (idle lanes compute along on valid data)
-  std::vector<double> tiled(tiles * 16 * 64);
-  for (size_t t = 0; t < tiles; ++t)
-    for (int i = 0; i < 16; ++i)
-      for (int l = 0; l < 64; ++l) {
-        const size_t b = t * 64 + l;
-        tiled[(t * 16 + i) * 64 + l] = (params && b < (size_t)B) ? params[16 * b + i] : P.mp[i];
-      }
-  HIPCHECK(hipMemcpyAsync(h->d_pm, tiled.data(), tiled.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  HIPCHECK(hipStreamSynchronize(h->stream));
+  TRY(upload_tiled(h, &h->d_pm, 16, params, P.mp));
   if (params) h->pm_host.assign(params, params + (size_t)16 * B);
   else {
     h->pm_host.resize((size_t)16 * B);
@@ -1501,7 +1487,7 @@ static int upload_plants(to_handle* h, const double* params) {
 }
 int to_set_model_params_batch(to_handle* h, const double* params) {
   CHECK_H(h); CHECK_IDLE(h); CHECK_P(params); TRY(use_device(h));
-  TRY(model_params_supported(h, "to_set_model_params_batch"));
+  TRY(plants_supported(h, "to_set_model_params_batch", "model parameters"));
   DevProblem& P = h->a.P;
   const int B = P.B, key = h->model_key;
   for (int b = 0; b < B; ++b) {
@@ -1520,7 +1506,7 @@ int to_set_model_params_batch(to_handle* h, const double* params) {
 }
 int to_get_model_params_batch(to_handle* h, double* params) {
   CHECK_H(h); CHECK_IDLE(h); CHECK_P(params);
-  TRY(model_params_supported(h, "to_get_model_params_batch"));
+  TRY(plants_supported(h, "to_get_model_params_batch", "model parameters"));
   const DevProblem& P = h->a.P;
   if (P.pm) std::memcpy(params, h->pm_host.data(), sizeof(double) * 16 * P.B);
   else for (int b = 0; b < P.B; ++b) std::memcpy(params + (size_t)16 * b, P.mp, sizeof(double) * 16);
@@ -1528,14 +1514,14 @@ int to_get_model_params_batch(to_handle* h, double* params) {
 }
 int to_clear_model_params_batch(to_handle* h) {
   CHECK_H(h); CHECK_IDLE(h); TRY(use_device(h));
-  TRY(model_params_supported(h, "to_clear_model_params_batch"));
+  TRY(plants_supported(h, "to_clear_model_params_batch", "model parameters"));
   h->pm_own = false;
   if (h->a.P.dtb) TRY(upload_plants(h, nullptr));  // per-trajectory time steps ride on the flagged instances: pm stays, on the shared plant
   else { h->a.P.pm = nullptr; h->pm_host.clear(); }
   return upload_tables(h);
 }
 
-// One diagonal Q / R per TRAJECTORY for the cost cost_id (DevProblem::gw; desc_lower.h has every refusal, the host copy and the tiling).  The
+// One diagonal Q / R per TRAJECTORY for the cost cost_id (DevProblem::gw; desc_lower.h has every refusal, the host copy and the shared row).  The
 // array holds the weights of EVERY cost — the descriptors' values where nothing was set — and the whole of it goes up again with every call.
 // The handle is then routed like one with per-trajectory constraint limits (path_plan.h TableFlags::cost_weights) and launches the GW
 // instances of the kernels that read a cost's diagonal; X, U, duals and gains are left as they are.
@@ -1544,9 +1530,7 @@ static CostWeightFacts cost_weight_facts(const to_handle* h) {
   return CostWeightFacts{h->model_key, model_key_name(h->model_key), P.n, P.m, P.B, h->costs.data(), (int)h->costs.size(), h->inflight.load(), h->track_Nref};
 }
 int to_set_cost_weights_batch(to_handle* h, int32_t cost_id, const double* Q, const double* R) {
-  CostWeightFacts f;
-  if (h) f = cost_weight_facts(h);
-  TRY(validate_cost_weights(h ? &f : nullptr, cost_id, Q, R));  // every refusal, before any device call and before anything changes
+  TRY(validate_cost_weights(FactsOf(h, cost_weight_facts), cost_id, Q, R));  // every refusal, before any device call and before anything changes
   TRY(use_device(h));
   DevProblem& P = h->a.P;
   TRY(cost_lane_apply(h, cost_lane_step(&h->lane, LANE_SET_WEIGHTS)));  // first use: gw and ga from the descriptors (gw may already stand, behind attitude references)
@@ -1556,9 +1540,7 @@ int to_set_cost_weights_batch(to_handle* h, int32_t cost_id, const double* Q, co
   return check_guards(h, "to_set_cost_weights_batch");
 }
 int to_get_cost_weights_batch(to_handle* h, int32_t cost_id, double* Q, double* R) {
-  CostWeightFacts f;
-  if (h) f = cost_weight_facts(h);
-  TRY(validate_cost_weights_get(h ? &f : nullptr, cost_id, Q, R));
+  TRY(validate_cost_weights_get(FactsOf(h, cost_weight_facts), cost_id, Q, R));
   const DevProblem& P = h->a.P;
   const int n = P.n, m = P.m, nz = n + m, B = P.B;
   const size_t L = h->costs.size() * (size_t)nz;
@@ -1571,9 +1553,7 @@ int to_get_cost_weights_batch(to_handle* h, int32_t cost_id, double* Q, double* 
   return TO_OK;
 }
 int to_clear_cost_weights_batch(to_handle* h) {
-  CostWeightFacts f;
-  if (h) f = cost_weight_facts(h);
-  TRY(validate_cost_weights_target("to_clear_cost_weights_batch", h ? &f : nullptr, -1, true));
+  TRY(validate_cost_weights_target("to_clear_cost_weights_batch", FactsOf(h, cost_weight_facts), -1, true));
   TRY(use_device(h));
   // every cost on its descriptor's weights; the kernel variants the handle ran before unless attitude references keep it routed (gw then holds the
   // descriptors' diagonals again)
@@ -1584,9 +1564,7 @@ int to_clear_cost_weights_batch(to_handle* h) {
 // One reference quaternion per TRAJECTORY for the DiagonalQuatCost cost_id (DevProblem::ga; desc_lower.h has every refusal and the image of the
 // array, path_plan.h cost_lane_step the rules by which ga rides on gw).  The setter moves the four rows of its cost and nothing else.
 int to_set_cost_attitude_batch(to_handle* h, int32_t cost_id, const double* q_ref) {
-  CostWeightFacts f;
-  if (h) f = cost_weight_facts(h);
-  TRY(validate_cost_attitude(h ? &f : nullptr, cost_id, q_ref));  // every refusal, before any device call and before anything changes
+  TRY(validate_cost_attitude(FactsOf(h, cost_weight_facts), cost_id, q_ref));  // every refusal, before any device call and before anything changes
   TRY(use_device(h));
   TRY(cost_lane_apply(h, cost_lane_step(&h->lane, LANE_SET_ATTITUDE)));
   TRY(upload_vec(h, q_ref, h->d_ga, 4, 4 * (int)h->costs.size(), 4 * cost_id));
@@ -1594,9 +1572,7 @@ int to_set_cost_attitude_batch(to_handle* h, int32_t cost_id, const double* q_re
   return check_guards(h, "to_set_cost_attitude_batch");
 }
 int to_get_cost_attitude_batch(to_handle* h, int32_t cost_id, double* q_ref) {
-  CostWeightFacts f;
-  if (h) f = cost_weight_facts(h);
-  TRY(validate_cost_attitude_get(h ? &f : nullptr, cost_id, q_ref));
+  TRY(validate_cost_attitude_get(FactsOf(h, cost_weight_facts), cost_id, q_ref));
   if (h->a.P.ga) {  // what every trajectory is evaluated with: the device rows (the setter's, or a tracking window's) ...
     TRY(use_device(h));
     return download_vec(h, q_ref, h->d_ga, 4, 4 * (int)h->costs.size(), 4 * cost_id);
@@ -1606,33 +1582,22 @@ int to_get_cost_attitude_batch(to_handle* h, int32_t cost_id, double* q_ref) {
   return TO_OK;
 }
 int to_clear_cost_attitude_batch(to_handle* h) {
-  CostWeightFacts f;
-  if (h) f = cost_weight_facts(h);
-  TRY(validate_cost_weights_target("to_clear_cost_attitude_batch", h ? &f : nullptr, -1, true));
+  TRY(validate_cost_weights_target("to_clear_cost_attitude_batch", FactsOf(h, cost_weight_facts), -1, true));
   TRY(use_device(h));
   TRY(cost_lane_apply(h, cost_lane_step(&h->lane, LANE_CLEAR_ATTITUDE)));  // (attitude tracking, while on, writes its rows again with the next lowering)
   return upload_tables(h);
 }
 
 // One set of time steps per TRAJECTORY (DevProblem::dtb): dt[(N-1), B], knot fastest.  Validation and tiling are host-only code
-// (desc_lower.h lower_time_steps).  The time step rides on the flagged instances that load one plant per trajectory: while
+// (desc_lower.h validate_time_steps, tile_rows).  The time step rides on the flagged instances that load one plant per trajectory: while
 // dtb is set pm is set too — the shared plant repeated unless to_set_model_params_batch gave each trajectory its own — so the handle is
 // routed exactly as one with `plants` (path_plan.h) and every launcher picks entry [1]; X, U, duals and gains are left as they are.
-static int time_steps_supported(const to_handle* h, const char* who) {
-  if (h->model_key > 4 || !h->ops->plants(h->a.bwd_lane != 0))
-    return fail(TO_ERR_UNSUPPORTED, std::string(who) + ": per-trajectory time steps are not available for the " + model_key_name(h->model_key) +
-                                        " (double integrator, Cartpole and quaternion Quadrotor only)");
-  return TO_OK;
-}
 int to_set_time_steps_batch(to_handle* h, const double* dt) {
   CHECK_H(h); CHECK_IDLE(h); CHECK_P(dt); TRY(use_device(h));
-  TRY(time_steps_supported(h, "to_set_time_steps_batch"));
+  TRY(plants_supported(h, "to_set_time_steps_batch", "time steps"));
   DevProblem& P = h->a.P;
-  std::vector<double> tiled;
-  TRY(lower_time_steps(P.N, P.B, P.Bp, dt, h->dt.data(), &tiled));
-  if (!h->d_dtb) TRY(dev_alloc(h, &h->d_dtb, tiled.size()));
-  HIPCHECK(hipMemcpyAsync(h->d_dtb, tiled.data(), tiled.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  HIPCHECK(hipStreamSynchronize(h->stream));
+  TRY(validate_time_steps(P.N, P.B, dt));
+  TRY(upload_tiled(h, &h->d_dtb, (size_t)P.N - 1, dt, h->dt.data()));
   if (!P.pm) TRY(upload_plants(h, nullptr));
   h->dtb_host.assign(dt, dt + (size_t)(P.N - 1) * P.B);
   P.dtb = h->d_dtb;
@@ -1641,7 +1606,7 @@ int to_set_time_steps_batch(to_handle* h, const double* dt) {
 }
 int to_get_time_steps_batch(to_handle* h, double* dt) {
   CHECK_H(h); CHECK_IDLE(h); CHECK_P(dt);
-  TRY(time_steps_supported(h, "to_get_time_steps_batch"));
+  TRY(plants_supported(h, "to_get_time_steps_batch", "time steps"));
   const DevProblem& P = h->a.P;
   const size_t L = (size_t)P.N - 1;
   if (P.dtb) std::memcpy(dt, h->dtb_host.data(), sizeof(double) * L * P.B);
@@ -1650,7 +1615,7 @@ int to_get_time_steps_batch(to_handle* h, double* dt) {
 }
 int to_clear_time_steps_batch(to_handle* h) {
   CHECK_H(h); CHECK_IDLE(h); TRY(use_device(h));
-  TRY(time_steps_supported(h, "to_clear_time_steps_batch"));
+  TRY(plants_supported(h, "to_clear_time_steps_batch", "time steps"));
   h->a.P.dtb = nullptr;
   h->dtb_host.clear();
   if (!h->pm_own) { h->a.P.pm = nullptr; h->pm_host.clear(); }
@@ -1994,11 +1959,8 @@ static TrackFacts track_facts(const to_handle* h) {
 // the stored starts -> the device, then all N knots of every trajectory into d_gl from the current descriptors (one launch)
 static int track_lower(to_handle* h, const char* who) {
   DevProblem& P = h->a.P;
-  const int nz = P.n + P.m, L = (int)h->costs.size() * nz;
-  if (!h->d_gl) {  // zero-filled: every cost starts with its descriptor's terms (as in to_set_cost_linear_batch)
-    TRY(dev_alloc(h, &h->d_gl, (size_t)L * P.Bp));
-    h->gl_set.assign(h->costs.size(), 0);
-  }
+  const int nz = P.n + P.m;
+  TRY(ensure_gl(h));
   HIPCHECK(hipMemcpyAsync(h->d_track_start, h->track_start.data(), sizeof(int32_t) * P.B, hipMemcpyHostToDevice, h->stream));
   TrackArgs ta;
   ta.n = P.n; ta.m = P.m; ta.N = P.N; ta.B = P.B; ta.Nref = h->track_Nref; ta.with_u = h->track_u ? 1 : 0; ta.n_costs = (int)h->costs.size();
@@ -2054,9 +2016,7 @@ static int tracking_attitude_off(to_handle* h) {
   return upload_tables(h);
 }
 int to_set_tracking_attitude(to_handle* h, int32_t on) {
-  TrackFacts f;
-  if (h) f = track_facts(h);
-  TRY(validate_tracking_attitude(h ? &f : nullptr, on));
+  TRY(validate_tracking_attitude(FactsOf(h, track_facts), on));
   TRY(use_device(h));
   if (!on) return tracking_attitude_off(h);
   TRY(cost_lane_apply(h, cost_lane_step(&h->lane, LANE_TRACK_ON)));
