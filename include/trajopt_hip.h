@@ -88,7 +88,10 @@ extern "C" {
  * weights of every cost among the trajectories of a handle.  And for to_set_cost_attitude_batch / to_get_cost_attitude_batch /
  * to_clear_cost_attitude_batch / to_set_tracking_attitude / to_get_tracking_attitude (one reference quaternion per trajectory for a
  * DiagonalQuatCost, windowed with the tracking reference): five symbols added with TO_ABI_VERSION and TO_ABI_MINOR unchanged and no existing
- * struct changed, found by symbol lookup; a library without them shares every q_ref among the trajectories of a handle. */
+ * struct changed, found by symbol lookup; a library without them shares every q_ref among the trajectories of a handle.  And for
+ * to_mpc_shift_duals (the multipliers moved with the plan of the receding-horizon loop, or reset, per trajectory): one symbol added with
+ * TO_ABI_VERSION and TO_ABI_MINOR unchanged and no existing struct changed, found by symbol lookup; with a library without it a host shifts
+ * the multipliers between to_get_duals and to_set_duals. */
 #define TO_ABI_VERSION 7
 #define TO_ABI_MINOR 1
 
@@ -356,7 +359,8 @@ int to_destroy(to_handle* h);
 /* Options are validated (TO_ERR_ARGUMENT for out-of-range values, here and in to_create).  The number of line-search
  * candidate slots is fixed at to_create from iterations_linesearch: raising it later works, with less concurrency than
  * a fresh handle would have.  The phase API (to_backward, to_forward, to_dual_update) keeps the regularisation and the
- * penalties that to_create wrote from bp_reg_initial / penalty_initial until a solve (both) or to_reset_duals (the penalties) rewrites them:
+ * penalties that to_create wrote from bp_reg_initial / penalty_initial until a solve (both), to_reset_duals or a TO_MPC_DUAL_RESET of
+ * to_mpc_shift_duals (the penalties) rewrites them:
  * setting those two options later changes the next solve, not the state the phase calls continue from. */
 int to_set_options(to_handle* h, const to_solver_opts* opts);
 int to_get_options(const to_handle* h, to_solver_opts* opts);
@@ -708,7 +712,8 @@ int to_policy_noise_draws(int device, uint64_t seed, uint32_t traj, uint32_t sam
  *     U[b][k] <- V[N-2] (TO_MPC_TAIL_HOLD) or u_fill (TO_MPC_TAIL_FILL)   for k > N-2-s
  * A trajectory whose rollout left the limits (status TO_STATE_LIMIT / TO_CONTROL_LIMIT) keeps its x0 and U bit for bit; status and
  * k_limit say why.  Then the handle's ordinary rollout runs: the handle is in the state that to_set_initial_state + to_set_controls +
- * to_rollout with those values would have left.  Not touched: duals and penalties (an AL solve resets them at its start), the
+ * to_rollout with those values would have left.  Not touched: duals and penalties (an AL solve resets them at its start;
+ * to_mpc_shift_duals below moves the multipliers with the plan for a caller that continues from them), the
  * per-trajectory arrays (cost terms, constraint parameters and limits, model parameters, time steps) and the gains beyond what
  * refresh_gains does.  With per-trajectory time steps the steps stay on their knots: the plan moves, the grid does not.
  * Everything the caller gets back is B (s (n + m) + 2 n) doubles and the five per-trajectory summaries; x_meas == NULL starts from the
@@ -739,6 +744,26 @@ typedef struct {        /* HOST arrays, any may be NULL */
 int to_mpc_advance(to_handle* h, const double* x_meas /* [n,B] or NULL = the handle's x0 */, const to_mpc_opts* mpc,
                    const to_policy_opts* popts /* NULL = to_policy_rollout's default */, const to_policy_noise* noise /* NULL = none */,
                    const to_mpc_result* out /* may be NULL */);
+
+/* ---- the dual shift of the receding-horizon loop -------------------------------------------------------
+ * to_mpc_shift_duals: after to_mpc_advance moved the plan `shift` knots, the multipliers follow.  For every constraint (p rows on its nk
+ * knots) of a trajectory with action TO_MPC_DUAL_SHIFT:
+ *     lambda[j] <- lambda[j + shift]                                               for j + shift < nk
+ *     lambda[j] <- lambda[nk - 1] (TO_MPC_DUAL_TAIL_HOLD) or 0 (TO_MPC_DUAL_TAIL_ZERO)  otherwise
+ * (shift >= nk, a terminal GoalConstraint included: every knot is tail).  Penalties are not touched.  TO_MPC_DUAL_RESET: lambda = 0 for every
+ * constraint and mu = penalty_initial, the per-trajectory to_reset_duals (for the member of a fleet whose solve diverged).
+ * TO_MPC_DUAL_LEAVE: nothing is stored.  action == NULL shifts every trajectory.  The values are copied, never computed with: the result is
+ * bit for bit the same shift done on the host between to_get_duals and to_set_duals.  One kernel launch after 4 B bytes of upload (none
+ * with action == NULL).  A handle without constraints returns TO_OK and launches nothing.  Who reads the result: to_ilqr_solve and the
+ * phase API (to_expand, to_backward, to_forward, to_dual_update, to_al_cost) continue from the multipliers the handle holds; to_al_solve and
+ * to_altro_solve still reset both when they start, so before them the call changes nothing they see.
+ * Errors: a solve in flight, shift outside 1 .. N-2, an unknown tail or action -> TO_ERR_ARGUMENT; the models to_mpc_advance refuses ->
+ * TO_ERR_UNSUPPORTED with the model's name.  A refused call changes nothing.  Not announced by TO_ABI_MINOR: look the symbols up (ABI
+ * history above). */
+enum { TO_MPC_DUAL_TAIL_HOLD = 0, TO_MPC_DUAL_TAIL_ZERO = 1 };
+enum { TO_MPC_DUAL_LEAVE = 0, TO_MPC_DUAL_SHIFT = 1, TO_MPC_DUAL_RESET = 2 };
+int to_mpc_shift_duals(to_handle* h, int32_t shift, int32_t tail,
+                       const int32_t* action /* [B] or NULL = SHIFT for all */);
 
 /* raw (non error-state) per-knot cost derivatives of the objective at the current trajectory
  * (RD.gradient! / RD.hessian!): grad[(n+m),N,B], hess[(n+m),(n+m),N,B] */

@@ -967,6 +967,30 @@ function cost_linear_batch(p::BatchProblem, i::Integer)
     check(ccall((:to_get_cost_linear_batch, lib), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}), p.handle, i - 1, q, r))
     (q = q, r = r)
 end
+
+"""
+The dual shift of the receding-horizon loop: `mpc_shift_duals!(p, shift; tail = :hold, action = nothing)` moves the multipliers `shift` knots
+forward with the plan after `mpc_advance!`.  `action` is a `B`-vector of `TO_MPC_DUAL_LEAVE` / `TO_MPC_DUAL_SHIFT` / `TO_MPC_DUAL_RESET`
+(nothing: shift every trajectory), `tail` `:hold` (the new knots repeat the last multiplier of the range) or `:zero`; a reset also puts the
+trajectory's penalties back on `penalty_initial`.  Added without raising `TO_ABI_MINOR`: a library that lacks it is detected by symbol
+lookup (`has_mpc_shift_duals()`).
+"""
+has_mpc_shift_duals() = Libdl.dlsym(Libdl.dlopen(lib), :to_mpc_shift_duals; throw_error = false) !== nothing
+const TO_MPC_DUAL_TAIL_HOLD = Int32(0)
+const TO_MPC_DUAL_TAIL_ZERO = Int32(1)
+const TO_MPC_DUAL_LEAVE = Int32(0)
+const TO_MPC_DUAL_SHIFT = Int32(1)
+const TO_MPC_DUAL_RESET = Int32(2)
+function mpc_shift_duals!(p::BatchProblem, shift::Integer; tail::Symbol = :hold, action::Union{Nothing,AbstractVector{<:Integer}} = nothing)
+    has_mpc_shift_duals() || error("libtrajopt_hip.so does not export to_mpc_shift_duals")
+    1 <= shift <= p.N - 2 || throw(ArgumentError("shift must be in 1 .. N-2"))
+    tail in (:hold, :zero) || throw(ArgumentError("tail must be :hold or :zero"))
+    action === nothing || length(action) == p.B || throw(DimensionMismatch("action must be (B,)"))
+    a = action === nothing ? Int32[] : Vector{Int32}(action)
+    GC.@preserve a check(ccall((:to_mpc_shift_duals, lib), Cint, (Ptr{Cvoid}, Int32, Int32, Ptr{Int32}), p.handle, shift,
+                               tail == :zero ? TO_MPC_DUAL_TAIL_ZERO : TO_MPC_DUAL_TAIL_HOLD, action === nothing ? Ptr{Int32}(C_NULL) : pointer(a)))
+    p
+end
 """
     set_cost_weights_batch!(p, i; Q = nothing, R = nothing)     # Q :: (n, B), R :: (m, B); cost i is 1-based
 One diagonal `Q` / `R` per trajectory for cost `i` (`to_set_cost_weights_batch`): trajectory `b` evaluates the cost with `Q[:, b]` and
@@ -1193,6 +1217,7 @@ end
 
 export LinearMap, MassDoubleIntegrator, BatchProblem, set_model_params_batch!, model_params_batch, clear_model_params_batch!, has_model_params_batch, set_constraint_limits_batch!, get_constraint_limits_batch, clear_constraint_limits_batch!, has_constraint_limits_batch, set_time_steps_batch!, set_final_times_batch!, time_steps_batch, clear_time_steps_batch!, has_time_steps_batch, policy_rollout, PolicyOpts, PolicyResult, policy_rollout_mc, policy_noise_draws, PolicyNoise, mpc_advance!, has_mpc_advance, MpcOpts, MpcResult, set_tracking_window!, tracking_window, clear_tracking_reference_batch!, cost_linear_batch, has_tracking_reference_batch, set_cost_weights_batch!, cost_weights_batch, clear_cost_weights_batch!, has_cost_weights_batch, set_cost_attitude_batch!, cost_attitude_batch, clear_cost_attitude_batch!, set_tracking_attitude!, tracking_attitude, has_cost_attitude_batch, abi_minor, SolverOpts, solver_options, default_options, solve_ilqr!, solve_al!, solve_pn!, solve_altro!, solve_async!, wait_solve!, dynamics_defect, expand!, backwardpass!, forwardpass!,
     stage_costs, al_cost, dynamics_jacobians, cost_expansion, gains, cost_gradient_hessian, discrete_jacobian, duals, set_duals!,
-    reset_duals!, dual_update!, comm_unique_id, comm_init_rank!, allgather!, allgather_stats, comm_shards, comm_destroy!, solver_path, knot_dims, device_count, build_id
+    reset_duals!, dual_update!, mpc_shift_duals!, has_mpc_shift_duals, TO_MPC_DUAL_LEAVE, TO_MPC_DUAL_SHIFT, TO_MPC_DUAL_RESET,
+    comm_unique_id, comm_init_rank!, allgather!, allgather_stats, comm_shards, comm_destroy!, solver_path, knot_dims, device_count, build_id
 
 end # module

@@ -180,6 +180,8 @@ class MpcResult(C.Structure):
 
 MPC_GUESS_CLOSED_LOOP, MPC_GUESS_NOMINAL = 0, 1
 MPC_TAIL_HOLD, MPC_TAIL_FILL = 0, 1
+MPC_DUAL_TAIL_HOLD, MPC_DUAL_TAIL_ZERO = 0, 1                     # to_mpc_shift_duals
+MPC_DUAL_LEAVE, MPC_DUAL_SHIFT, MPC_DUAL_RESET = 0, 1, 2
 TRACK_END_REFUSE, TRACK_END_HOLD = 0, 1
 
 _H = C.c_void_p
@@ -298,6 +300,8 @@ HIP_ONLY = {
     "clear_cost_attitude_batch": [_H],
     "set_tracking_attitude": [_H, C.c_int32],
     "get_tracking_attitude": [_H, _PI],
+    # the dual shift of the receding-horizon loop (OPTIONAL_HIP below)
+    "mpc_shift_duals": [_H, C.c_int32, C.c_int32, _PI],
 }
 # Entry points added without raising TO_ABI_MINOR (include/trajopt_hip.h, ABI history): detected by symbol lookup.  A library that does
 # not export them still loads; the names are then absent from Library._fn and the wrappers in api.py raise UnsupportedError.
@@ -309,7 +313,8 @@ OPTIONAL_HIP = ("set_model_params_batch", "get_model_params_batch", "clear_model
                 "get_cost_linear_batch",
                 "set_cost_weights_batch", "get_cost_weights_batch", "clear_cost_weights_batch",
                 "set_cost_attitude_batch", "get_cost_attitude_batch", "clear_cost_attitude_batch", "set_tracking_attitude",
-                "get_tracking_attitude")
+                "get_tracking_attitude",
+                "mpc_shift_duals")
 
 
 class Library:

@@ -43,7 +43,7 @@ __all__ = [
     "GoalConstraint", "BoundConstraint", "NormConstraint", "CircleConstraint", "SphereConstraint", "CollisionConstraint", "QuatVecEq",
     "LinearConstraint", "StateBound", "ControlBound", "IndexedConstraint", "change_dimension",
     "ConstraintList", "add_constraint", "num_constraints", "constraint_hessians",
-    "KnotPoint", "Problem", "rollout", "policy_rollout", "PolicyRollout", "PolicyNoise", "policy_noise_draws", "mpc_advance", "MpcAdvance", "mpc_run", "MpcRun", "set_model_params", "model_params", "clear_model_params",
+    "KnotPoint", "Problem", "rollout", "policy_rollout", "PolicyRollout", "PolicyNoise", "policy_noise_draws", "mpc_advance", "MpcAdvance", "mpc_run", "MpcRun", "mpc_shift_duals", "set_model_params", "model_params", "clear_model_params",
     "set_time_steps_batch", "set_final_times_batch", "time_steps", "clear_time_steps_batch", "cost", "states", "controls", "initial_controls", "initial_states",
     "set_initial_state", "set_goal_state", "update_trajectory", "set_tracking_reference_batch", "set_tracking_window", "get_tracking_window",
     "clear_tracking_reference_batch", "get_cost_linear_batch", "set_cost_weights_batch", "get_cost_weights_batch", "clear_cost_weights_batch",
@@ -1509,7 +1509,8 @@ def mpc_advance(prob, x_meas=None, shift=1, guess="closed_loop", tail="hold", u_
     ``refresh_gains``, ``u_min`` / ``u_max``, ``plant`` and ``noise`` are ``policy_rollout``'s.  Equal, bit for bit, to
     ``policy_rollout(..., trajectories=True)``, a shift in numpy, ``set_initial_state``, ``initial_controls`` and ``rollout``; only
     B (shift (n + m) + 2 n) doubles come back.  A trajectory with a nonzero ``status`` keeps its x0 and controls.  Duals, penalties,
-    per-trajectory parameters and time steps are not shifted.  Returns an ``MpcAdvance``."""
+    per-trajectory parameters and time steps are not shifted (``mpc_shift_duals`` moves the duals with the plan).  Returns an
+    ``MpcAdvance``."""
     _need_mpc_advance(prob)
     B, N, n, m = prob.B, prob.N, prob.n, prob.m
     if isinstance(shift, bool) or not isinstance(shift, (int, np.integer)) or not 1 <= shift <= N - 2:
@@ -1575,6 +1576,45 @@ def _advance_tracking_window(prob, moved, s, t):
     else:
         start = np.minimum(start, tr["Nref"])  # every knot of such a window already tracks the last reference knot
     set_tracking_window(prob, start.astype(np.int32))
+
+
+_MPC_DUAL_TAIL = {"hold": capi.MPC_DUAL_TAIL_HOLD, "zero": capi.MPC_DUAL_TAIL_ZERO}
+_MPC_DUAL_ACTION = {"leave": capi.MPC_DUAL_LEAVE, "shift": capi.MPC_DUAL_SHIFT, "reset": capi.MPC_DUAL_RESET}
+
+
+def mpc_shift_duals(prob, shift, tail="hold", action=None):
+    """Move the duals ``shift`` knots forward with the plan, on the device (to_mpc_shift_duals): for every constraint of a trajectory
+    whose ``action`` is "shift" (1), ``lam[j] <- lam[j + shift]`` on the knots of its range that have a source and, on the others, the dual
+    of the range's last knot (``tail="hold"``) or 0 (``tail="zero"``); penalties stay.  "reset" (2): that trajectory's duals go to 0 and its
+    penalties to ``penalty_initial`` (a per-trajectory ``reset_duals``); "leave" (0): nothing is stored.  ``action``: [B] of 0/1/2 or of the
+    three strings; None shifts every trajectory.  The values are copied: the result is bit for bit the numpy shift between ``get_duals`` and
+    ``set_duals``.  A problem without constraints is left alone.  ``iLQRSolver`` and the phase calls continue from the shifted duals;
+    ``ALSolver`` / ``ALTROSolver`` still reset duals and penalties when they start."""
+    if "mpc_shift_duals" not in prob._lib._fn:
+        if "policy_rollout" not in prob._lib._fn:
+            raise NotImplementedError("mpc_shift_duals needs the HIP library (on the CPU oracle, shift between get_duals and set_duals)")
+        raise UnsupportedError("mpc_shift_duals needs a HIP library that exports to_mpc_shift_duals")
+    B, N = prob.B, prob.N
+    if isinstance(shift, bool) or not isinstance(shift, (int, np.integer)) or not 1 <= shift <= N - 2:
+        raise ArgumentError(f"shift must be an integer in 1 .. N-2 = {N - 2}; got {shift!r}")
+    if tail not in _MPC_DUAL_TAIL:
+        raise ArgumentError(f"tail must be one of {sorted(_MPC_DUAL_TAIL)}; got {tail!r}")
+    act = None
+    if action is not None:
+        a = np.asarray(action)
+        if a.shape != (B,):
+            raise DimensionMismatch(f"action must be [B={B}]; got {a.shape}")
+        if a.dtype.kind in "US":
+            bad = [x for x in a.tolist() if x not in _MPC_DUAL_ACTION]
+            if bad:
+                raise ArgumentError(f"action must hold 0 / 1 / 2 or {sorted(_MPC_DUAL_ACTION)}; got {bad[0]!r}")
+            a = np.array([_MPC_DUAL_ACTION[x] for x in a.tolist()], dtype=np.int32)
+        elif a.dtype == bool or not np.issubdtype(a.dtype, np.integer):
+            raise ArgumentError(f"action must hold 0 / 1 / 2 or {sorted(_MPC_DUAL_ACTION)}; got {a.dtype}")
+        elif a.size and (a.min() < 0 or a.max() > 2):
+            raise ArgumentError(f"action must hold 0 / 1 / 2 or {sorted(_MPC_DUAL_ACTION)}; got {int(a[(a < 0) | (a > 2)][0])}")
+        act = np.ascontiguousarray(a, dtype=np.int32)
+    prob._call("mpc_shift_duals", int(shift), _MPC_DUAL_TAIL[tail], prob._pi(act) if act is not None else None)
 
 
 def mpc_run(solver, steps, shift=1, x_true=None, plant=None, noise=None, before_solve=None, advance_reference=True, **advance_kw):

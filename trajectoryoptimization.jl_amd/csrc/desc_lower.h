@@ -385,6 +385,30 @@ inline void pack_tracking_reference(int n, int m, int B, int Nref, const double*
     }
 }
 
+// The dual shift of the receding-horizon loop (to_mpc_shift_duals): every refusal of the entry point, decided from what the host knows of the
+// handle before any device call (model_key as in TrackFacts).  A handle without constraints passes: the entry point then launches nothing.
+struct MpcDualFacts {
+  int model_key; const char* model_name;
+  int N, B;
+  bool in_flight;
+};
+inline int validate_mpc_shift_duals(const MpcDualFacts& f, int32_t shift, int32_t tail, const int32_t* action /* [B] or NULL */) {
+  const char* who = "to_mpc_shift_duals";
+  if (f.in_flight) return fail(TO_ERR_ARGUMENT, "an asynchronous solve is in flight on this handle (call to_solve_wait first)");
+  if (f.model_key >= 7)  // the models to_mpc_advance refuses: their plan cannot move, so neither can its multipliers
+    return fail(TO_ERR_UNSUPPORTED, std::string(who) + ": not available for the " + f.model_name +
+                                        " (TO_MODEL_HYBRID_DOUBLE_INTEGRATOR, TO_MODEL_VECTOR and TO_MODEL_INFEASIBLE cannot shift their plan)");
+  if (shift < 1 || shift > f.N - 2)
+    return fail(TO_ERR_ARGUMENT, std::string(who) + ": shift must be in 1 .. N-2 = " + std::to_string(f.N - 2) + "; got " + std::to_string(shift));
+  if (tail != TO_MPC_DUAL_TAIL_HOLD && tail != TO_MPC_DUAL_TAIL_ZERO)
+    return fail(TO_ERR_ARGUMENT, std::string(who) + ": tail must be TO_MPC_DUAL_TAIL_HOLD (0) or TO_MPC_DUAL_TAIL_ZERO (1)");
+  for (int b = 0; action && b < f.B; ++b)
+    if (action[b] != TO_MPC_DUAL_LEAVE && action[b] != TO_MPC_DUAL_SHIFT && action[b] != TO_MPC_DUAL_RESET)
+      return fail(TO_ERR_ARGUMENT, std::string(who) + ": action of trajectory " + std::to_string(b) + " is " + std::to_string(action[b]) +
+                                       " (TO_MPC_DUAL_LEAVE 0, TO_MPC_DUAL_SHIFT 1 or TO_MPC_DUAL_RESET 2)");
+  return TO_OK;
+}
+
 // Per-trajectory time steps (to_set_time_steps_batch): dt[(N-1), B], knot fastest, column b read exactly like to_problem_desc::dt.
 // validate_time_steps checks every value — finite and > 0, the check the descriptor's own steps get at to_create; there is NO "must sum to
 // tf - t0" check: trajectory b ends at its own tf_b = t0 + sum_k dt_b[k].  lower_time_steps: the checks, then the image of DevProblem::dtb

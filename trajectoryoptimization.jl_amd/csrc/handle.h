@@ -20,6 +20,7 @@
 namespace to {
 
 int fail(int code, const std::string& msg);  // records the message for to_last_error(), returns code
+struct MpcDualCon;  // k_mpc.h (one translation unit only)
 
 #define HIPCHECK(expr)                                                                         \
   do {                                                                                         \
@@ -92,6 +93,8 @@ struct to_handle_s {
   std::vector<int32_t> track_start;   // host copy of the starts (to_get_tracking_window)
   int track_Nref = 0, track_end = 0;  // knots of the stored reference (0: none) and its end mode (TO_TRACK_END_*)
   bool track_u = false;               // the reference carries controls
+  to::MpcDualCon* d_dual_cons = nullptr;  // to_mpc_shift_duals (k_mpc.h): {dual_off, p, nk} per constraint, written on first use (the constraints are fixed at to_create)
+  int* d_dual_action = nullptr;           // ... and the [Bp] actions of a call
   double* d_pm = nullptr;        // model parameters (DevProblem::pm), L = 16
   std::vector<double> pm_host;   // [16, B] host copy of what DevProblem::pm holds: what to_set_model_params_batch was given, or — pm_own false, the handle
                                  // carries per-trajectory time steps only — the shared parameters repeated (empty: DevProblem::pm is null)

@@ -100,4 +100,50 @@ __global__ void __launch_bounds__(64) k_mpc_shift_nominal(MpcArgs a) {
   }
 }
 
+// ---- to_mpc_shift_duals: the multipliers follow the plan -------------------------------------------------------------------------------
+// The tiled dual array (L = n_duals) holds, for constraint ci on knots k1 .. k2 (nk of them, p rows each), the rows
+// dual_off + j p + r of knot j = k - k1.  On a trajectory with action 1 (TO_MPC_DUAL_SHIFT)  lam[j] <- lam[j + s]  for j + s < nk, the other
+// knots take lam[nk - 1] (tail 0, TO_MPC_DUAL_TAIL_HOLD) or 0 (tail 1, TO_MPC_DUAL_TAIL_ZERO); s >= nk (a terminal constraint: nk = 1): every
+// knot is tail.  Action 2 (TO_MPC_DUAL_RESET): lam <- 0 and the constraint's penalty <- mu_reset.  Action 0 (TO_MPC_DUAL_LEAVE), and a lane behind
+// the batch, stores nothing.  Penalties are touched by RESET only.
+// In place, by the argument of k_mpc_shift_nominal: a lane walks its own column in ascending e, reads row e + s p (not yet written) or, for the
+// hold tail, a row of knot nk - 1, which the walk rewrites last and with its own values (s p >= p, so those rows are never shifted into).
+// The action picks the value with selects: every lane of the wave issues the same whole-row load and, unless it leaves, the same whole-row store.
+struct MpcDualCon {
+  long long dual_off;  // DevCon::dual_off
+  int p, nk;           // rows per knot, knots (k2 - k1 + 1)
+};
+struct MpcDualArgs {
+  int B, n_cons;
+  int s;       // knots the multipliers move forward, >= 1
+  int tail;    // 0 hold, 1 zero
+  long long n_duals;
+  double mu_reset;         // penalty_initial
+  const MpcDualCon* cons;  // [n_cons]
+  const int* action;       // [B], or null: shift every trajectory
+  double* lam;             // tiled, L = n_duals
+  double* mu;              // tiled, L = n_cons
+};
+// grid (tiles, constraints)
+__global__ void __launch_bounds__(64) k_mpc_shift_duals(MpcDualArgs a) {
+  const int lane = threadIdx.x, tile = blockIdx.x, ci = blockIdx.y, b = tile * 64 + lane;
+  if (b >= a.B) return;
+  const int act = a.action ? a.action[b] : 1;
+  const bool store = act != 0, shift = act == 1;
+  const MpcDualCon c = a.cons[ci];
+  const int p = c.p, L = p * c.nk;
+  const long long d = (long long)a.s * p;
+  const int keep = d < L ? (int)(L - d) : 0;  // rows that have a source s knots ahead
+  double* lam = a.lam + ((size_t)tile * (size_t)a.n_duals + (size_t)c.dual_off) * 64 + lane;
+  for (int e = 0, r = 0; e < L; ++e, r = (r + 1 == p) ? 0 : r + 1) {  // r = e % p
+    const bool has = e < keep;
+    const int src = has ? e + (int)d : L - p + r;
+    double v = lam[(size_t)src * 64];
+    v = (has || a.tail == 0) ? v : 0.0;
+    v = shift ? v : 0.0;
+    if (store) lam[(size_t)e * 64] = v;
+  }
+  if (act == 2) a.mu[((size_t)tile * (size_t)a.n_cons + (size_t)ci) * 64 + lane] = a.mu_reset;
+}
+
 }  // namespace to

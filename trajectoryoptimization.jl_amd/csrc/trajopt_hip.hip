@@ -1950,6 +1950,31 @@ int to_mpc_advance(to_handle* h, const double* x_meas, const to_mpc_opts* mpc, c
   HIPCHECK(hipStreamSynchronize(h->stream));
   return check_guards(h, "to_mpc_advance");
 }
+// ---- the dual shift of the receding-horizon loop (k_mpc.h k_mpc_shift_duals) -----------------------------------------------
+// One launch over (tiles, constraints) after the 4 B bytes of the actions; every refusal before any device call (desc_lower.h).
+int to_mpc_shift_duals(to_handle* h, int32_t shift, int32_t tail, const int32_t* action) {
+  CHECK_H(h);
+  const DevProblem& P = h->a.P;
+  TRY(validate_mpc_shift_duals(MpcDualFacts{h->model_key, model_key_name(h->model_key), P.N, P.B, h->inflight.load()}, shift, tail, action));
+  if (P.n_cons == 0) return TO_OK;
+  TRY(use_device(h));
+  std::vector<MpcDualCon> table;  // (lives until the synchronisation below)
+  if (!h->d_dual_cons) {
+    for (const DevCon& c : h->cons) table.push_back(MpcDualCon{c.dual_off, c.p, c.k2 - c.k1 + 1});
+    TRY(dev_alloc(h, &h->d_dual_cons, table.size(), false));
+    HIPCHECK(hipMemcpyAsync(h->d_dual_cons, table.data(), table.size() * sizeof(MpcDualCon), hipMemcpyHostToDevice, h->stream));
+  }
+  if (action) {
+    if (!h->d_dual_action) TRY(dev_alloc(h, &h->d_dual_action, (size_t)P.Bp));
+    HIPCHECK(hipMemcpyAsync(h->d_dual_action, action, sizeof(int32_t) * P.B, hipMemcpyHostToDevice, h->stream));
+  }
+  MpcDualArgs da;
+  da.B = P.B; da.n_cons = P.n_cons; da.s = shift; da.tail = tail; da.n_duals = P.n_duals; da.mu_reset = P.opts.penalty_initial;
+  da.cons = h->d_dual_cons; da.action = action ? h->d_dual_action : nullptr; da.lam = h->a.lam; da.mu = h->a.mu;
+  TRY(launch(k_mpc_shift_duals, dim3((unsigned)(P.Bp / 64), (unsigned)P.n_cons), dim3(BLOCK), 0, h->stream, da));
+  HIPCHECK(hipStreamSynchronize(h->stream));
+  return check_guards(h, "to_mpc_shift_duals");
+}
 // ---- one tracking reference per trajectory, windowed on the device (k_track.h) --------------------------------------------------------
 static TrackFacts track_facts(const to_handle* h) {
   const DevProblem& P = h->a.P;
