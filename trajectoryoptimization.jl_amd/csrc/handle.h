@@ -72,6 +72,7 @@ struct to_handle_s {
   to::PathTraits traits;  // what `ops` tells the host logic (path_plan.h), built once at to_create
   to::PathPlan plan;      // the kernel path of this handle's solves and the candidate-buffer sizes that follow from it (path_plan.h plan_paths)
   int list_active = 0;    // list mode (KArgs::fwd_list): the last active count the solve loop has seen — what k_forward2's grid is sized for
+  bool sync_debug = false;  // TRAJOPT_SYNC_DEBUG as the solve in flight read it (solve_loop.h read_solve_knobs): a synchronisation and a stderr line per batch step
   int accept_chunks = 1;  // grid.z of k_accept (a chunk is >= 32 elements of [X; U]: the copy is latency-bound per wave)
   // device copies of the descriptor tables
   to_cost_desc* d_costs = nullptr;

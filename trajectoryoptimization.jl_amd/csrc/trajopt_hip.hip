@@ -22,6 +22,7 @@
 #include "k_generic.h"
 #include "k_mpc.h"
 #include "k_track.h"
+#include "solve_loop.h"
 
 using namespace to;
 
@@ -319,22 +320,26 @@ int launch_accept(to_handle* h) {  // materialise accepted candidate slots on sl
   enqueue(k_accept, grid_b(h, 1, h->accept_chunks), dim3(BLOCK), 0, h->stream, h->a);
   return launch(k_clear_acc, grid_b(h), dim3(BLOCK), 0, h->stream, h->a);
 }
-// forward pass: ONE launch runs the whole line search (CW step sizes per round, concurrently, inside each wave) and the
-// per-trajectory state machine (k_forward.h), in the kernel variant path_plan.h forward_mode picks
-int launch_forward(to_handle* h, bool accept = true, bool two_wave = false) {
+// the forward-pass variant of the handle's problem (path_plan.h forward_mode) — among the instances that load one plant per trajectory (the
+// general ones, stage cost read per knot), or among the others; < 0: not compiled for this model
+int forward_variant(const to_handle* h, bool with_plants) {
   const DevProblem& P = h->a.P;  // (the general variants also with per-trajectory linear cost terms / constraint parameters: only they read them)
-  if (plants(h)) {  // one plant per trajectory: the general variants that load it per trajectory, as one-wave workgroups (stage cost read per knot)
-    const int pmode = forward_mode(false, P.n_cons > 0, P.integrator == INTEG_RK4, true, false, h->traits.forward_plants);
-    if (pmode < 0) return fail(TO_ERR_UNSUPPORTED, "forward-pass variant with per-trajectory model parameters not compiled for this model");
-    TRY(h->ops->forward[1][pmode](h));
-    if (accept) TRY(launch_accept(h));
-    return TO_OK;
+  if (with_plants) return forward_mode(false, P.n_cons > 0, P.integrator == INTEG_RK4, true, false, h->traits.forward_plants);
+  return forward_mode(forward_simple(P.simple_stage, P.gw != nullptr), P.n_cons > 0, P.integrator == INTEG_RK4,
+                      forward_general(P.expand_variant, P.gl != nullptr, P.cp != nullptr, P.cl != nullptr, P.gw != nullptr), P.unit_soc, h->traits.forward);
+}
+// forward pass: ONE launch runs the whole line search (CW step sizes per round, concurrently, inside each wave) and the
+// per-trajectory state machine (k_forward.h), in the kernel variant forward_variant picks
+int launch_forward(to_handle* h, bool accept = true, bool two_wave = false) {
+  const int mode = forward_variant(h, plants(h) != 0);
+  if (plants(h)) {  // one plant per trajectory: as one-wave workgroups
+    if (mode < 0) return fail(TO_ERR_UNSUPPORTED, "forward-pass variant with per-trajectory model parameters not compiled for this model");
+    TRY(h->ops->forward[1][mode](h));
+  } else {
+    if (mode < 0) return fail(TO_ERR_UNSUPPORTED, "forward-pass variant not compiled for this model");
+    if ((two_wave || h->plan.fwd2 == 1) && h->ops->forward2[mode]) TRY(h->ops->forward2[mode](h));
+    else TRY(h->ops->forward[0][mode](h));
   }
-  const int mode = forward_mode(forward_simple(P.simple_stage, P.gw != nullptr), P.n_cons > 0, P.integrator == INTEG_RK4,
-                                forward_general(P.expand_variant, P.gl != nullptr, P.cp != nullptr, P.cl != nullptr, P.gw != nullptr), P.unit_soc, h->traits.forward);
-  if (mode < 0) return fail(TO_ERR_UNSUPPORTED, "forward-pass variant not compiled for this model");
-  if ((two_wave || h->plan.fwd2 == 1) && h->ops->forward2[mode]) TRY(h->ops->forward2[mode](h));
-  else TRY(h->ops->forward[0][mode](h));
   if (accept) TRY(launch_accept(h));  // inside a solve the next expansion writes the accepted step through instead
   return TO_OK;
 }
@@ -359,6 +364,20 @@ int launch_flag_list(to_handle* h) {
   if (!compact_grid(a.P.Bp, &per, &nb)) return fail(TO_ERR_UNSUPPORTED, "batch too large for the compaction kernels (16 777 216 trajectories)");
   enqueue(k_flags_count, dim3(nb), dim3(1024), 0, h->stream, a.pending, a.P.Bp, per, a.ccount);
   return launch(k_flags_write, dim3(nb), dim3(1024), 0, h->stream, a.pending, a.P.Bp, per, a.ccount, a.plist, a.pcount);
+}
+// the two-launch line search: launch A — one round for everybody; flags -> list; launch B — the rest of the search for the flagged ones; the accept
+int launch_forward_two(to_handle* h) {
+  KArgs& a = h->a;
+  const PathPlan& pl = h->plan;
+  const int cw0 = a.CW, tw0 = a.TW, dump0 = a.dump_wave;
+  a.dump_wave = pl.ls2_dump;
+  a.CW = pl.ls2_cwa; a.TW = 64 / pl.ls2_cwa; a.ls_phase = 1; a.blk0 = 0;
+  TRY(launch_forward(h, false, false));
+  TRY(launch_flag_list(h));
+  a.CW = pl.ls2_cwb; a.TW = 64 / pl.ls2_cwb; a.ls_phase = 2; a.ls_c0 = pl.ls2_cwa; a.blk0 = pl.ls2_blkA;
+  TRY(launch_forward(h, false, false));
+  a.ls_phase = 0; a.blk0 = 0; a.CW = cw0; a.TW = tw0; a.dump_wave = dump0;
+  return launch_accept(h);
 }
 int launch_violation(to_handle* h, double* out) { return h->ops->violation(h, out); }
 
@@ -523,6 +542,7 @@ void publish_progress(to_handle* h, int active, int steps) {
   if (active < before) { std::lock_guard<std::mutex> lk(h->prog_mu); h->prog_cv.notify_all(); }
 }
 int solve_impl(to_handle* h, to_solve_stats* st, int al_mode);
+SolveKnobs solve_knobs() { return read_solve_knobs([](const char* name) -> const char* { return std::getenv(name); }); }  // (solve_loop.h; per solve)
 int solve(to_handle* h, to_solve_stats* st, int al_mode) {
   int rc = solve_impl(h, st, al_mode);
   if (rc == TO_OK && h->guard) rc = check_guards(h, "the end of a solve (final accept, working set home, statistics)");
@@ -651,8 +671,7 @@ int altro_solve(to_handle* h, to_solve_stats* st) {
   if (!pn) return solve(h, st, 1);
   TRY(use_device(h));
   const int B = h->a.P.B;
-  int early = 1;
-  if (const char* env = std::getenv("TRAJOPT_PN_EARLY")) early = std::max(0, std::min(8, std::atoi(env)));
+  const int early = solve_knobs().pn_early;
   h->pn_early = 0; h->pn_early_slots = 0;
   if (early > 0 && h->ops->pn_launch[0] && !h->ops->write_through) {  // (write-through models keep accepted steps in candidate slots until the solve ends)
     // (a problem the polish cannot take — too many rows on a knot, no memory for the workspace — still gets its AL stage)
@@ -697,6 +716,41 @@ int altro_solve(to_handle* h, to_solve_stats* st) {
   return TO_OK;
 }
 
+// one batch step of a solve: the launches `sp` names (path_plan.h plan_step), with the step's profile events, guard check and sync-debug line
+int batch_step(to_handle* h, int step, const StepPlan& sp) {
+  KArgs& a = h->a;
+  const DevProblem& P = a.P;
+  a.step = step;
+  if (h->profile) HIPCHECK(hipEventRecord(h->ev[4 * step + 0], h->stream));
+  if (sp.kind == STEP_SPLIT) TRY(launch_expand(h));
+  if (h->profile) HIPCHECK(hipEventRecord(h->ev[4 * step + 1], h->stream));
+  switch (sp.kind) {
+    case STEP_FUSED_LANE: TRY(h->ops->expand_backward(h)); break;
+    case STEP_SCAN: TRY(h->ops->expand_backward_scan(h)); break;
+    case STEP_FUSED_COOP: TRY(h->ops->expand_backward_coop(h)); break;
+    case STEP_SPLIT: TRY(launch_backward(h)); break;
+  }
+  if (h->profile) HIPCHECK(hipEventRecord(h->ev[4 * step + 2], h->stream));
+  a.CW = sp.CW; a.TW = sp.TW; a.store_x = sp.store_x;
+  if (sp.two_launch) TRY(launch_forward_two(h));
+  else TRY(launch_forward(h, !h->ops->write_through || !a.store_x, sp.two_wave));
+  a.store_x = 1;
+  if (a.al_mode) TRY(launch_outer(h));
+  if (a.compact) TRY(launch_compact(h));
+  if (h->profile) HIPCHECK(hipEventRecord(h->ev[4 * step + 3], h->stream));
+  if (h->guard) {
+    if (step == 0) if (const char* env = std::getenv("TRAJOPT_GUARD_SELFTEST")) if (std::atoi(env))  // one double behind the nominal states
+      enqueue(k_guard_poke, dim3(1), dim3(1), 0, h->stream, a.Xs, (long long)P.N * P.n * (P.Bp + 64) + 3);
+    TRY(check_guards(h, ("batch step " + std::to_string(step) + " of a solve").c_str()));
+  }
+  if (h->sync_debug) {  // TRAJOPT_SYNC_DEBUG=1: localise a device fault to a batch step
+    const hipError_t e = hipStreamSynchronize(h->stream);
+    std::fprintf(stderr, "[sync-debug] step %d B=%d Bp=%d level=%d store_x-path=%d: %s\n", step, a.P.B, a.P.Bp, h->rp_level, h->list_active, hipGetErrorString(e));
+    if (e != hipSuccess) return fail(TO_ERR_HIP, "device fault (sync debug)");
+  }
+  return TO_OK;
+}
+
 int solve_impl(to_handle* h, to_solve_stats* st, int al_mode) {
   TRY(use_device(h));
   KArgs& a = h->a;
@@ -716,13 +770,13 @@ int solve_impl(to_handle* h, to_solve_stats* st, int al_mode) {
     h->counter_len = max_steps;
   }
   HIPCHECK(hipMemsetAsync(a.counter - 1, 0, sizeof(int) * (max_steps + 1), h->stream));
+  const SolveKnobs knobs = solve_knobs();
+  h->sync_debug = knobs.sync_debug != 0;
   {  // list mode (path_plan.h solve_forward_list), for this whole solve or not at all; TRAJOPT_FWD_LIST=0 keeps the forward pass's fixed map
-    const char* env = std::getenv("TRAJOPT_FWD_LIST");
-    const int mode = forward_mode(forward_simple(P.simple_stage, P.gw != nullptr), P.n_cons > 0, P.integrator == INTEG_RK4,
-                                  forward_general(P.expand_variant, P.gl != nullptr, P.cp != nullptr, P.cl != nullptr, P.gw != nullptr), P.unit_soc, h->traits.forward);
+    const int mode = forward_variant(h, false);
     a.fwd_list = solve_forward_list(h->plan, h->traits, a.h_diag, P.expand_variant, a.compact, al_mode, P.B, P.Bp, plants(h) != 0, P.gl != nullptr,
                                     mode >= 0 && h->ops->forward2[mode] != nullptr && h->ops->expand_backward_scan != nullptr,
-                                    !(env && std::atoi(env) == 0), FWD_LIST_MAX_BP, P.gw != nullptr) ? 1 : 0;
+                                    knobs.fwd_list != 0, FWD_LIST_MAX_BP, P.gw != nullptr) ? 1 : 0;
   }
   TRY(ensure_solve_events(h));
   const hipEvent_t e0 = h->sev[0], e1 = h->sev[1];
@@ -735,125 +789,48 @@ int solve_impl(to_handle* h, to_solve_stats* st, int al_mode) {
     a.step = -1;
     TRY(launch_compact(h));
   }
-  int steps = 0;
   if (h->profile) {
     while ((int)h->ev.size() < 4 * max_steps) { hipEvent_t e; HIPCHECK(hipEventCreate(&e)); h->ev.push_back(e); }
   }
-  // The host only needs to know WHEN every trajectory has finished: it enqueues CHECK_EVERY batch steps back to back
-  // and reads the per-step "still active" counters once per chunk.  The read-back is pipelined: chunk g+1 is already
-  // enqueued when the host waits for the counters of chunk g, so the GPU never idles on the round trip; the price is at
-  // most one chunk of launches whose kernels find nothing to do (kernels of finished trajectories exit at once).
-  constexpr int CHECK_EVERY = 4;
-  const hipEvent_t cev[2] = {h->sev[2], h->sev[3]};
-  int launched = 0, checked = 0, nchunks = 0, last_active = P.B;
-  bool done = false;
   h->prog_active = P.B; h->prog_steps = 0;
-  const bool dbg_sync = std::getenv("TRAJOPT_SYNC_DEBUG") != nullptr;
-  auto enqueue_chunk = [&]() -> int {
-    const int chunk = std::min(CHECK_EVERY, max_steps - launched);
-    for (int c = 0; c < chunk; ++c) {
-      const int step = launched + c;
-      a.step = step;
-      if (h->profile) HIPCHECK(hipEventRecord(h->ev[4 * step + 0], h->stream));
-      // what this step launches (path_plan.h), from the last active count the host has seen (results do not depend on it)
-      const PathPlan& pl = h->plan;
-      const StepPlan sp = plan_step(pl, h->traits, a.h_diag, P.expand_variant, a.compact, last_active, P.B, plants(h) != 0);
-      if (sp.kind == STEP_SPLIT) TRY(launch_expand(h));
-      if (h->profile) HIPCHECK(hipEventRecord(h->ev[4 * step + 1], h->stream));
-      switch (sp.kind) {
-        case STEP_FUSED_LANE: TRY(h->ops->expand_backward(h)); break;
-        case STEP_SCAN: TRY(h->ops->expand_backward_scan(h)); break;
-        case STEP_FUSED_COOP: TRY(h->ops->expand_backward_coop(h)); break;
-        case STEP_SPLIT: TRY(launch_backward(h)); break;
-      }
-      if (h->profile) HIPCHECK(hipEventRecord(h->ev[4 * step + 2], h->stream));
-      a.CW = sp.CW; a.TW = sp.TW; a.store_x = sp.store_x;
-      h->list_active = last_active;  // (list mode: the forward pass's grid)
-      if (sp.two_launch) {  // launch A — one round for everybody; flags -> list; launch B — the rest of the search for the flagged ones; the accept
-        const int cw0 = a.CW, tw0 = a.TW, dump0 = a.dump_wave;
-        a.dump_wave = pl.ls2_dump;
-        a.CW = pl.ls2_cwa; a.TW = 64 / pl.ls2_cwa; a.ls_phase = 1; a.blk0 = 0;
-        TRY(launch_forward(h, false, false));
-        TRY(launch_flag_list(h));
-        a.CW = pl.ls2_cwb; a.TW = 64 / pl.ls2_cwb; a.ls_phase = 2; a.ls_c0 = pl.ls2_cwa; a.blk0 = pl.ls2_blkA;
-        TRY(launch_forward(h, false, false));
-        a.ls_phase = 0; a.blk0 = 0; a.CW = cw0; a.TW = tw0; a.dump_wave = dump0;
-        TRY(launch_accept(h));
-      } else
-      TRY(launch_forward(h, !h->ops->write_through || !a.store_x, sp.two_wave));
-      a.store_x = 1;
-      if (al_mode) TRY(launch_outer(h));
-      if (a.compact) TRY(launch_compact(h));
-      if (h->profile) HIPCHECK(hipEventRecord(h->ev[4 * step + 3], h->stream));
-      if (h->guard) {
-        if (step == 0) if (const char* env = std::getenv("TRAJOPT_GUARD_SELFTEST")) if (std::atoi(env))  // one double behind the nominal states
-          enqueue(k_guard_poke, dim3(1), dim3(1), 0, h->stream, a.Xs, (long long)P.N * P.n * (P.Bp + 64) + 3);
-        TRY(check_guards(h, ("batch step " + std::to_string(step) + " of a solve").c_str()));
-      }
-      if (dbg_sync) {  // TRAJOPT_SYNC_DEBUG=1: localise a device fault to a batch step
-        const hipError_t e = hipStreamSynchronize(h->stream);
-        std::fprintf(stderr, "[sync-debug] step %d B=%d Bp=%d level=%d store_x-path=%d: %s\n", step, a.P.B, a.P.Bp, h->rp_level, (int)(last_active), hipGetErrorString(e));
-        if (e != hipSuccess) return fail(TO_ERR_HIP, "device fault (sync debug)");
-      }
-    }
-    HIPCHECK(hipMemcpyAsync(&h->counter_host[launched], &a.counter[launched], sizeof(int) * chunk, hipMemcpyDeviceToHost, h->stream));
-    HIPCHECK(hipEventRecord(cev[nchunks & 1], h->stream));
-    launched += chunk;
-    ++nchunks;
-    return TO_OK;
-  };
-  int waited = 0;  // chunks whose counters have been inspected
-  // early polish (ALTRO solves): the next active count at which the finished trajectories are handed over
-  int early_div = 4;  // hand-over when a quarter of the batch is left (TRAJOPT_PN_EARLY_AT: the divisor)
-  if (const char* env = std::getenv("TRAJOPT_PN_EARLY_AT")) early_div = std::max(1, std::atoi(env));
-  int early_thr = (al_mode && h->pn_early > 0) ? P.B / early_div : -1, early_left = h->pn_early;
-  bool snapshot_pending = false;
+  // the driver loop: every decision is SolveLoop's (solve_loop.h); here each operation it names is performed and its outcome reported back
+  const hipEvent_t cev[QUEUE_EVENTS] = {h->sev[2], h->sev[3]};
+  SolveLoopConfig cfg;
+  cfg.max_steps = max_steps; cfg.B = P.B; cfg.al_mode = al_mode;
   // repacked working set (above): iLQR solves of the small models on the fused lane path with compaction
-  bool repack = !al_mode && a.compact && working_set_repack(h->plan, h->traits, plants(h) != 0);
-  if (max_steps > 0) TRY(enqueue_chunk());
-  while (!done && waited < nchunks) {
-    if (repack && last_active >= 1 && (double)last_active <= h->plan.rp_at * (double)a.P.B && a.P.B >= h->plan.rp_min) {
-      // the exact count is needed on the host (B of every later launch): drain the queue once — a handful of times per solve
-      HIPCHECK(hipStreamSynchronize(h->stream));
-      for (; checked < launched; ++checked) {
-        ++steps;
-        last_active = h->counter_host[checked];
-        if (last_active == 0) { done = true; break; }
-      }
-      waited = nchunks;
-      publish_progress(h, last_active, steps);
-      if (done) break;
-      a.step = launched - 1;   // (k_compact of that step built the list the move reads)
-      {
-        const int mrc = rp_move(h, last_active);
-        if (mrc > 0) repack = false;  // declined (out of memory): no further attempts in this solve
-        else TRY(mrc);
-        if (h->guard) TRY(check_guards(h, "a move into a repacked working set"));
-      }
-      if (launched < max_steps) TRY(enqueue_chunk());
-      continue;
+  cfg.repack = a.compact && working_set_repack(h->plan, h->traits, plants(h) != 0);
+  cfg.rp_at = h->plan.rp_at; cfg.rp_min = h->plan.rp_min;
+  cfg.early = h->pn_early; cfg.early_div = knobs.pn_early_at;  // early polish (ALTRO solves)
+  SolveLoop lp(cfg);
+  for (LoopOp op = lp.next(); op.kind != OP_FINISH; op = lp.next()) switch (op.kind) {
+    case OP_CHUNK:
+      h->list_active = op.last_active;  // (list mode: the forward pass's grid)
+      for (int step = op.step; step < op.step + op.n; ++step)  // what each step launches, from the last active count the host has seen (results do not depend on it)
+        TRY(batch_step(h, step, plan_step(h->plan, h->traits, a.h_diag, P.expand_variant, a.compact, op.last_active, op.B, plants(h) != 0)));
+      break;
+    case OP_COPY:
+      HIPCHECK(hipMemcpyAsync(&h->counter_host[op.step], &a.counter[op.step], sizeof(int) * op.n, hipMemcpyDeviceToHost, h->stream));
+      HIPCHECK(hipEventRecord(cev[op.event], h->stream));
+      break;
+    case OP_WAIT: HIPCHECK(hipEventSynchronize(cev[op.event])); break;
+    case OP_DRAIN: HIPCHECK(hipStreamSynchronize(h->stream)); break;
+    case OP_CONSUME:
+      lp.consume(h->counter_host, op);
+      publish_progress(h, lp.last_active, lp.steps);
+      break;
+    case OP_MOVE: {
+      a.step = op.step;   // (k_compact of that step built the list the move reads)
+      const int mrc = rp_move(h, op.n);
+      if (mrc <= 0) TRY(mrc);
+      lp.moved(mrc == 0);  // (> 0: declined, out of memory)
+      if (h->guard) TRY(check_guards(h, "a move into a repacked working set"));
+      break;
     }
-    if (launched < max_steps) TRY(enqueue_chunk());  // keep the queue one chunk ahead
-    if (snapshot_pending) {  // taken before that chunk: the device keeps working while the host lists and launches
-      TRY(early_polish_launch(h));
-      snapshot_pending = false;
-    }
-    HIPCHECK(hipEventSynchronize(cev[waited & 1]));
-    const int upto = std::min(launched, (waited + 1) * CHECK_EVERY);
-    for (; checked < upto; ++checked) {
-      ++steps;
-      last_active = h->counter_host[checked];
-      if (h->counter_host[checked] == 0) { done = true; break; }
-    }
-    ++waited;
-    publish_progress(h, last_active, steps);
-    if (!done && early_left > 0 && last_active <= early_thr) {
-      TRY(early_polish_snapshot(h));
-      snapshot_pending = true;
-      --early_left;
-      while (early_thr > 0 && last_active <= early_thr) early_thr /= 2;
-    }
+    case OP_SNAPSHOT: TRY(early_polish_snapshot(h)); break;
+    case OP_POLISH: TRY(early_polish_launch(h)); break;
+    case OP_FINISH: break;
   }
+  const int steps = lp.steps;
   TRY(launch_accept(h));  // trajectories keep the slot of their last accepted step until here
   a.CW = h->plan.cw_base; a.TW = h->plan.tw_base;
   TRY(rp_finish(h, true));  // a repacked working set goes home
