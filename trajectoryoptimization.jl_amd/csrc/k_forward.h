@@ -50,6 +50,20 @@ __device__ __forceinline__ void stage_gains(const double* Kt, int b, int TW, int
   typedef __attribute__((address_space(1))) const void* gptr_t;
   typedef __attribute__((address_space(3))) void* lptr_t;
   const int pieces = TW * PCS;
+#ifdef TO_POLICY_HOST  // host build of k_policy.h (tests/host_shim/policy_harness.cpp): lanes run one after another there, so whichever lane
+                       // gets here copies the pieces of all 64 — the same rows to the same LDS offsets as the DMA; the trajectory of row t
+                       // comes from the lane map (TO_POLICY_HOST_LANE_B(t): what lane t of the wave holds)
+  (void)b; (void)hw;
+  for (int i0 = 0; i0 < pieces; i0 += 64)
+    for (int hl = 0; hl < 64; ++hl) {
+      const int gl = i0 + hl;
+      int t = gl / PCS;
+      const int off = gl - t * PCS;
+      t = t < TW ? t : TW - 1;
+      const int bt = TO_POLICY_HOST_LANE_B(t);
+      std::memcpy((char*)kbuf + (size_t)(i0 + hl) * 16, (const char*)(Kt + ((size_t)bt * (N - 1) + k) * RSK) + off * 16, 16);
+    }
+#else
   for (int i0 = 0; i0 < pieces; i0 += 64) {
     const int gl = i0 + hw;
     int t = gl / PCS;
@@ -59,6 +73,7 @@ __device__ __forceinline__ void stage_gains(const double* Kt, int b, int TW, int
     const char* src = (const char*)(Kt + ((size_t)bt * (N - 1) + k) * RSK) + off * 16;
     __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)((char*)kbuf + (size_t)i0 * 16), 16, 0, 0);
   }
+#endif
 }
 template <class M>
 __host__ __device__ inline int gains_lds_doubles(int TW) {  // per buffer, whole DMA instructions

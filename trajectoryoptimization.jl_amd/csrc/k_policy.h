@@ -25,6 +25,19 @@
 #include "k_forward.h"
 #include "noise.h"
 
+// TO_POLICY_HOST (tests/host_shim/policy_harness.cpp compiles this file for the host and runs the kernel thread by thread): the wave's LDS is
+// a heap block of exactly the launch's dynamic-LDS bytes (TO_POLICY_HOST_LDS), the DMA of stage_gains a copy that has landed when it returns
+// (k_forward.h) and plant parameters stay where they are.  Without the macro nothing below differs from the device text.
+#ifdef TO_POLICY_HOST
+#define TO_POLICY_LDS(name) double* const name = TO_POLICY_HOST_LDS
+#define TO_POLICY_GAINS_LANDED() ((void)0)
+#define TO_POLICY_IN_VGPR(x) (x)
+#else
+#define TO_POLICY_LDS(name) extern __shared__ double name[]
+#define TO_POLICY_GAINS_LANDED() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
+#define TO_POLICY_IN_VGPR(x) in_vgpr(x)
+#endif
+
 namespace to {
 
 template <bool SC>
@@ -73,7 +86,7 @@ __global__ void __launch_bounds__(64) k_policy_rollout(KArgs a, PolicyArgs pa) {
   constexpr int n = M::n, m = M::m, ne = M::ne, RSK = Gains<M>::RSK;
   constexpr bool KLDS = M::lds_gains;
   constexpr bool KSC = UNIFORM && !KLDS && RSK <= 12;
-  extern __shared__ double kbuf[];
+  TO_POLICY_LDS(kbuf);
   const DevProblem& P = a.P;
   const int N = P.N, S = pa.S, hw = threadIdx.x;
   const int g = pa.g0 + blockIdx.x;
@@ -105,7 +118,7 @@ __global__ void __launch_bounds__(64) k_policy_rollout(KArgs a, PolicyArgs pa) {
     for (int i = 0; i < 16; ++i) mp[i] = pp[i];
   } else {
 #pragma unroll
-    for (int i = 0; i < 16; ++i) mp[i] = in_vgpr(pa.mp[i]);
+    for (int i = 0; i < 16; ++i) mp[i] = TO_POLICY_IN_VGPR(pa.mp[i]);
   }
   // counter of this lane's draws (noise.h): the GLOBAL trajectory and sample, so that neither the lane map nor a split of the batch
   // over handles or of the samples over calls changes a draw
@@ -128,7 +141,7 @@ __global__ void __launch_bounds__(64) k_policy_rollout(KArgs a, PolicyArgs pa) {
   double J = 0.0, cm = 0.0, dxm = 0.0;
   int lim = 0, klim = 0;
   for (int k = 0; k < N - 1; ++k) {
-    if constexpr (KLDS) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this knot's gains row has landed in LDS
+    if constexpr (KLDS) TO_POLICY_GAINS_LANDED();  // this knot's gains row has landed in LDS
     const PolicyKnot<M, UNIFORM, KSC, !KLDS> cur = nxt;
     const double* kcur = kbuf + (size_t)(k & 1) * kbuf_len + krow;
     // the next knot's nominal and gains are requested first: nothing issued here is needed before the next iteration
@@ -213,7 +226,7 @@ __global__ void __launch_bounds__(64) k_policy_rollout(KArgs a, PolicyArgs pa) {
     J += knot_cost<M, true>(P, N - 1, xb, u0, nullptr, nullptr, false, gl0, cp0);
     if (has_cons) { const double v = knot_violation<M>(P, N - 1, xb, u0, cp0, cl0); if (!(v <= cm)) cm = v; }
   }
-  if constexpr (KLDS) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  if constexpr (KLDS) TO_POLICY_GAINS_LANDED();
   if (live) {
     const double inf = __builtin_inf();
     pa.J[c] = lim ? inf : J;

@@ -251,7 +251,8 @@ int op_accept_roll(to_handle* h) {
 template <class M, int NZ = 0>
 int op_policy_rollout(to_handle* h, const PolicyArgs& pa, int waves) {
   const bool uniform = pa.TPW == 0;
-  const size_t lds = M::lds_gains ? sizeof(double) * 2 * gains_lds_doubles<M>(uniform ? 1 : pa.TPW) : 0;  // two gains buffers
+  const size_t lds = policy_lds_bytes(M::lds_gains ? Gains<M>::RSK / 2 : 0, uniform ? 1 : pa.TPW);  // two gains buffers (path_plan.h)
+  static_assert(!M::lds_gains || Gains<M>::RSK % 2 == 0, "gains rows must be whole 16-byte pieces");
   return with_integrator<M>(h, [&](auto fi) {
     return with_time_steps<M, (NZ & 4) != 0>(h, [&](auto dt) {  // (a handle with per-trajectory time steps runs a one-plant-per-sample instance)
       return with_weights<M>(h, [&](auto gw) {  // (... and one with per-trajectory cost weights the instance that reads them for J)

@@ -320,6 +320,77 @@ inline int forward_mode(bool simple_stage, bool has_cons, bool rk4, bool general
   if (!has(mode)) mode = (mode | 8) & ~1 & ~16;  // the general variant (any cost kind, stage cost read per knot): a superset
   return has(mode) ? mode : -1;
 }
+// ---- closed-loop policy rollouts and the receding-horizon step (k_policy.h, k_mpc.h): every size their entry points give a buffer --------
+// One routine for to_policy_rollout, to_policy_rollout_mc and to_mpc_advance (trajopt_hip.hip policy_prepare / policy_staging) and for the
+// launcher (ops.h op_policy_rollout: the LDS bytes); tests/host_shim/policy_harness.cpp allocates every array of the host build of the kernels
+// with exactly these lengths, so a length that is too short here is a heap overflow there.  Lengths are in elements, not bytes.
+// LDS of one policy wave: two gains buffers of whole DMA instructions (k_forward.h gains_lds_doubles; pieces = 16-byte pieces of one gains
+// row, 0 for the models whose gains travel in registers), TW rows each.
+inline size_t policy_lds_bytes(int gains_pieces, int TW) {
+  return gains_pieces ? sizeof(double) * 2 * (size_t)(((TW * gains_pieces + 63) / 64) * 64 * 2) : 0;
+}
+struct PolicyPlan {
+  bool packed = true;         // lane map: packed (a wave = TPW trajectories x S samples) or uniform (a wave = 64 samples of one trajectory)
+  int TPW = 0, WPT = 1;       // PolicyArgs::TPW (0: uniform), WPT
+  long long waves = 0;        // waves over the whole batch
+  size_t SB = 0;              // samples
+  size_t x0s_len = 0;         // pol_x0s: [n, S, B]
+  size_t sample_len = 0;      // pol_J, pol_cmax, pol_dxmax, pol_status, pol_klim: one entry per sample
+  size_t plants_len = 0;      // pol_plants: [16, S*B]
+  size_t Lx = 0, Lu = 0;      // elements of one trajectory's states / controls
+  long long chunk = 0;        // waves of one staging chunk
+  size_t xw_len = 0, uw_len = 0;  // the staging pair of one chunk: [chunk][Lx][64], [chunk][Lu][64]
+  size_t rollout_stage_len = 0;   // to_policy_rollout with trajectories: host-layout staging of one chunk (h->stage)
+  size_t lds_bytes = 0;       // dynamic LDS of one wave
+};
+// map_env / chunk_env: TRAJOPT_POLICY_MAP (null where the caller forces the packed map: to_mpc_advance) and TRAJOPT_POLICY_CHUNK_WAVES as the
+// environment has them (null: unset)
+inline PolicyPlan plan_policy(int n, int m, int N, int B, int S, const char* map_env, const char* chunk_env, int gains_pieces) {
+  PolicyPlan p;
+  // lane map: packed while a wave holds at least two trajectories, one trajectory per wave beyond (TRAJOPT_POLICY_MAP=packed forces the
+  // per-lane body up to S = 64: the A/B of tools/policy_rollout_probe.py)
+  p.packed = S <= 32;
+  if (map_env) {
+    if (!std::strcmp(map_env, "packed") && S <= 64) p.packed = true;
+    if (!std::strcmp(map_env, "uniform")) p.packed = false;
+  }
+  p.TPW = p.packed ? 64 / S : 0; p.WPT = (S + 63) / 64;
+  p.waves = p.packed ? ((long long)B + p.TPW - 1) / p.TPW : (long long)B * p.WPT;
+  p.SB = (size_t)S * B;
+  p.x0s_len = p.SB * n; p.sample_len = p.SB; p.plants_len = p.SB * 16;
+  p.Lx = (size_t)N * n; p.Lu = (size_t)(N - 1) * m;
+  // The closed-loop trajectories go through a bounded staging pair, a chunk of waves at a time (sample-fastest blocks [wave - g0][e][64]):
+  // 32 MiB, whatever S * B * N is.  TRAJOPT_POLICY_CHUNK_WAVES overrides the chunk (tests of the chunked path).
+  p.chunk = std::max<long long>(1, (32ll << 20) / (long long)(64 * (p.Lx + p.Lu) * sizeof(double)));
+  if (chunk_env) p.chunk = std::max(1, std::atoi(chunk_env));
+  p.chunk = std::min<long long>(p.chunk, p.waves);
+  p.xw_len = (size_t)p.chunk * p.Lx * 64; p.uw_len = (size_t)p.chunk * p.Lu * 64;
+  p.rollout_stage_len = (size_t)p.chunk * 64 * (p.Lx + p.Lu);
+  p.lds_bytes = policy_lds_bytes(gains_pieces, p.packed ? p.TPW : 1);
+  return p;
+}
+// sample index of lane 0 of wave g (the waves enumerate the samples in order): what a chunk of waves [g0, g0 + ng) hands to the caller
+inline long long policy_first_sample(const PolicyPlan& p, int S, long long g) {
+  if (g >= p.waves) return (long long)p.SB;
+  if (p.packed) return std::min<long long>((long long)p.SB, g * p.TPW * (long long)S);
+  const long long b = g / p.WPT, w = g - b * p.WPT;
+  return b * S + w * 64;
+}
+// to_mpc_advance: the host-layout gather of one call, [x_next n B][X_applied n (s+1) B][U_applied m s B] in h->stage, and the row groups
+// (grid.y) of k_mpc_writeback
+struct MpcPlan {
+  size_t cx = 0, cX = 0, cU = 0;  // lengths, and with them the offsets 0, cx, cx + cX
+  size_t stage_len = 0;
+  int row_groups = 1;
+};
+inline MpcPlan plan_mpc(int n, int m, int N, int B, int s) {
+  MpcPlan p;
+  p.cx = (size_t)n * B; p.cX = (size_t)n * (s + 1) * B; p.cU = (size_t)m * s * B;
+  p.stage_len = p.cx + p.cX + p.cU;
+  p.row_groups = std::min(std::max((N - 1) * m, (s + 1) * n), 32);
+  return p;
+}
+
 // Stream compaction of Bp flags (k_generic.h): one workgroup up to COMPACT_ONE_LAUNCH, else count + write launches of nb <= 256
 // workgroups, each owning `per` flags (a multiple of 1024, at most 64 slices of 1024).  false: the batch is too large (> 16 777 216).
 constexpr int COMPACT_ONE_LAUNCH = 16384;

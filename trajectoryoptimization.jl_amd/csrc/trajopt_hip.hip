@@ -1672,6 +1672,7 @@ struct PolicyRun {
   bool packed = true;  // lane map
   int waves = 0;
   size_t SB = 0;
+  PolicyPlan plan;     // every length below comes from here (path_plan.h plan_policy)
   std::vector<double> own_plants;  // the handle's per-trajectory plants repeated per sample (alive until the entry point returns)
 };
 static int policy_launch(to_handle* h, const PolicyRun& r, const PolicyArgs& a, int w) {
@@ -1733,20 +1734,14 @@ static int policy_prepare(to_handle* h, int32_t S, const to_policy_opts* opts, c
   }
   if (nz && (!h->ops->policy_rollout_mc || (nz & ~h->ops->policy_noise_mask)))
     return fail(TO_ERR_UNSUPPORTED, "to_policy_rollout_mc: not compiled for this model");
-  // lane map: packed while a wave holds at least two trajectories, one trajectory per wave beyond (TRAJOPT_POLICY_MAP=packed forces the
-  // per-lane body up to S = 64: the A/B of tools/policy_rollout_probe.py)
-  bool packed = S <= 32;
-  if (!force_packed)
-    if (const char* env = std::getenv("TRAJOPT_POLICY_MAP")) {
-      if (!std::strcmp(env, "packed") && S <= 64) packed = true;
-      if (!std::strcmp(env, "uniform")) packed = false;
-    }
-  run->packed = packed;
-  pa.S = S; pa.TPW = packed ? 64 / S : 0; pa.WPT = (S + 63) / 64;
-  const long long waves_ll = packed ? ((long long)B + pa.TPW - 1) / pa.TPW : (long long)B * pa.WPT;
-  if (waves_ll > 0x7fffffffLL / 64) return fail(TO_ERR_ARGUMENT, "to_policy_rollout: S * B is too large for one call");
-  run->waves = (int)waves_ll;
-  const size_t SB = run->SB = (size_t)S * B;
+  // lane map, waves and every buffer length: path_plan.h plan_policy
+  const PolicyPlan& pl = run->plan = plan_policy(n, m, P.N, B, S, force_packed ? nullptr : std::getenv("TRAJOPT_POLICY_MAP"),
+                                                 std::getenv("TRAJOPT_POLICY_CHUNK_WAVES"), h->ops->lds_gains ? h->ops->gains_lds_pieces : 0);
+  run->packed = pl.packed;
+  pa.S = S; pa.TPW = pl.TPW; pa.WPT = pl.WPT;
+  if (pl.waves > 0x7fffffffLL / 64) return fail(TO_ERR_ARGUMENT, "to_policy_rollout: S * B is too large for one call");
+  run->waves = (int)pl.waves;
+  const size_t SB = run->SB = pl.SB;
   pa.alpha = o.alpha;
   pa.clamp = (o.u_min || o.u_max) ? 1 : 0;
   for (int j = 0; j < TO_MAX_M; ++j) {
@@ -1762,9 +1757,9 @@ static int policy_prepare(to_handle* h, int32_t S, const to_policy_opts* opts, c
     dev_release(h, &h->pol_x0s); dev_release(h, &h->pol_J); dev_release(h, &h->pol_cmax); dev_release(h, &h->pol_dxmax);
     dev_release(h, &h->pol_status); dev_release(h, &h->pol_klim);
     h->pol_cap = 0;
-    TRY(dev_alloc(h, &h->pol_x0s, SB * n, false));
-    TRY(dev_alloc(h, &h->pol_J, SB, false)); TRY(dev_alloc(h, &h->pol_cmax, SB, false)); TRY(dev_alloc(h, &h->pol_dxmax, SB, false));
-    TRY(dev_alloc(h, &h->pol_status, SB, false)); TRY(dev_alloc(h, &h->pol_klim, SB, false));
+    TRY(dev_alloc(h, &h->pol_x0s, pl.x0s_len, false));
+    TRY(dev_alloc(h, &h->pol_J, pl.sample_len, false)); TRY(dev_alloc(h, &h->pol_cmax, pl.sample_len, false)); TRY(dev_alloc(h, &h->pol_dxmax, pl.sample_len, false));
+    TRY(dev_alloc(h, &h->pol_status, pl.sample_len, false)); TRY(dev_alloc(h, &h->pol_klim, pl.sample_len, false));
     h->pol_cap = SB;
   }
   pa.x0s = h->pol_x0s; pa.J = h->pol_J; pa.cmax = h->pol_cmax; pa.dxmax = h->pol_dxmax; pa.status = h->pol_status; pa.klim = h->pol_klim;
@@ -1773,27 +1768,23 @@ static int policy_prepare(to_handle* h, int32_t S, const to_policy_opts* opts, c
       HIPCHECK(hipStreamSynchronize(h->stream));
       dev_release(h, &h->pol_plants);
       h->pol_plants_cap = 0;
-      TRY(dev_alloc(h, &h->pol_plants, SB * 16, false));
+      TRY(dev_alloc(h, &h->pol_plants, pl.plants_len, false));
       h->pol_plants_cap = SB;
     }
     pa.plants = h->pol_plants;
-    HIPCHECK(hipMemcpyAsync(h->pol_plants, plants_src, SB * 16 * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHECK(hipMemcpyAsync(h->pol_plants, plants_src, pl.plants_len * sizeof(double), hipMemcpyHostToDevice, h->stream));
   }
   return TO_OK;
 }
-// The closed-loop trajectories go through a bounded staging pair, a chunk of waves at a time (sample-fastest blocks [wave - g0][e][64]):
-// 32 MiB, whatever S * B * N is.  TRAJOPT_POLICY_CHUNK_WAVES overrides the chunk (tests of the chunked path).  Sets pa.store / Xw / Uw.
+// The closed-loop trajectories go through a bounded staging pair, a chunk of waves at a time (path_plan.h plan_policy: chunk, xw_len, uw_len).
+// Sets pa.store / Xw / Uw.
 static int policy_staging(to_handle* h, PolicyRun* run, long long* chunk_out) {
-  const DevProblem& P = h->a.P;
-  const size_t Lx = (size_t)P.N * P.n, Lu = (size_t)(P.N - 1) * P.m;
-  long long chunk = std::max<long long>(1, (32ll << 20) / (long long)(64 * (Lx + Lu) * sizeof(double)));
-  if (const char* env = std::getenv("TRAJOPT_POLICY_CHUNK_WAVES")) chunk = std::max(1, std::atoi(env));
-  chunk = std::min<long long>(chunk, run->waves);
+  const long long chunk = run->plan.chunk;
   if (h->pol_waves < chunk) {
     HIPCHECK(hipStreamSynchronize(h->stream));
     dev_release(h, &h->pol_xw); dev_release(h, &h->pol_uw);
     h->pol_waves = 0;
-    TRY(dev_alloc(h, &h->pol_xw, (size_t)chunk * Lx * 64, false)); TRY(dev_alloc(h, &h->pol_uw, (size_t)chunk * Lu * 64, false));
+    TRY(dev_alloc(h, &h->pol_xw, run->plan.xw_len, false)); TRY(dev_alloc(h, &h->pol_uw, run->plan.uw_len, false));
     h->pol_waves = (int)chunk;
   }
   run->pa.store = 1; run->pa.Xw = h->pol_xw; run->pa.Uw = h->pol_uw;
@@ -1817,24 +1808,18 @@ static int policy_rollout_impl(to_handle* h, int32_t S, const double* x0s, const
   PolicyRun run;
   TRY(policy_prepare(h, S, opts, noise, false, &run));
   PolicyArgs& pa = run.pa;
-  const DevProblem& P = h->a.P;
-  const int n = P.n, m = P.m, N = P.N, waves = run.waves;
+  const int waves = run.waves;
   const size_t SB = run.SB;
-  HIPCHECK(hipMemcpyAsync(h->pol_x0s, x0s, SB * n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  HIPCHECK(hipMemcpyAsync(h->pol_x0s, x0s, run.plan.x0s_len * sizeof(double), hipMemcpyHostToDevice, h->stream));
   if (!out->X && !out->U) {
     TRY(policy_launch(h, run, pa, waves));
   } else {
     // trajectories: each chunk of waves is transposed to host layout in the staging buffer and downloaded: only the caller's arrays grow with S * B * N
-    const size_t Lx = (size_t)N * n, Lu = (size_t)(N - 1) * m;
+    const size_t Lx = run.plan.Lx, Lu = run.plan.Lu;
     long long chunk = 0;
     TRY(policy_staging(h, &run, &chunk));
-    TRY(ensure_stage(h, (size_t)chunk * 64 * (Lx + Lu) * sizeof(double)));
-    auto first_sample = [&](long long g) -> long long {  // sample index of lane 0 of wave g (the waves enumerate the samples in order)
-      if (g >= waves) return (long long)SB;
-      if (run.packed) return std::min<long long>((long long)SB, g * pa.TPW * (long long)S);
-      const long long b = g / pa.WPT, w = g - b * pa.WPT;
-      return b * S + w * 64;
-    };
+    TRY(ensure_stage(h, run.plan.rollout_stage_len * sizeof(double)));
+    auto first_sample = [&](long long g) { return policy_first_sample(run.plan, S, g); };
     for (long long g0 = 0; g0 < waves; g0 += chunk) {
       const int ng = (int)std::min<long long>(chunk, waves - g0);
       pa.g0 = (int)g0;
@@ -1901,8 +1886,9 @@ int to_mpc_advance(to_handle* h, const double* x_meas, const to_mpc_opts* mpc, c
   long long chunk = 0;
   TRY(policy_staging(h, &run, &chunk));
   // host-layout gather of the call: [x_next n B][X_applied n (s+1) B][U_applied m s B], the parts the caller asked for
-  const size_t cx = (size_t)n * B, cX = (size_t)n * (s + 1) * B, cU = (size_t)m * s * B;
-  TRY(ensure_stage(h, (cx + cX + cU) * sizeof(double)));
+  const MpcPlan mp = plan_mpc(n, m, N, B, s);
+  const size_t cx = mp.cx, cX = mp.cX, cU = mp.cU;
+  TRY(ensure_stage(h, mp.stage_len * sizeof(double)));
   ma.n = n; ma.m = m; ma.N = N; ma.B = B; ma.s = s; ma.guess = mpc->guess; ma.tail = mpc->tail;
   ma.Xw = h->pol_xw; ma.Uw = h->pol_uw; ma.status = h->pol_status; ma.x0 = h->a.x0; ma.Us = h->a.Us;
   ma.x_next = (out && out->x_next) ? h->stage : nullptr;
@@ -1910,12 +1896,11 @@ int to_mpc_advance(to_handle* h, const double* x_meas, const to_mpc_opts* mpc, c
   ma.U_applied = (out && out->U_applied) ? h->stage + cx + cX : nullptr;
   if (x_meas) HIPCHECK(hipMemcpyAsync(h->pol_x0s, x_meas, cx * sizeof(double), hipMemcpyHostToDevice, h->stream));
   else enqueue(k_mpc_x0_in, dim3((unsigned)waves), dim3(BLOCK), 0, h->stream, (const double*)h->a.x0, h->pol_x0s, n, B);
-  const int rows = std::max((N - 1) * m, (s + 1) * n);
   for (long long g0 = 0; g0 < waves; g0 += chunk) {
     const int ng = (int)std::min<long long>(chunk, waves - g0);
     pa.g0 = ma.g0 = (int)g0;
     TRY(policy_launch(h, run, pa, ng));
-    enqueue(k_mpc_writeback, dim3((unsigned)ng, (unsigned)std::min(rows, 32)), dim3(BLOCK), 0, h->stream, ma);
+    enqueue(k_mpc_writeback, dim3((unsigned)ng, (unsigned)mp.row_groups), dim3(BLOCK), 0, h->stream, ma);
     if (ma.guess == TO_MPC_GUESS_NOMINAL) enqueue(k_mpc_shift_nominal, dim3((unsigned)ng), dim3(BLOCK), 0, h->stream, ma);
     TRY(launched());
   }
