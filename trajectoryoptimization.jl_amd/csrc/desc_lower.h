@@ -1,5 +1,6 @@
 // desc_lower.h — host-side lowering of the C-ABI descriptors (include/trajopt_hip.h): solver-option defaults and validation,
-// model dimensions, constraint descriptors -> DevCon (selector tables), cost validation.  Pure host C++ (no HIP calls): shared
+// model dimensions, constraint descriptors -> DevCon (selector tables), cost validation, the whole problem (lower_problem: to_create), and the
+// host half of every per-trajectory setter.  Pure host C++ (no HIP calls): shared
 // by the library (trajopt_hip.hip) and by the host build of the projected-Newton kernel that the CPU test-suite runs
 // (tests/host_shim/pn_harness.cpp).  Mirrors the reference's constructors: Problem src/problem.jl:44-72, add_constraint!
 // src/constraint_list.jl:103-134, BoundConstraint src/constraints.jl:660-687, NormConstraint :442-455.
@@ -8,6 +9,7 @@
 #include <cmath>
 #include <cstring>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "models.h"
@@ -610,6 +612,152 @@ inline int validate_cost(int n, int rot, const to_cost_desc& c) {
     if (rot > TO_ROT_QUATERNION) return fail(TO_ERR_ARGUMENT, "DiagonalQuatCost needs a state that carries a unit quaternion");
     for (int i = 0; i < 4; ++i) if (c.q_ind[i] < 1 || c.q_ind[i] > n) return fail(TO_ERR_DIMENSION_MISMATCH, "quat_ind outside the state");
   }
+  return TO_OK;
+}
+
+// The whole problem descriptor (to_create): every check and every host table, before the entry point asks for a device.  A refused call leaves
+// *out untouched (as with every routine below).
+struct LoweredProblem {
+  int n = 0, m = 0, ne = 0, key = -1;
+  std::vector<double> dt, step_table;  // [N-1]; TO_MODEL_VECTOR: the per-step model table (models.h ModelVectorModel), else empty
+  std::vector<int> cost_index;         // [N]
+  std::vector<DevCon> cons;
+  long long n_duals = 0;
+};
+inline int lower_problem(const to_problem_desc* desc, const to_solver_opts* opts /* may be NULL */, LoweredProblem* out) {
+  if (!desc) return fail(TO_ERR_NULL, "null descriptor");
+  if (desc->abi_version != TO_ABI_VERSION) return fail(TO_ERR_ARGUMENT, "ABI version mismatch");
+  if (opts) if (int r = validate_opts(*opts)) return r;
+  LoweredProblem lp;
+  int& n = lp.n; int& m = lp.m;
+  if (model_dims(desc->model, desc->model_params, &n, &m, &lp.ne, &lp.key)) return fail(TO_ERR_UNSUPPORTED, "unknown model");
+  if (desc->n != n || desc->m != m) return fail(TO_ERR_DIMENSION_MISMATCH, "Objective state/control dimensions don't match model.");  // src/problem.jl:65-68
+  if (desc->N < 2) return fail(TO_ERR_ASSERTION, "length(models) == N-1 requires N >= 2");                                         // src/problem.jl:49
+  if (desc->B < 1) return fail(TO_ERR_ARGUMENT, "batch must be positive");
+  if (!(desc->tf > desc->t0)) return fail(TO_ERR_ASSERTION, "tf > t0");                                                             // src/problem.jl:50
+  if (desc->integrator < TO_RK4 || desc->integrator > TO_EULER) return fail(TO_ERR_UNSUPPORTED, "unknown integrator");
+  const int N = desc->N;
+  std::vector<double>& dt = lp.dt;
+  dt.resize(N - 1);
+  if (desc->dt) {
+    double s = 0;
+    for (int k = 0; k < N - 1; ++k) { dt[k] = desc->dt[k]; s += dt[k]; if (!(dt[k] > 0)) return fail(TO_ERR_ASSERTION, "dt must be positive"); }
+    if (std::fabs(s - (desc->tf - desc->t0)) > 1e-8 * std::fmax(1.0, std::fabs(desc->tf - desc->t0)))
+      return fail(TO_ERR_ASSERTION, "time(Z[end]) ≈ tf: time steps are inconsistent with the final time");                          // src/problem.jl:52
+  } else {
+    for (int k = 0; k < N - 1; ++k) dt[k] = (desc->tf - desc->t0) / (N - 1);
+  }
+  if (desc->n_costs < 1 || !desc->costs) return fail(TO_ERR_ARGUMENT, "objective needs at least one cost function");
+  const int rot = desc->model == TO_MODEL_QUADROTOR ? (int)desc->model_params[10] : -1;
+  for (int i = 0; i < desc->n_costs; ++i) if (int r = validate_cost(n, rot, desc->costs[i])) return r;
+  if (desc->model == TO_MODEL_HYBRID_DOUBLE_INTEGRATOR) {
+    const double S = desc->model_params[1];
+    if (!(S >= 1.0) || !(S <= (double)(N - 2)) || S != std::floor(S))
+      return fail(TO_ERR_ARGUMENT, "hybrid double integrator: params[1] (time steps of the first model) must be an integer in 1 .. N-2");
+  }
+  if (desc->model == TO_MODEL_VECTOR) if (int r = lower_step_models(desc->step_models, N, &lp.step_table)) return r;  // validated like RD.dims(models)
+  std::vector<int>& cost_index = lp.cost_index;
+  cost_index.resize(N);
+  if (desc->cost_index) {
+    for (int k = 0; k < N; ++k) {
+      if (desc->cost_index[k] < 0 || desc->cost_index[k] >= desc->n_costs) return fail(TO_ERR_DIMENSION_MISMATCH, "cost_index outside the cost list");
+      cost_index[k] = desc->cost_index[k];
+    }
+  } else {
+    if (desc->n_costs < 2) return fail(TO_ERR_ARGUMENT, "Objective(stage, terminal, N) needs two cost functions");
+    for (int k = 0; k < N; ++k) cost_index[k] = (k == N - 1) ? 1 : 0;
+  }
+  if (desc->n_constraints < 0 || (desc->n_constraints > 0 && !desc->constraints)) return fail(TO_ERR_ARGUMENT, "bad constraint list");
+  for (int i = 0; i < desc->n_constraints; ++i) {
+    DevCon ci;
+    if (int r = validate_constraint(n, m, N, desc->constraints[i], &ci)) return r;
+    ci.dual_off = lp.n_duals;
+    lp.n_duals += (long long)ci.p * (ci.k2 - ci.k1 + 1);
+    lp.cons.push_back(ci);
+  }
+  *out = std::move(lp);
+  return TO_OK;
+}
+
+// to_set_constraint_params_batch: params[p, B] -> the shift of z = [x; u] the constraint sees, shift[nz, B] (DevProblem::cp).  GOAL, params =
+// xf_b[inds]: target xf + d is the shared constraint at x - d.  LINEAR, params = b_b: A z[inds] - (b + db) = A (z[inds] - dz) - b with the
+// minimum-norm dz = A'(A A')^-1 db, which needs linearly independent rows.
+inline int lower_constraint_params(const DevCon& ci, int nz, int B, const double* params /* [p, B] */, std::vector<double>* shift_out /* [nz, B] */) {
+  if (ci.d.kind != TO_CON_GOAL && ci.d.kind != TO_CON_LINEAR)
+    return fail(TO_ERR_UNSUPPORTED, "per-trajectory constraint parameters: GoalConstraint (its target) and LinearConstraint (its b) only");
+  const int p = ci.p;
+  std::vector<double> shift((size_t)nz * B, 0.0);
+  if (ci.d.kind == TO_CON_GOAL) {
+    for (int b = 0; b < B; ++b)
+      for (int r = 0; r < p; ++r) shift[(size_t)(ci.d.inds[r] - 1) + (size_t)nz * b] = params[r + (size_t)p * b] - ci.d.params[r];
+  } else {
+    const int D = ci.d.n_inds;
+    const double* A = ci.d.params;          // p x D, column-major
+    const double* b0 = ci.d.params + (size_t)p * D;
+    std::vector<double> G((size_t)p * p, 0.0), Lc((size_t)p * p, 0.0), w(p), y(p);
+    double gmax = 0.0;
+    for (int i = 0; i < p; ++i)
+      for (int j = 0; j < p; ++j) { double t = 0.0; for (int c = 0; c < D; ++c) t += A[i + (size_t)p * c] * A[j + (size_t)p * c]; G[i + (size_t)p * j] = t; if (i == j) gmax = std::fmax(gmax, t); }
+    for (int j = 0; j < p; ++j) {  // Cholesky of A A'
+      double d = G[j + (size_t)p * j];
+      for (int k = 0; k < j; ++k) d -= Lc[j + (size_t)p * k] * Lc[j + (size_t)p * k];
+      if (!(d > 1e-12 * gmax)) return fail(TO_ERR_UNSUPPORTED, "per-trajectory b of a LinearConstraint: the rows of A must be linearly independent");
+      Lc[j + (size_t)p * j] = std::sqrt(d);
+      for (int i = j + 1; i < p; ++i) {
+        double t = G[i + (size_t)p * j];
+        for (int k = 0; k < j; ++k) t -= Lc[i + (size_t)p * k] * Lc[j + (size_t)p * k];
+        Lc[i + (size_t)p * j] = t / Lc[j + (size_t)p * j];
+      }
+    }
+    for (int b = 0; b < B; ++b) {
+      for (int i = 0; i < p; ++i) { double t = params[i + (size_t)p * b] - b0[i]; for (int k = 0; k < i; ++k) t -= Lc[i + (size_t)p * k] * y[k]; y[i] = t / Lc[i + (size_t)p * i]; }
+      for (int i = p - 1; i >= 0; --i) { double t = y[i]; for (int k = i + 1; k < p; ++k) t -= Lc[k + (size_t)p * i] * w[k]; w[i] = t / Lc[i + (size_t)p * i]; }
+      for (int c = 0; c < D; ++c) { double t = 0.0; for (int i = 0; i < p; ++i) t += A[i + (size_t)p * c] * w[i]; shift[(size_t)(ci.d.inds[c] - 1) + (size_t)nz * b] += t; }
+    }
+  }
+  shift_out->swap(shift);
+  return TO_OK;
+}
+
+// to_set_cost_linear_batch (DevProblem::gl): q[n, B] / r[m, B] as the difference from the descriptor's, which the kernels ADD to the shared
+// terms; a NULL argument leaves its output alone.  cost_linear_zero: the rows [n + m, B] a cost starts over with behind to_set_cost.
+inline int cost_linear_delta(const to_cost_desc& c, int n, int m, int B, const double* q, const double* r, std::vector<double>* dq, std::vector<double>* dr) {
+  if (!q && !r) return fail(TO_ERR_NULL, "null pointer");
+  if (c.kind == TO_COST_ERROR_QUADRATIC) return fail(TO_ERR_UNSUPPORTED, "per-trajectory linear terms: not for ErrorQuadratic (its q slot carries x_ref)");
+  if (q) {
+    dq->resize((size_t)n * B);
+    for (int b = 0; b < B; ++b) for (int i = 0; i < n; ++i) (*dq)[i + (size_t)n * b] = q[i + (size_t)n * b] - c.q[i];
+  }
+  if (r) {
+    dr->resize((size_t)m * B);
+    for (int b = 0; b < B; ++b) for (int j = 0; j < m; ++j) (*dr)[j + (size_t)m * b] = r[j + (size_t)m * b] - c.r[j];
+  }
+  return TO_OK;
+}
+inline void cost_linear_zero(int n, int m, int B, std::vector<double>* rows) { rows->assign((size_t)(n + m) * B, 0.0); }
+
+// THE rule for a second set of model parameters pp[16] next to the problem's mp (model_key as in TrackFacts): the entries that select dimensions
+// or the attitude representation must be equal.  Key 8 (model vector) takes no such set.  (to_set_model_params_batch never gets here with a key
+// above 4: plants_supported refuses first.)
+inline bool all_finite(const double* v, int n) { for (int i = 0; i < n; ++i) if (!std::isfinite(v[i])) return false; return true; }
+inline bool plant_params_compatible(int key, const double* mp, const double* pp) {
+  auto same = [&](int i) { return pp[i] == mp[i]; };
+  if (key == 8) return false;
+  if (key <= 2 || key == 7) return same(1);         // double integrator: D; hybrid double integrator: S
+  if (key >= 4 && key <= 6) return same(10);        // Quadrotor: rotation
+  if (key == 9 || key == 10) return same(15) && same(1);  // InfeasibleModel: the base model, and its D
+  if (key == 11) return same(15);
+  return true;
+}
+// The refusal of one set.  need_finite: a plant the problem is PLANNED on (to_set_model_params_batch: "the parameters", every entry finite); else
+// one a rollout simulates ("plant_params").  where: "" or " of <which one>"; a caller with many sets asks the predicates first and formats once.
+inline int validate_plant_params(const char* who, int key, const double* mp, const double* pp, bool need_finite, const std::string& where) {
+  if (key == 8) return fail(TO_ERR_ARGUMENT, std::string(who) + ": a model vector takes no plant_params (its models live in the step table)");
+  for (int i = 0; need_finite && i < 16; ++i)
+    if (!std::isfinite(pp[i])) return fail(TO_ERR_ARGUMENT, std::string(who) + ": entry " + std::to_string(i) + where + " is not finite");
+  if (!plant_params_compatible(key, mp, pp))
+    return fail(TO_ERR_ARGUMENT, std::string(who) + ": " + (need_finite ? "the parameters" : "plant_params") + where +
+                                     " change the model's dimensions or attitude representation");
   return TO_OK;
 }
 

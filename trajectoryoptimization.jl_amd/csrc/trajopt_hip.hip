@@ -22,6 +22,7 @@
 #include "k_generic.h"
 #include "k_mpc.h"
 #include "k_track.h"
+#include "policy_lower.h"
 #include "solve_loop.h"
 
 using namespace to;
@@ -926,56 +927,13 @@ int to_default_options(to_solver_opts* o) { CHECK_P(o); default_opts(o); return 
 
 int to_create(const to_problem_desc* desc, const to_solver_opts* opts, int device, to_handle** out) {
   CHECK_P(out);
-  if (!desc) return fail(TO_ERR_NULL, "null descriptor");
-  if (desc->abi_version != TO_ABI_VERSION) return fail(TO_ERR_ARGUMENT, "ABI version mismatch");
-  if (opts) TRY(validate_opts(*opts));
-  int n, m, ne, key;
-  if (model_dims(desc->model, desc->model_params, &n, &m, &ne, &key)) return fail(TO_ERR_UNSUPPORTED, "unknown model");
-  if (desc->n != n || desc->m != m) return fail(TO_ERR_DIMENSION_MISMATCH, "Objective state/control dimensions don't match model.");  // src/problem.jl:65-68
-  if (desc->N < 2) return fail(TO_ERR_ASSERTION, "length(models) == N-1 requires N >= 2");                                         // src/problem.jl:49
-  if (desc->B < 1) return fail(TO_ERR_ARGUMENT, "batch must be positive");
-  if (!(desc->tf > desc->t0)) return fail(TO_ERR_ASSERTION, "tf > t0");                                                             // src/problem.jl:50
-  if (desc->integrator < TO_RK4 || desc->integrator > TO_EULER) return fail(TO_ERR_UNSUPPORTED, "unknown integrator");
-  const int N = desc->N, B = desc->B;
-  std::vector<double> dt(N - 1);
-  if (desc->dt) {
-    double s = 0;
-    for (int k = 0; k < N - 1; ++k) { dt[k] = desc->dt[k]; s += dt[k]; if (!(dt[k] > 0)) return fail(TO_ERR_ASSERTION, "dt must be positive"); }
-    if (std::fabs(s - (desc->tf - desc->t0)) > 1e-8 * std::fmax(1.0, std::fabs(desc->tf - desc->t0)))
-      return fail(TO_ERR_ASSERTION, "time(Z[end]) ≈ tf: time steps are inconsistent with the final time");                          // src/problem.jl:52
-  } else {
-    for (int k = 0; k < N - 1; ++k) dt[k] = (desc->tf - desc->t0) / (N - 1);
-  }
-  if (desc->n_costs < 1 || !desc->costs) return fail(TO_ERR_ARGUMENT, "objective needs at least one cost function");
-  const int rot = desc->model == TO_MODEL_QUADROTOR ? (int)desc->model_params[10] : -1;
-  for (int i = 0; i < desc->n_costs; ++i) TRY(validate_cost(n, rot, desc->costs[i]));
-  if (desc->model == TO_MODEL_HYBRID_DOUBLE_INTEGRATOR) {
-    const double S = desc->model_params[1];
-    if (!(S >= 1.0) || !(S <= (double)(N - 2)) || S != std::floor(S))
-      return fail(TO_ERR_ARGUMENT, "hybrid double integrator: params[1] (time steps of the first model) must be an integer in 1 .. N-2");
-  }
-  std::vector<double> step_table;  // TO_MODEL_VECTOR: the per-step model table (models.h ModelVectorModel), validated like RD.dims(models)
-  if (desc->model == TO_MODEL_VECTOR) TRY(lower_step_models(desc->step_models, N, &step_table));
-  std::vector<int> cost_index(N);
-  if (desc->cost_index) {
-    for (int k = 0; k < N; ++k) {
-      if (desc->cost_index[k] < 0 || desc->cost_index[k] >= desc->n_costs) return fail(TO_ERR_DIMENSION_MISMATCH, "cost_index outside the cost list");
-      cost_index[k] = desc->cost_index[k];
-    }
-  } else {
-    if (desc->n_costs < 2) return fail(TO_ERR_ARGUMENT, "Objective(stage, terminal, N) needs two cost functions");
-    for (int k = 0; k < N; ++k) cost_index[k] = (k == N - 1) ? 1 : 0;
-  }
-  if (desc->n_constraints < 0 || (desc->n_constraints > 0 && !desc->constraints)) return fail(TO_ERR_ARGUMENT, "bad constraint list");
-  std::vector<DevCon> cons;
-  long long n_duals = 0;
-  for (int i = 0; i < desc->n_constraints; ++i) {
-    DevCon ci;
-    TRY(validate_constraint(n, m, N, desc->constraints[i], &ci));
-    ci.dual_off = n_duals;
-    n_duals += (long long)ci.p * (ci.k2 - ci.k1 + 1);
-    cons.push_back(ci);
-  }
+  LoweredProblem lp;
+  TRY(lower_problem(desc, opts, &lp));  // every refusal of the descriptor and the options, and the host tables (desc_lower.h)
+  const int n = lp.n, m = lp.m, ne = lp.ne, key = lp.key, N = desc->N, B = desc->B;
+  const std::vector<double>& dt = lp.dt;
+  const std::vector<int>& cost_index = lp.cost_index;
+  const std::vector<DevCon>& cons = lp.cons;
+  const long long n_duals = lp.n_duals;
   int ndev = 0;
   {
     hipError_t e = hipGetDeviceCount(&ndev);
@@ -992,7 +950,7 @@ int to_create(const to_problem_desc* desc, const to_solver_opts* opts, int devic
   if (!h->ops || !h->ops->rollout[0] || !h->ops->expand[0] || !h->ops->backward) { delete h; return fail(TO_ERR_UNSUPPORTED, "model kernels not linked"); }
   h->traits = path_traits(*h->ops);
   h->costs.assign(desc->costs, desc->costs + desc->n_costs);
-  h->cons = cons; h->dt = dt; h->cost_index = cost_index; h->step_table = step_table;
+  h->cons = cons; h->dt = dt; h->cost_index = cost_index; h->step_table = lp.step_table;
   auto bail = [&](int rc) { std::string e = g_err; to_destroy(h); g_err = e; return rc; };
 #define TRYB(expr) do { int r_ = (expr); if (r_ != TO_OK) return bail(r_); } while (0)
 #define HIPB(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return bail(fail(TO_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_))); } while (0)
@@ -1270,7 +1228,8 @@ int to_set_cost(to_handle* h, int32_t id, const to_cost_desc* c) {
   h->costs[id] = *c;
   if (h->d_gl) {  // the cost's per-trajectory linear terms start over (they were relative to the old descriptor)
     const int nz = h->a.P.n + h->a.P.m, L = (int)h->costs.size() * nz;
-    std::vector<double> zero((size_t)nz * h->a.P.B, 0.0);
+    std::vector<double> zero;
+    cost_linear_zero(h->a.P.n, h->a.P.m, h->a.P.B, &zero);
     TRY(upload_vec(h, zero.data(), h->d_gl, nz, L, id * nz));
     h->gl_set[id] = 0;
     null_unless_any(&h->a.P.gl, h->gl_set, [](char f) { return f != 0; });  // every cost is back on its shared descriptor: the default forward variants again
@@ -1285,23 +1244,13 @@ int to_set_cost(to_handle* h, int32_t id, const to_cost_desc* c) {
 int to_set_cost_linear_batch(to_handle* h, int32_t id, const double* q, const double* r) {
   CHECK_H(h); CHECK_IDLE(h); TRY(use_device(h));
   if (id < 0 || id >= (int)h->costs.size()) return fail(TO_ERR_ARGUMENT, "cost id out of range");
-  if (!q && !r) return fail(TO_ERR_NULL, "null pointer");
-  const to_cost_desc& c = h->costs[id];
-  if (c.kind == TO_COST_ERROR_QUADRATIC) return fail(TO_ERR_UNSUPPORTED, "per-trajectory linear terms: not for ErrorQuadratic (its q slot carries x_ref)");
   DevProblem& P = h->a.P;
-  const int n = P.n, m = P.m, nz = n + m, L = (int)h->costs.size() * nz, B = P.B;
+  const int n = P.n, m = P.m, nz = n + m, L = (int)h->costs.size() * nz;
+  std::vector<double> dq, dr;  // the differences from the descriptor's q / r (desc_lower.h)
+  TRY(cost_linear_delta(h->costs[id], n, m, P.B, q, r, &dq, &dr));
   TRY(ensure_gl(h));
-  std::vector<double> delta;
-  if (q) {  // stored as the difference from the descriptor's q: the kernels ADD it to what the shared code path computes
-    delta.resize((size_t)n * B);
-    for (int b = 0; b < B; ++b) for (int i = 0; i < n; ++i) delta[i + (size_t)n * b] = q[i + (size_t)n * b] - c.q[i];
-    TRY(upload_vec(h, delta.data(), h->d_gl, n, L, id * nz));
-  }
-  if (r) {
-    delta.resize((size_t)m * B);
-    for (int b = 0; b < B; ++b) for (int j = 0; j < m; ++j) delta[j + (size_t)m * b] = r[j + (size_t)m * b] - c.r[j];
-    TRY(upload_vec(h, delta.data(), h->d_gl, m, L, id * nz + n));
-  }
+  if (q) TRY(upload_vec(h, dq.data(), h->d_gl, n, L, id * nz));
+  if (r) TRY(upload_vec(h, dr.data(), h->d_gl, m, L, id * nz + n));
   P.gl = h->d_gl;
   h->gl_set[id] = 1;
   return TO_OK;
@@ -1337,41 +1286,10 @@ int to_set_constraint_params_batch(to_handle* h, int32_t id, const double* param
   CHECK_H(h); CHECK_IDLE(h); CHECK_P(params); TRY(use_device(h));
   if (id < 0 || id >= (int)h->cons.size()) return fail(TO_ERR_ARGUMENT, "constraint id out of range");
   DevCon& ci = h->cons[id];
-  if (ci.d.kind != TO_CON_GOAL && ci.d.kind != TO_CON_LINEAR)
-    return fail(TO_ERR_UNSUPPORTED, "per-trajectory constraint parameters: GoalConstraint (its target) and LinearConstraint (its b) only");
   DevProblem& P = h->a.P;
-  const int n = P.n, nz = P.n + P.m, B = P.B, p = ci.p, L = nz * (int)h->cons.size();
-  std::vector<double> shift((size_t)nz * B, 0.0);
-  if (ci.d.kind == TO_CON_GOAL) {
-    for (int b = 0; b < B; ++b)
-      for (int r = 0; r < p; ++r) shift[(size_t)(ci.d.inds[r] - 1) + (size_t)nz * b] = params[r + (size_t)p * b] - ci.d.params[r];
-  } else {
-    // A z[inds] - (b + db) = A (z[inds] - dz) - b with the minimum-norm dz = A'(A A')^-1 db: needs linearly independent rows
-    const int D = ci.d.n_inds;
-    const double* A = ci.d.params;          // p x D, column-major
-    const double* b0 = ci.d.params + (size_t)p * D;
-    std::vector<double> G((size_t)p * p, 0.0), Lc((size_t)p * p, 0.0), w(p), y(p);
-    double gmax = 0.0;
-    for (int i = 0; i < p; ++i)
-      for (int j = 0; j < p; ++j) { double t = 0.0; for (int c = 0; c < D; ++c) t += A[i + (size_t)p * c] * A[j + (size_t)p * c]; G[i + (size_t)p * j] = t; if (i == j) gmax = std::fmax(gmax, t); }
-    for (int j = 0; j < p; ++j) {  // Cholesky of A A'
-      double d = G[j + (size_t)p * j];
-      for (int k = 0; k < j; ++k) d -= Lc[j + (size_t)p * k] * Lc[j + (size_t)p * k];
-      if (!(d > 1e-12 * gmax)) return fail(TO_ERR_UNSUPPORTED, "per-trajectory b of a LinearConstraint: the rows of A must be linearly independent");
-      Lc[j + (size_t)p * j] = std::sqrt(d);
-      for (int i = j + 1; i < p; ++i) {
-        double t = G[i + (size_t)p * j];
-        for (int k = 0; k < j; ++k) t -= Lc[i + (size_t)p * k] * Lc[j + (size_t)p * k];
-        Lc[i + (size_t)p * j] = t / Lc[j + (size_t)p * j];
-      }
-    }
-    for (int b = 0; b < B; ++b) {
-      for (int i = 0; i < p; ++i) { double t = params[i + (size_t)p * b] - b0[i]; for (int k = 0; k < i; ++k) t -= Lc[i + (size_t)p * k] * y[k]; y[i] = t / Lc[i + (size_t)p * i]; }
-      for (int i = p - 1; i >= 0; --i) { double t = y[i]; for (int k = i + 1; k < p; ++k) t -= Lc[k + (size_t)p * i] * w[k]; w[i] = t / Lc[i + (size_t)p * i]; }
-      for (int c = 0; c < D; ++c) { double t = 0.0; for (int i = 0; i < p; ++i) t += A[i + (size_t)p * c] * w[i]; shift[(size_t)(ci.d.inds[c] - 1) + (size_t)nz * b] += t; }
-    }
-    (void)n;
-  }
+  const int nz = P.n + P.m, L = nz * (int)h->cons.size();
+  std::vector<double> shift;
+  TRY(lower_constraint_params(ci, nz, P.B, params, &shift));  // the kind refusal, the GOAL scatter, the LINEAR minimum-norm shift (desc_lower.h)
   if (!h->d_cp) TRY(dev_alloc(h, &h->d_cp, (size_t)L * P.Bp));  // zero-filled
   TRY(upload_vec(h, shift.data(), h->d_cp, nz, L, id * nz));
   ci.cp_off = id * nz;
@@ -1466,15 +1384,10 @@ int to_set_model_params_batch(to_handle* h, const double* params) {
   CHECK_H(h); CHECK_IDLE(h); CHECK_P(params); TRY(use_device(h));
   TRY(plants_supported(h, "to_set_model_params_batch", "model parameters"));
   DevProblem& P = h->a.P;
-  const int B = P.B, key = h->model_key;
-  for (int b = 0; b < B; ++b) {
+  for (int b = 0; b < P.B; ++b) {
     const double* pp = params + (size_t)16 * b;
-    for (int i = 0; i < 16; ++i)
-      if (!std::isfinite(pp[i]))
-        return fail(TO_ERR_ARGUMENT, "to_set_model_params_batch: entry " + std::to_string(i) + " of trajectory " + std::to_string(b) + " is not finite");
-    const bool ok = key <= 2 ? pp[1] == P.mp[1] : key == 4 ? pp[10] == P.mp[10] : true;  // double integrator: D; Quadrotor: rotation
-    if (!ok) return fail(TO_ERR_ARGUMENT, "to_set_model_params_batch: the parameters of trajectory " + std::to_string(b) +
-                                              " change the model's dimensions or attitude representation");
+    if (!all_finite(pp, 16) || !plant_params_compatible(h->model_key, P.mp, pp))
+      return validate_plant_params("to_set_model_params_batch", h->model_key, P.mp, pp, true, " of trajectory " + std::to_string(b));
   }
   TRY(upload_plants(h, params));
   h->pm_own = true;
@@ -1649,109 +1562,26 @@ int to_backward(to_handle* h) {
 }
 
 // ---- closed-loop policy rollouts (k_policy.h) -------------------------------------------------------------------------------------
-// Entries of model_params that select dimensions or the attitude representation: a simulated plant must share them with the problem.
-static int check_plant_params(const to_handle* h, const double* pp, const std::string& where = "") {
-  const double* mp = h->a.P.mp;
-  const int key = h->model_key;
-  auto same = [&](int i) { return pp[i] == mp[i]; };
-  bool ok = true;
-  if (key <= 2 || key == 7) ok = same(1);                 // double integrator: D; hybrid double integrator: S
-  else if (key >= 4 && key <= 6) ok = same(10);           // Quadrotor: rotation
-  else if (key == 8) return fail(TO_ERR_ARGUMENT, "to_policy_rollout: a model vector takes no plant_params (its models live in the step table)");
-  else if (key == 9 || key == 10) ok = same(15) && same(1);
-  else if (key == 11) ok = same(15);
-  if (!ok) return fail(TO_ERR_ARGUMENT, "to_policy_rollout: plant_params" + where + " change the model's dimensions or attitude representation");
-  return TO_OK;
-}
-// One closed-loop rollout as its entry points (to_policy_rollout, to_policy_rollout_mc, to_mpc_advance) share it: the validated options as
-// the kernel's argument block, the kernel instance, the lane map and the per-sample arrays (policy_prepare), then the staging pair of one
-// chunk of waves (policy_staging).  What differs is where the start states come from and where the closed-loop trajectory goes.
-struct PolicyRun {
-  PolicyArgs pa;
-  int nz = 0;          // the kernel's NZ: bit 0 process noise, bit 1 measurement noise, bit 2 one plant per sample
-  bool packed = true;  // lane map
-  int waves = 0;
-  size_t SB = 0;
-  PolicyPlan plan;     // every length below comes from here (path_plan.h plan_policy)
-  std::vector<double> own_plants;  // the handle's per-trajectory plants repeated per sample (alive until the entry point returns)
-};
+// PolicyRun, and everything its entry points check and compute on the host before the first device call: policy_lower.h.
 static int policy_launch(to_handle* h, const PolicyRun& r, const PolicyArgs& a, int w) {
   return r.nz ? h->ops->policy_rollout_mc(h, a, w, r.nz) : h->ops->policy_rollout(h, a, w);
 }
-// noise == NULL (or nothing set in it) is to_policy_rollout itself, the NZ = 0 kernel and nothing else.  force_packed: the packed lane map
-// whatever TRAJOPT_POLICY_MAP says (to_mpc_advance: its S = 1 staging blocks must have the row layout of the nominal tiles, k_mpc.h)
+// The host half of a run — every refusal, the argument block, the lane map, the plan, the per-sample plants — is policy_lower.h
+// lower_policy_opts; here: the gain refresh, the per-sample arrays (grown on demand), their pointers and the plants copy.
 static int policy_prepare(to_handle* h, int32_t S, const to_policy_opts* opts, const to_policy_noise* noise, bool force_packed, PolicyRun* run) {
-  if (S < 1) return fail(TO_ERR_ARGUMENT, "to_policy_rollout: S must be >= 1");
-  if (!h->ops->policy_rollout) return fail(TO_ERR_UNSUPPORTED, "policy rollout not compiled for this model");
-  to_policy_opts o = {1, 0, 0.0, nullptr, nullptr, nullptr};
-  if (opts) o = *opts;
-  if (o.refresh_gains != 0 && o.refresh_gains != 1) return fail(TO_ERR_ARGUMENT, "to_policy_rollout: refresh_gains must be 0 or 1");
-  if (!std::isfinite(o.alpha)) return fail(TO_ERR_ARGUMENT, "to_policy_rollout: alpha must be finite");
-  if (o.plant_params) TRY(check_plant_params(h, o.plant_params));
   const DevProblem& P = h->a.P;
-  const int n = P.n, m = P.m, B = P.B;
+  const ModelOps& ops = *h->ops;
+  const PolicyFacts facts{h->model_key, P.mp, P.n, P.m, P.ne, P.N, P.B, P.pm != nullptr, P.dtb != nullptr, h->pm_host.data(),
+                          ops.policy_rollout != nullptr, ops.policy_rollout_mc != nullptr, ops.policy_noise_mask, ops.lds_gains ? ops.gains_lds_pieces : 0,
+                          std::getenv("TRAJOPT_POLICY_MAP"), std::getenv("TRAJOPT_POLICY_CHUNK_WAVES")};
+  const double* plants_src = nullptr;
+  TRY(lower_policy_opts(facts, S, opts, noise, force_packed, run, &plants_src));
   PolicyArgs& pa = run->pa;
-  std::memset(&pa, 0, sizeof(pa));
-  int& nz = run->nz;
-  nz = 0;
-  if (noise) {
-    const int ne = P.ne;
-    if ((noise->sigma_w || noise->sigma_v) && (h->model_key == 7 || h->model_key == 8))
-      return fail(TO_ERR_UNSUPPORTED, "to_policy_rollout_mc: sigma_w / sigma_v on a hybrid model or a model vector (their padded coordinates must stay "
-                                      "exactly 0 and their live dimensions change per knot)");
-    for (int kind = 0; kind < 2; ++kind) {
-      const double* sg = kind == 0 ? noise->sigma_w : noise->sigma_v;
-      if (!sg) continue;
-      for (int i = 0; i < ne; ++i) {
-        if (!std::isfinite(sg[i]) || sg[i] < 0.0)
-          return fail(TO_ERR_ARGUMENT, std::string("to_policy_rollout_mc: ") + (kind == 0 ? "sigma_w" : "sigma_v") + " must be finite and >= 0");
-        (kind == 0 ? pa.sigma_w : pa.sigma_v)[i] = sg[i];
-      }
-      nz |= 1 << kind;
-    }
-    if (noise->plant_params) {
-      if (o.plant_params) return fail(TO_ERR_ARGUMENT, "to_policy_rollout_mc: plant_params given both in the options (one plant) and in the noise (one per sample)");
-      for (int b = 0; b < B; ++b)
-        for (int s = 0; s < S; ++s)
-          TRY(check_plant_params(h, noise->plant_params + ((size_t)b * S + s) * 16, " of sample (b = " + std::to_string(b) + ", s = " + std::to_string(s) + ")"));
-      nz |= 4;
-    }
-    pa.seed = noise->seed; pa.traj_offset = noise->traj_offset; pa.sample_offset = noise->sample_offset;
-  }
-  // A handle planned on one plant per trajectory (to_set_model_params_batch) simulates each trajectory on ITS plant when the caller names none:
-  // the host fills the per-sample plants array and the one-plant-per-sample instance runs (an explicit plant, shared or per sample, overrides)
-  const double* plants_src = (noise && noise->plant_params) ? noise->plant_params : nullptr;
-  std::vector<double>& own_plants = run->own_plants;
-  // (a handle with per-trajectory time steps, DevProblem::dtb, always takes a one-plant-per-sample instance — only those read the steps per
-  // trajectory — so there an explicit shared plant is repeated for every sample)
-  if (P.pm && !plants_src && (!o.plant_params || P.dtb)) {
-    own_plants.resize((size_t)16 * S * B);
-    for (int b = 0; b < B; ++b)
-      for (int s = 0; s < S; ++s)
-        std::memcpy(&own_plants[((size_t)b * S + s) * 16], o.plant_params ? o.plant_params : &h->pm_host[(size_t)16 * b], sizeof(double) * 16);
-    plants_src = own_plants.data();
-    nz |= 4;
-  }
-  if (nz && (!h->ops->policy_rollout_mc || (nz & ~h->ops->policy_noise_mask)))
-    return fail(TO_ERR_UNSUPPORTED, "to_policy_rollout_mc: not compiled for this model");
-  // lane map, waves and every buffer length: path_plan.h plan_policy
-  const PolicyPlan& pl = run->plan = plan_policy(n, m, P.N, B, S, force_packed ? nullptr : std::getenv("TRAJOPT_POLICY_MAP"),
-                                                 std::getenv("TRAJOPT_POLICY_CHUNK_WAVES"), h->ops->lds_gains ? h->ops->gains_lds_pieces : 0);
-  run->packed = pl.packed;
-  pa.S = S; pa.TPW = pl.TPW; pa.WPT = pl.WPT;
-  if (pl.waves > 0x7fffffffLL / 64) return fail(TO_ERR_ARGUMENT, "to_policy_rollout: S * B is too large for one call");
-  run->waves = (int)pl.waves;
-  const size_t SB = run->SB = pl.SB;
-  pa.alpha = o.alpha;
-  pa.clamp = (o.u_min || o.u_max) ? 1 : 0;
-  for (int j = 0; j < TO_MAX_M; ++j) {
-    pa.u_min[j] = (o.u_min && j < m) ? o.u_min[j] : -HUGE_VAL;
-    pa.u_max[j] = (o.u_max && j < m) ? o.u_max[j] : HUGE_VAL;
-    if (!(pa.u_min[j] <= pa.u_max[j])) return fail(TO_ERR_ARGUMENT, "to_policy_rollout: u_min must not exceed u_max");
-  }
-  std::memcpy(pa.mp, o.plant_params ? o.plant_params : P.mp, sizeof(pa.mp));
+  const PolicyPlan& pl = run->plan;
+  const int nz = run->nz;
+  const size_t SB = run->SB;
   TRY(use_device(h));
-  if (o.refresh_gains) { TRY(phase_expand(h)); TRY(phase_backward(h)); }
+  if (run->refresh_gains) { TRY(phase_expand(h)); TRY(phase_backward(h)); }
   if (h->pol_cap < SB) {
     HIPCHECK(hipStreamSynchronize(h->stream));
     dev_release(h, &h->pol_x0s); dev_release(h, &h->pol_J); dev_release(h, &h->pol_cmax); dev_release(h, &h->pol_dxmax);
@@ -1857,28 +1687,11 @@ int to_mpc_advance(to_handle* h, const double* x_meas, const to_mpc_opts* mpc, c
                    const to_mpc_result* out) {
   static_assert(MPC_MAX_M == TO_MAX_M, "MpcArgs::u_fill holds one control");
   CHECK_H(h); CHECK_IDLE(h);
-  if (!mpc) return fail(TO_ERR_NULL, "to_mpc_advance: mpc is NULL");
   const DevProblem& P = h->a.P;
   const int n = P.n, m = P.m, N = P.N, B = P.B;
-  if (h->model_key >= 7)  // a shift changes which model governs a knot (hybrid, model vector); slack controls have no meaning once shifted
-    return fail(TO_ERR_UNSUPPORTED, std::string("to_mpc_advance: not available for the ") + model_key_name(h->model_key) +
-                                        " (TO_MODEL_HYBRID_DOUBLE_INTEGRATOR, TO_MODEL_VECTOR and TO_MODEL_INFEASIBLE cannot shift their plan)");
-  if (mpc->shift < 1 || mpc->shift > N - 2)
-    return fail(TO_ERR_ARGUMENT, "to_mpc_advance: shift must be in 1 .. N-2 = " + std::to_string(N - 2) + "; got " + std::to_string(mpc->shift));
-  if (mpc->guess != TO_MPC_GUESS_CLOSED_LOOP && mpc->guess != TO_MPC_GUESS_NOMINAL)
-    return fail(TO_ERR_ARGUMENT, "to_mpc_advance: guess must be TO_MPC_GUESS_CLOSED_LOOP (0) or TO_MPC_GUESS_NOMINAL (1)");
-  if (mpc->tail != TO_MPC_TAIL_HOLD && mpc->tail != TO_MPC_TAIL_FILL)
-    return fail(TO_ERR_ARGUMENT, "to_mpc_advance: tail must be TO_MPC_TAIL_HOLD (0) or TO_MPC_TAIL_FILL (1)");
-  if (mpc->reserved != 0) return fail(TO_ERR_ARGUMENT, "to_mpc_advance: reserved must be 0");
   MpcArgs ma;
   std::memset(&ma, 0, sizeof(ma));
-  if (mpc->tail == TO_MPC_TAIL_FILL) {
-    if (!mpc->u_fill) return fail(TO_ERR_NULL, "to_mpc_advance: TO_MPC_TAIL_FILL needs u_fill");
-    for (int j = 0; j < m; ++j) {
-      if (!std::isfinite(mpc->u_fill[j])) return fail(TO_ERR_ARGUMENT, "to_mpc_advance: u_fill must be finite");
-      ma.u_fill[j] = mpc->u_fill[j];
-    }
-  }
+  TRY(lower_mpc_opts(MpcFacts{h->model_key, model_key_name(h->model_key), N, m}, mpc, ma.u_fill));  // every refusal of to_mpc_opts (policy_lower.h)
   PolicyRun run;
   TRY(policy_prepare(h, 1, popts, noise, true, &run));  // (S = 1, packed: wave g = tile g, lane = b & 63)
   PolicyArgs& pa = run.pa;
