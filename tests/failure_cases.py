@@ -101,7 +101,7 @@ def _cartpole(B=70, N=41, tf=2.0, Qf=(100.0, 100.0, 100.0, 100.0), constrained=F
     return build
 
 
-def _double_integrator(B=70, N=21, tf=2.0, R=(0.1, 0.1), Qf=(10.0, 10.0, 10.0, 10.0), u_bnd=None, amp=1.0, **base):
+def _double_integrator(B=70, N=21, tf=2.0, R=(0.1, 0.1), Qf=(10.0, 10.0, 10.0, 10.0), u_bnd=None, amp=1.0, integration=T.RK4, **base):
     """2-D double integrator (m = 2).  A linear model with a quadratic cost has the same Quu for every trajectory; the control bounds
     bring the trajectories apart: every violated bound adds its penalty to Quu's diagonal, knot by knot."""
     def build(lib, extra):
@@ -114,7 +114,7 @@ def _double_integrator(B=70, N=21, tf=2.0, R=(0.1, 0.1), Qf=(10.0, 10.0, 10.0, 1
             T.add_constraint(cons, T.BoundConstraint(n, m, u_min=-u_bnd, u_max=u_bnd), range(1, N))
             T.add_constraint(cons, T.GoalConstraint(xf), N)
         o = _options(lib, base, extra)
-        p = T.Problem(model, obj, np.zeros(n), tf, xf=xf, constraints=cons, batch=B, lib=lib, options=o)
+        p = T.Problem(model, obj, np.zeros(n), tf, xf=xf, constraints=cons, batch=B, lib=lib, options=o, integration=integration)
         p.case_options = o
         p.set_initial_state(np.linspace(-0.5, 0.5, B)[(17 * np.arange(B)) % B][:, None] * np.ones((B, n)))   # (scattered like the amplitudes, not with them)
         b, k = np.arange(B)[:, None, None], np.arange(N - 1)[None, :, None]

@@ -1261,7 +1261,7 @@ def test_line_search_deeper_than_the_deep_shape(hip, oracle, monkeypatch):
     np.testing.assert_allclose(sols[1][1], T.states(po), rtol=1e-6, atol=1e-8)
 
 
-def _mrp_quadrotor(lib, constrained, batch, N=41, tf=2.0):
+def _mrp_quadrotor(lib, constrained, batch, N=41, tf=2.0, integration=T.RK4, options=None):
     model = T.Quadrotor(rotation="mrp")
     n, m = model.dims()
     th = math.radians(70.0) / 2
@@ -1273,7 +1273,8 @@ def _mrp_quadrotor(lib, constrained, batch, N=41, tf=2.0):
     if constrained:
         T.add_constraint(cons, T.BoundConstraint(n, m, u_min=0.0, u_max=2.2), range(1, N))
         T.add_constraint(cons, T.GoalConstraint(xf, [1, 2, 3, 7, 8, 9, 10, 11, 12]), N)
-    prob = T.Problem(model, T.Objective(stage, term, N), np.zeros(n), tf, xf=xf, constraints=cons, batch=batch, lib=lib)
+    prob = T.Problem(model, T.Objective(stage, term, N), np.zeros(n), tf, xf=xf, constraints=cons, batch=batch, lib=lib,
+                     integration=integration, options=options)
     rng = np.random.default_rng(11)
     x0 = np.zeros((batch, n)); x0[:, :3] = rng.uniform(-0.5, 0.5, (batch, 3)); x0[:, 3:6] = 0.1 * rng.standard_normal((batch, 3))
     prob.set_initial_state(x0)

@@ -57,7 +57,7 @@ def lqr_reference(steps_2d, N, dt, mass, costs, x0):
     return X, U, J
 
 
-def hybrid_problem(lib, batch=3, constrained=False, steps_2d=5, N=11, tf=2.0, mass=1.3):
+def hybrid_problem(lib, batch=3, constrained=False, steps_2d=5, N=11, tf=2.0, mass=1.3, integration=T.RK4):
     hyb = T.HybridDoubleIntegrator(mass, steps_2d)
     models = hyb.models(N)
     nx, nu = T.dims(models)
@@ -70,7 +70,7 @@ def hybrid_problem(lib, batch=3, constrained=False, steps_2d=5, N=11, tf=2.0, ma
         T.add_constraint(cons, T.BoundConstraint(2, 1, u_max=0.6, u_min=-0.6, x_max=[10, np.inf]), range(steps_2d + 2, N))
         T.add_constraint(cons, T.GoalConstraint(np.array([0.3, -0.2])), N)
     x0 = np.array([0.5, -0.4, 0.2, 0.1])
-    prob = T.Problem(models, T.Objective(costs), x0, tf, constraints=cons, batch=batch, lib=lib)
+    prob = T.Problem(models, T.Objective(costs), x0, tf, constraints=cons, batch=batch, lib=lib, integration=integration)
     return prob, costs, x0, hyb
 
 

@@ -30,9 +30,9 @@ def line_guess(x0, xf, N):
     return x0[:, None, :] * (1 - t) + np.asarray(xf)[None, None, :] * t   # positions on a line, velocities inconsistent with them
 
 
-def cartpole_infeasible(lib, B=6, amp=0.3):
+def cartpole_infeasible(lib, B=6, amp=0.3, integration=T.RK4):
     """The constrained Cartpole (bounds + goal) with a state guess its controls cannot produce."""
-    p = configs.cartpole_problem(batch=B, constrained=True, lib=lib)
+    p = configs.cartpole_problem(batch=B, constrained=True, lib=lib, integration=integration)
     T.rollout(p)
     X = T.states(p).copy()
     t = np.linspace(0, 1, p.N)

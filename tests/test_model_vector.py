@@ -25,7 +25,7 @@ def cartpole_mix():
     return [T.DoubleIntegrator(1.0, 2)] * 3 + [T.Cartpole()] * 6 + [j] + [T.DoubleIntegrator(2.0, 1)] * 3
 
 
-def build(models, lib, batch=3, constrained=False, tf=None, seed=5):
+def build(models, lib, batch=3, constrained=False, tf=None, seed=5, integration=T.RK4):
     nx, nu = T.dims(models)
     N = len(models) + 1
     rng = np.random.default_rng(seed)
@@ -36,7 +36,7 @@ def build(models, lib, batch=3, constrained=False, tf=None, seed=5):
         T.add_constraint(cons, T.BoundConstraint(nx[0], nu[0], u_max=0.8, u_min=-0.8), range(1, 3))
         T.add_constraint(cons, T.GoalConstraint(np.array([0.3, -0.2])), N)
     x0 = rng.uniform(-0.4, 0.4, (batch, nx[0]))
-    prob = T.Problem(models, T.Objective(costs), x0[0], tf or 0.1 * (N - 1), constraints=cons, batch=batch, lib=lib)
+    prob = T.Problem(models, T.Objective(costs), x0[0], tf or 0.1 * (N - 1), constraints=cons, batch=batch, lib=lib, integration=integration)
     prob.set_initial_state(np.c_[x0, np.zeros((batch, prob.n - nx[0]))])
     return prob, costs, x0
 
